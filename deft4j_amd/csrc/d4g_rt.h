@@ -96,23 +96,32 @@ struct RtGlobals {
         // in creation order, and a thread that created sixteen streams up front pushed the next thread's main stream back onto
         // the first thread's queue — where that thread's candidate search (one launch of milliseconds) held up the other batch's
         // parse (measured: two batches in flight 9.7 ms per step when they collided, 7.0 when they did not).
+        // For the same reason a lane's header-search stream is made when a persistent or level-executor round first launches on
+        // it: the fused search runs on the state-op stream alone, so every thread makes one stream, and the threads' streams
+        // take HIP's hardware queues in turn.  With both made up front, each thread's state-op stream could take the same queue
+        // as the last thread's (two queues, six batches in flight: 8.3 against 5.7-5.9 ms per step, profiles/stream_creation_ab.json).
         made = true;
         make_lane(0);
     }
-    void make_lane(int k) {
-        if (a[k]) return;
-        int least = 0, greatest = 0;
+    hipStream_t make_stream() {
+        hipStream_t s = nullptr;
         if (rt_low_priority_thread()) {
+            int least = 0, greatest = 0;
             RT_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            RT_CHECK(hipStreamCreateWithPriority(&a[k], hipStreamNonBlocking, least));
-            RT_CHECK(hipStreamCreateWithPriority(&b[k], hipStreamNonBlocking, least));
+            RT_CHECK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least));
         } else {
-            RT_CHECK(hipStreamCreateWithFlags(&a[k], hipStreamNonBlocking));
-            RT_CHECK(hipStreamCreateWithFlags(&b[k], hipStreamNonBlocking));
+            RT_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         }
+        return s;
+    }
+    void make_lane(int k) {
+        if (!a[k]) a[k] = make_stream();
     }
     hipStream_t sa() { make_lane(cur); return a[cur]; }
-    hipStream_t sb() { make_lane(cur); return b[cur]; }
+    hipStream_t sb() {
+        if (!b[cur]) b[cur] = make_stream();
+        return b[cur];
+    }
     void destroy_streams() {
         if (!made) return;
         for (int k = 0; k < RT_MAX_LANES; k++) {

@@ -1,5 +1,6 @@
 import sys, time, zlib, os
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import deft4j_amd as D
 D.init(0)
 cases = {'zeros8M': b'\0'*(8<<20), 'ab8M': b'ab'*(4<<20), 'period259_4M': (os.urandom(259)*(20000))[:4<<20], 'run_mix': b''.join(bytes([i&255])*(300+i%700) for i in range(8000))}

@@ -43,6 +43,10 @@ def main():
                     "sha256_in": hashlib.sha256(data).hexdigest(), "out_len": len(out), "sha256_out": hashlib.sha256(out).hexdigest()})
     json.dump({"proxy": "libzopfli 1.0.3 (master block 1000000)", "cases": man}, open(os.path.join(HERE, "zopfli_manifest.json"), "w"), indent=1)
     print("wrote", len(man), "cases")
+    # ZopfliLengthLimitedCodeLengths on seeded histograms: one byte (code length) per symbol, histograms in order
+    lengths = bytes(b for f, maxbits in Z.length_limited_cases() for b in Z.proxy_length_limited(f, maxbits))
+    open(os.path.join(HERE, "zopfli_length_limited.bin"), "wb").write(lengths)
+    print("wrote", len(lengths), "code lengths")
 
 
 if __name__ == "__main__":

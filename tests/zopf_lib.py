@@ -70,3 +70,25 @@ def proxy_deflate(data, iterations=15, blocksplitting=1, maxblocks=15):
     r = C.string_at(out, n.value)
     C.CDLL(None).free(out)
     return r
+
+
+def length_limited_cases():
+    """(frequencies, maxbits) of the 600 seeded histograms tests/golden/zopfli_length_limited.bin holds the code lengths of."""
+    import random
+    rng = random.Random(3)
+    for n, maxbits in ((288, 15), (32, 15), (19, 7)):
+        for _ in range(200):
+            k = rng.choice((1, 2, 3, n // 2, n))
+            f = [0] * n
+            for i in rng.sample(range(n), k):
+                f[i] = rng.choice((1, 1, 2, 3, rng.randrange(1, 50), rng.randrange(1, 100000)))
+            yield f, maxbits
+
+
+def proxy_length_limited(freqs, maxbits):
+    """libzopfli 1.0.3's ZopfliLengthLimitedCodeLengths — generation of golden vectors only."""
+    n = len(freqs)
+    f = (C.c_size_t * n)(*freqs)
+    o = (C.c_uint * n)()
+    C.CDLL(PROXY_PATH).ZopfliLengthLimitedCodeLengths(f, n, maxbits, o)
+    return list(o)
