@@ -367,6 +367,127 @@ D4G_DEV int d4g_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 D4G_DEV void d4g_wave_sync() { __builtin_amdgcn_wave_barrier(); }  // LDS accesses of one wave are already in order
 #endif
 
+// ---------------------------------------------------------------------------------------
+// The 19-symbol code-length tree of one lane in registers (the header search: one candidate per lane).
+// The same lengths as d4g_build_tree(…, 19, 7, …) for every tree no deeper than 7.  The JDK PriorityQueue is
+// simulated slot by slot with selects over compile-time slot numbers (a dynamically indexed private array
+// would live in scratch).  A queue entry is weight << 19 | the set of leaves (symbols) under the node: a
+// merge is one addition, and a leaf's depth is the number of merged nodes that hold it (byte counters, four
+// per register), so no DFS is needed.  Slots beyond the queue's size hold D4G_CLQ_EMPTY, heavier than any
+// entry (weights stay below 512: at most 316 code-length symbols plus two dummy leaves), so no sift step
+// looks at the size.  A deeper tree needs the limiter: the lane reports it and is rebuilt by d4g_build_tree.
+// ---------------------------------------------------------------------------------------
+#define D4G_CLQ_EMPTY 0xffffffffu
+#define D4G_CLQ_LEAVES 0x7ffffu
+struct D4GClLens {   // code lengths (0..7) as 4-bit fields: symbols 0..15 in lo, 16..18 in hi
+    uint64_t lo;
+    uint32_t hi;
+    D4G_DEV int get(int s) const { return s < 16 ? (int)(lo >> (4 * s)) & 15 : (int)(hi >> (4 * (s - 16))) & 15; }
+};
+constexpr int d4g_cl_level(int i) { return i < 1 ? 0 : i < 3 ? 1 : i < 7 ? 2 : i < 15 ? 3 : 4; }   // heap level of slot i
+struct D4GClQueue {
+    uint32_t q[19];
+    // PriorityQueue.poll on a queue of n >= 2 entries: the root out, the last entry sifted down from the root
+    // (pq_remove of d4g_build_tree: the right child only when the left is strictly heavier, stop when <= child)
+    D4G_DEV uint32_t poll(int n) {
+        const uint32_t res = q[0];
+        const int s = n - 1;
+        uint32_t x = 0;
+#pragma unroll
+        for (int j = 1; j < 19; j++) {
+            const bool at = j == s;
+            x = at ? q[j] : x;
+            q[j] = at ? D4G_CLQ_EMPTY : q[j];
+        }
+        const uint32_t lim = x & ~D4G_CLQ_LEAVES;   // e < lim: e strictly lighter than x
+        int k = 0;
+        bool done = false;
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            uint32_t l = D4G_CLQ_EMPTY, r = D4G_CLQ_EMPTY;
+#pragma unroll
+            for (int j = (1 << d) - 1; j <= (2 << d) - 2; j++) {
+                if (2 * j + 1 < 19) l = k == j ? q[2 * j + 1] : l;
+                if (2 * j + 2 < 19) r = k == j ? q[2 * j + 2] : r;
+            }
+            const bool takeR = l > (r | D4G_CLQ_LEAVES);
+            const uint32_t cv = takeR ? r : l;
+            const bool move = !done && cv < lim;
+            const uint32_t put = move ? cv : x;
+#pragma unroll
+            for (int j = (1 << d) - 1; j <= (2 << d) - 2; j++) q[j] = (!done && k == j) ? put : q[j];
+            k = move ? 2 * k + 1 + (takeR ? 1 : 0) : k;
+            done = !move;
+        }
+#pragma unroll
+        for (int j = 15; j < 19; j++) q[j] = (!done && k == j) ? x : q[j];
+        return res;
+    }
+    // PriorityQueue.offer of x at slot n < N: sift up while strictly lighter than the parent (pq_add).  Every
+    // slot is rewritten from the old values: on x's path to the root, a slot takes its parent's entry when the
+    // parent is strictly heavier than x, else x when its own entry is (the queue is ordered along the path).
+    template <int N>
+    D4G_DEV void offer(uint32_t x, int n) {
+        const uint32_t t = x | D4G_CLQ_LEAVES;     // e > t: e strictly heavier than x
+        const int K = n + 1, lk = 31 - __builtin_clz((unsigned)K);
+        int anc[5];                                 // 1-based ancestor of slot n at each level (0: none)
+#pragma unroll
+        for (int L = 0; L < 5; L++) anc[L] = lk >= L ? K >> (lk - L) : 0;
+#pragma unroll
+        for (int i = N - 1; i >= 0; i--) {
+            const bool on = anc[d4g_cl_level(i)] == i + 1;
+            const uint32_t up = i > 0 ? q[(i - 1) >> 1] : 0u;
+            const bool fromUp = on && i > 0 && up > t;
+            const bool here = on && q[i] > t;
+            q[i] = fromUp ? up : here ? x : q[i];
+        }
+    }
+};
+// the used symbols in order, symbol I at slot n <= I
+template <int I, typename FreqFn>
+D4G_DEV void d4g_cl_offer_leaves(D4GClQueue& Q, FreqFn freq, int& n) {
+    const uint32_t f = freq(I);
+    if (f) { Q.offer<I + 1>((f << 19) | (1u << I), n); n++; }
+    if constexpr (I < 18) d4g_cl_offer_leaves<I + 1>(Q, freq, n);
+}
+// Builds the tree of the 19 counts freq(0..18) (freq is called with constants); returns true when it is deeper
+// than 7 (len is then not set).
+template <typename FreqFn>
+D4G_DEV bool d4g_cl_tree_regs(FreqFn freq, D4GClLens& len) {
+    D4GClQueue Q;
+#pragma unroll
+    for (int j = 0; j < 19; j++) Q.q[j] = D4G_CLQ_EMPTY;
+    int n = 0;
+    d4g_cl_offer_leaves<0>(Q, freq, n);
+    if (n < 2) {   // dummy leaves of weight 1 on the first unused symbols — HuffmanTree.java:50-58
+        Q.offer<2>((1u << 19) | (freq(0) == 0 ? 1u : 2u), n);
+        if (n == 0) Q.offer<2>((1u << 19) | 2u, 1);
+        n = 2;
+    }
+    uint32_t dep[5] = {0, 0, 0, 0, 0};   // leaf depths, one byte per symbol
+    for (int m = n; m > 1; m--) {
+        const uint32_t a = Q.poll(m);
+        const uint32_t b = Q.poll(m - 1);
+        const uint32_t node = a + b;
+        Q.offer<19>(node, m - 2);
+        const uint32_t leaves = node & D4G_CLQ_LEAVES;
+#pragma unroll
+        for (int j = 0; j < 5; j++) dep[j] += (((leaves >> (4 * j)) & 15u) * 0x00204081u) & 0x01010101u;
+    }
+    uint32_t deep = 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++) deep |= (dep[j] + 0x78787878u) & 0x80808080u;   // some byte >= 8
+    uint32_t h[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        const uint32_t y = (dep[j] | (dep[j] >> 4)) & 0x00ff00ffu;   // bytes 0 and 2: two lengths each
+        h[j] = (y & 0xffu) | ((y >> 8) & 0xff00u);
+    }
+    len.lo = (uint64_t)h[0] | ((uint64_t)h[1] << 16) | ((uint64_t)h[2] << 32) | ((uint64_t)h[3] << 48);
+    len.hi = h[4];
+    return deep != 0;
+}
+
 struct D4GWaveHeap {
     int w0, i0;
     uint64_t* deep;   // LDS, slots >= 64: weight << 32 | id

@@ -40,7 +40,7 @@
 #define D4F_SWEEP_K 8     // codes evaluated per sweep over the records
 #define D4F_CODE_FIXED 1  // reserved code id: the fixed Huffman code
 #define D4F_MAXROUNDS 16
-#define D4F_HS_SLOTS 3      // header searches running side by side (one wave each)
+#define D4F_HS_SLOTS 8      // header searches running side by side (one wave each)
 #define D4F_TREE_SLOTS 4   // Huffman rebuilds running side by side (two waves each: literal/length and distance tree)
 
 #ifdef D4G_HOSTSIM
@@ -1622,7 +1622,8 @@ D4F_TASK void d4f_tree_publish(int slotIdx) {
 // ---------------------------------------------------------------------------------------
 // Header search of one code (one wave): the 56 optimiseBlockDynBlock candidates — see d4g_exec_hdr_search
 // ---------------------------------------------------------------------------------------
-D4F_TASK void d4f_hs_task(int slotIdx, int code) {
+// Returns the number of candidates whose code-length tree needed the depth limiter.
+D4F_TASK int d4f_hs_task(int slotIdx, int code) {
     D4FLds& F = d4fLds;
     D4F_CTX;
     D4FHsScr& X = ((D4FHsScr*)&F.least)[slotIdx];
@@ -1678,10 +1679,12 @@ D4F_TASK void d4f_hs_task(int slotIdx, int code) {
     }
     d4g_wave_sync();
     long long key = D4G_KEY_NONE;
+    bool fellBack = false;
     if (lane < 56) {
-        long long size = d4g_hdr_candidate_body(&H, lane, c.hdrFlags[lane], c.hdrPrune[lane], 0LL);
+        long long size = d4g_hdr_candidate_body(&H, lane, c.hdrFlags[lane], c.hdrPrune[lane], 0LL, nullptr, &fellBack);
         key = D4G_MAKE_KEY(size, lane);
     }
+    const int nFallback = __popcll(d4g_ballot(fellBack));
     key = wave_min_i64(key);
     if (lane == 0) {
         F.hsBits[code] = (int32_t)(key >> D4G_KEY_SEQ_BITS);
@@ -1690,6 +1693,7 @@ D4F_TASK void d4f_hs_task(int slotIdx, int code) {
         F.hsState[code] = 2;
     }
     d4g_wave_sync();
+    return nFallback;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2316,7 +2320,8 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int rounds = 0, info = 0;
     // optional accounting (D4G_FUSED_STATS): [0,8) tasks per kind, [8,16) steps per kind, [16,24) cycles per kind, 24 advance,
-    // 25 set-up, 26 selection, 27 rounds, 28 steps, 29 cycles in total, 30 / 31 / 32 masks / codes / headers made
+    // 25 set-up, 26 selection, 27 rounds, 28 steps, 29 cycles in total, 30 / 31 / 32 masks / codes / headers made,
+    // 62 header-search candidates whose code-length tree took the depth limiter
     const bool prof = P.stats != nullptr && threadIdx.x == 0;
     auto acc = [&](int k, long long v) { if (prof) atomicAdd((unsigned long long*)&P.stats[k], (unsigned long long)v); };
     const long long tKernel = prof ? clock64() : 0;
@@ -2471,7 +2476,10 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
             case D4F_Q_HS: {
                 const int nhs = nw < D4F_HS_SLOTS ? nw : D4F_HS_SLOTS;
                 for (int t0 = 0; t0 < nq; t0 += nhs) {
-                    if (wave < nhs && t0 + wave < nq) d4f_hs_task(wave, F.qAll[d4f_qoff(D4F_Q_HS) + t0 + wave]);
+                    if (wave < nhs && t0 + wave < nq) {
+                        const int nfb = d4f_hs_task(wave, F.qAll[d4f_qoff(D4F_Q_HS) + t0 + wave]);
+                        if (P.stats && lane == 0 && nfb) atomicAdd((unsigned long long*)&P.stats[62], (unsigned long long)nfb);
+                    }
                     __syncthreads();
                 }
                 break;
@@ -2512,11 +2520,11 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
         if (rounds >= P.maxRounds || rounds >= D4F_MAXROUNDS) { info |= D4F_INFO_MORE; break; }
     }
     __syncthreads();
-    if (prof) {   // [39] the slowest block, [40, 63) blocks by duration (0.5 M cycles per class)
+    if (prof) {   // [39] the slowest block, [40, 62) blocks by duration (0.5 M cycles per class)
         const long long dt = clock64() - tKernel;
         acc(29, dt);
         atomicMax((unsigned long long*)&P.stats[39], (unsigned long long)dt);
-        const int cls = (int)(dt / 500000) < 22 ? (int)(dt / 500000) : 22;
+        const int cls = (int)(dt / 500000) < 21 ? (int)(dt / 500000) : 21;
         acc(40 + cls, 1);
     }
     if (threadIdx.x == 0) P.roundInfo[which] = rounds | info;

@@ -1518,10 +1518,11 @@ __global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_PERSIST_WAVES) k_p
 // Header search: the 56 optimiseBlockDynBlock candidates of one base block, one lane each.
 // DeflateStream.java:184-198 (rewriteHeader(flags) -> [recodeHeaderToLessRLEMatches] ->
 // optimiseHeader) enumerated in addOptimisedRecoded's loop order (:281-315).
-// Pairs are never stored: each lane re-generates them from the shared code-length runs and
-// keeps only the 19 symbol counts, two code-length-code tables and its tree scratch in LDS.
+// Pairs are never stored: each lane re-generates them from the shared code-length runs and keeps its
+// 19 symbol counts and both code-length-code tables in registers; its trees are built in registers
+// (d4g_cl_tree_regs).  Only a tree deeper than 7 (the limiter) goes through LDS, one lane at a time.
 // ---------------------------------------------------------------------------------------
-// one code-length tree per lane: 16-bit queue entries (weight < 1024, node id < 64), depths in the queue's memory
+// the limiter's code-length tree: 16-bit queue entries (weight < 1024, node id < 64), depths in the queue's memory
 typedef TreeMem<uint16_t, uint8_t, 20, 6, true> D4GHdrTree;
 struct D4GHdrLds {
     alignas(16) uint8_t lens[D4G_NLIT + D4G_NDIST];
@@ -1529,56 +1530,107 @@ struct D4GHdrLds {
     uint16_t runL[D4G_MAXPAIRS];
     int nRuns;              // runs whose packing depends on the flags (the others are summed in baseFreq)
     uint32_t baseFreq[20];  // code-length symbols contributed by the runs every candidate packs as plain literals
-    alignas(16) unsigned char tree[D4GHdrTree::bytes(64)];
-    uint16_t freq[19 * 64];
-    uint8_t cl0[19 * 64];
-    uint8_t cl1[19 * 64];
+    alignas(16) unsigned char tree[D4GHdrTree::bytes(1)];   // the one tree deeper than 7 being rebuilt
+    uint16_t fbFreq[19];
+    uint8_t fbLen[19];
 };
 
-__device__ __forceinline__ long long d4g_hdr_candidate_body(D4GHdrLds* H, int lane, int flags, int prune, long long litlenBits, long long* prof = nullptr) {
+// a wave-uniform value in a scalar register (in the emulator, where this would be a wave collective, the value itself)
+#ifdef D4G_HOSTSIM
+D4G_DEV int d4g_scalar(int v) { return v; }
+#else
+D4G_DEV int d4g_scalar(int v) { return __builtin_amdgcn_readfirstlane(v); }
+#endif
+
+// count += cnt for the wave-uniform symbol v < 16 of counts packed two per register
+D4G_DEV void d4g_cl_count(uint32_t (&f2)[8], int v, uint32_t cnt) {
+    const uint32_t add = cnt << (16 * (v & 1));
+#pragma unroll
+    for (int j = 0; j < 8; j++) f2[j] += j == (v >> 1) ? add : 0u;
+}
+
+// The code lengths of f: d4g_cl_tree_regs, and the lanes whose tree is deeper than 7 rebuild theirs with the
+// limiter (d4g_build_tree) in H's small tree area, one after another.  Returns true when this lane did.
+template <typename FreqFn>
+D4G_DEV bool d4g_cl_lengths(D4GHdrLds* H, int lane, FreqFn freq, D4GClLens& len) {
+    const bool deep = d4g_cl_tree_regs(freq, len);
+    auto rebuild = [&]() {
+#pragma unroll
+        for (int s = 0; s < 19; s++) { H->fbFreq[s] = (uint16_t)freq(s); H->fbLen[s] = 0; }
+        D4GHdrTree tm;
+        tm.carve(H->tree, 1);
+        d4g_build_tree(tm, 1, 0, 19, 7, [&](int i) { return (unsigned)H->fbFreq[i]; }, [&](int v, int ln) { H->fbLen[v] = (uint8_t)ln; });
+        len.lo = 0;
+        len.hi = 0;
+#pragma unroll
+        for (int s = 0; s < 16; s++) len.lo |= (uint64_t)H->fbLen[s] << (4 * s);
+#pragma unroll
+        for (int s = 16; s < 19; s++) len.hi |= (uint32_t)H->fbLen[s] << (4 * (s - 16));
+    };
+#ifdef D4G_HOSTSIM
+    if (deep) rebuild();   // the emulator's lanes run one at a time between wave collectives
+#else
+    unsigned long long need = d4g_ballot(deep);
+    while (need) {
+        const int l = __ffsll((long long)need) - 1;
+        need &= need - 1;
+        if (lane == l) rebuild();
+    }
+#endif
+    return deep;
+}
+
+// *fellBack (optional): set when one of this lane's trees needed the limiter
+__device__ __forceinline__ long long d4g_hdr_candidate_body(D4GHdrLds* H, int lane, int flags, int prune, long long litlenBits, long long* prof = nullptr,
+                                                            bool* fellBack = nullptr) {
 #ifdef D4G_PROFILE_OPS
     long long q0 = d4g_clock_drained();
 #endif
-    D4GHdrTree tm;
-    tm.carve(H->tree, 64);
-#define FQ(s) H->freq[(s) * 64 + lane]
-#define C0(s) H->cl0[(s) * 64 + lane]
-#define C1(s) H->cl1[(s) * 64 + lane]
-    int nRuns = H->nRuns;
-    for (int s = 0; s < 19; s++) { FQ(s) = (uint16_t)H->baseFreq[s]; C0(s) = 0; C1(s) = 0; }
+    const int nRuns = H->nRuns;
+    uint32_t base2[8];   // baseFreq of symbols 0..15, two 16-bit counts per register
+#pragma unroll
+    for (int j = 0; j < 8; j++) base2[j] = H->baseFreq[2 * j] | (H->baseFreq[2 * j + 1] << 16);
+    const uint32_t base16 = H->baseFreq[16], base17 = H->baseFreq[17], base18 = H->baseFreq[18];
+    // the counts of the candidate's packing in hand: symbols 0..15 two per register, 16..18 one each
+    uint32_t f2[8], c16, c17, c18;
+    auto fq = [&](int s) -> uint32_t { return s < 16 ? (f2[s >> 1] >> (16 * (s & 1))) & 0xffffu : s == 16 ? c16 : s == 17 ? c17 : c18; };
     // rewriteHeader(flags): symbol counts of the packed lengths
-    // The repeat symbols are counted in registers; each run touches LDS once, for its own (wave-uniform) value.
     {
-        int c16 = 0, c17 = 0, c18 = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) f2[j] = base2[j];
+        c16 = base16; c17 = base17; c18 = base18;
         for (int r = 0; r < nRuns; r++) {
-            const int v = H->runV[r];
+            const int v = d4g_scalar(H->runV[r]);
             d4g_pack_kinds(v, H->runL[r], flags,
                            [&](int sym, int, int, int cnt) { if (sym == 16) c16 += cnt; else if (sym == 17) c17 += cnt; else c18 += cnt; },
-                           [&](int cnt) { FQ(v) += (uint16_t)cnt; });
+                           [&](int cnt) { d4g_cl_count(f2, v, (uint32_t)cnt); });
         }
-        FQ(16) += (uint16_t)c16; FQ(17) += (uint16_t)c17; FQ(18) += (uint16_t)c18;
     }
 #ifdef D4G_PROFILE_OPS
     long long q1 = d4g_clock_drained();
 #endif
-    d4g_build_tree(tm, 64, lane, 19, 7, [&](int i) { return (unsigned)FQ(i); }, [&](int v, int len) { C0(v) = (uint8_t)len; });
+    D4GClLens c0, c1 = {0, 0};
+    bool fb = d4g_cl_lengths(H, lane, fq, c0);
 #ifdef D4G_PROFILE_OPS
     long long q2 = d4g_clock_drained();
 #endif
     long long hdr = 5 + 5 + 4 + 19 * 3;
-    for (int s = 0; s < 19; s++) hdr += (long long)FQ(s) * (C0(s) + (s >= 16 ? pair_extra_bits(s) : 0));
-    int nCl = trim_codelens(19, [&](int s) { return (int)C0(s); });
+#pragma unroll
+    for (int s = 0; s < 19; s++) hdr += (long long)fq(s) * (c0.get(s) + (s >= 16 ? pair_extra_bits(s) : 0));
+    int nCl = trim_codelens(19, [&](int s) { return c0.get(s); });
     hdr -= 3 * (19 - nCl);
     bool useC1 = false;
     if (prune) {
         // recodeHeaderToLessRLEMatches: expand runs that are not shorter than literals, then re-derive the code
-        for (int s = 0; s < 19; s++) FQ(s) = (uint16_t)H->baseFreq[s];
         {
-            const int l16 = C0(16), l17 = C0(17), l18 = C0(18), l0 = C0(0);
-            int c16 = 0, c17 = 0, c18 = 0, z = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) f2[j] = base2[j];
+            const int l16 = c0.get(16), l17 = c0.get(17), l18 = c0.get(18), l0 = c0.get(0);
+            uint32_t z = 0;
+            c16 = base16; c17 = base17; c18 = base18;
             for (int r = 0; r < nRuns; r++) {
-                const int v = H->runV[r];
-                const int lv = C0(v);
+                const int v = d4g_scalar(H->runV[r]);
+                const int lv = c0.get(v);
                 int addV = 0;
                 d4g_pack_kinds(v, H->runL[r], flags,
                                [&](int sym, int run, int, int cnt) {
@@ -1592,29 +1644,30 @@ __device__ __forceinline__ long long d4g_hdr_candidate_body(D4GHdrLds* H, int la
                                    else c18 += cnt;
                                },
                                [&](int cnt) { addV += cnt; });
-                if (addV) FQ(v) += (uint16_t)addV;
+                d4g_cl_count(f2, v, (uint32_t)addV);
             }
-            FQ(16) += (uint16_t)c16; FQ(17) += (uint16_t)c17; FQ(18) += (uint16_t)c18; FQ(0) += (uint16_t)z;
+            f2[0] += z;   // symbol 0 is the low half of register 0
         }
-        d4g_build_tree(tm, 64, lane, 19, 7, [&](int i) { return (unsigned)FQ(i); }, [&](int v, int len) { C1(v) = (uint8_t)len; });
-        nCl = trim_codelens(nCl, [&](int s) { return (int)C1(s); });
+        fb |= d4g_cl_lengths(H, lane, fq, c1);
+        nCl = trim_codelens(nCl, [&](int s) { return c1.get(s); });
         hdr = 5 + 5 + 4 + 3 * nCl;
-        for (int s = 0; s < 19; s++) hdr += (long long)FQ(s) * (C1(s) + (s >= 16 ? pair_extra_bits(s) : 0));
+#pragma unroll
+        for (int s = 0; s < 19; s++) hdr += (long long)fq(s) * (c1.get(s) + (s >= 16 ? pair_extra_bits(s) : 0));
         useC1 = true;
     }
     // optimiseHeader: trim again, then expand runs that are strictly longer than literals
     {
-        int n2 = useC1 ? trim_codelens(nCl, [&](int s) { return (int)C1(s); }) : trim_codelens(nCl, [&](int s) { return (int)C0(s); });
+        int n2 = useC1 ? trim_codelens(nCl, [&](int s) { return c1.get(s); }) : trim_codelens(nCl, [&](int s) { return c0.get(s); });
         hdr -= 3 * (nCl - n2);
         nCl = n2;
     }
     long long saved = 0;
     {
-        const int a16 = C0(16), a17 = C0(17), a18 = C0(18), a0 = C0(0);
-        const int b16 = C1(16), b17 = C1(17), b18 = C1(18), b0 = C1(0);
+        const int a16 = c0.get(16), a17 = c0.get(17), a18 = c0.get(18), a0 = c0.get(0);
+        const int b16 = c1.get(16), b17 = c1.get(17), b18 = c1.get(18), b0 = c1.get(0);
         for (int r = 0; r < nRuns; r++) {
-            const int v = H->runV[r];
-            const int av = C0(v), bv = C1(v);
+            const int v = d4g_scalar(H->runV[r]);
+            const int av = c0.get(v), bv = c1.get(v);
             d4g_pack_kinds(v, H->runL[r], flags,
                            [&](int sym, int run, int, int cnt) {
                                int as = sym == 16 ? a16 : sym == 17 ? a17 : a18, al = sym == 16 ? av : a0;
@@ -1640,9 +1693,7 @@ __device__ __forceinline__ long long d4g_hdr_candidate_body(D4GHdrLds* H, int la
         atomicAdd((unsigned long long*)&prof[51], 1ULL);
     }
 #endif
-#undef FQ
-#undef C0
-#undef C1
+    if (fellBack) *fellBack = fb;
     return litlenBits + hdr;
 }
 // (a call in the header-search kernels; the fused executor inlines the body under its own register budget)

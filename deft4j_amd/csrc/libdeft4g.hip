@@ -653,6 +653,44 @@ int d4g_debug_zopfli_code_lengths(const uint32_t* freq, int n, int maxbits, uint
     }
 }
 
+__global__ void __launch_bounds__(64) k_debug_cl_tree(const uint32_t* freq, int n, uint32_t* out, int32_t* limited) {
+    __shared__ D4GHdrLds H;
+    const int lane = threadIdx.x & 63;
+    const long long h = (long long)blockIdx.x * 64 + lane;
+    const bool live = h < n;
+    uint32_t f[19];
+#pragma unroll
+    for (int s = 0; s < 19; s++) f[s] = live ? freq[h * 19 + s] : 0u;
+    D4GClLens len;
+    const bool deep = d4g_cl_lengths(&H, lane, [&](int s) { return f[s]; }, len);
+    if (live) {
+#pragma unroll
+        for (int s = 0; s < 19; s++) out[h * 19 + s] = (uint32_t)len.get(s);
+        limited[h] = deep ? 1 : 0;
+    }
+}
+
+int d4g_debug_cl_tree_lengths(const uint32_t* freq, int n, uint32_t* lengths, int32_t* limited) {
+    enter_ctx(nullptr);
+    if (!freq || !lengths || !limited || n < 1) return fail(D4G_ERR_ARG, "bad argument");
+    D4G_API_LOCK();
+    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
+    try {
+        bind_device();
+        LzScratch own;
+        uint32_t* dF = own.own((uint32_t*)rt_malloc((size_t)n * 19 * 4));
+        uint32_t* dO = own.own((uint32_t*)rt_malloc((size_t)n * 19 * 4));
+        int32_t* dL = own.own((int32_t*)rt_malloc((size_t)n * 4));
+        rt_h2d(dF, freq, (size_t)n * 19 * 4);
+        RT_LAUNCH(k_debug_cl_tree, (n + 63) / 64, 64, dF, n, dO, dL);
+        rt_d2h(lengths, dO, (size_t)n * 19 * 4);
+        rt_d2h(limited, dL, (size_t)n * 4);
+        return D4G_OK;
+    } catch (const std::exception& ex) {
+        return fail(D4G_ERR_RUNTIME, ex.what());
+    }
+}
+
 void d4g_free(void* p) { free(p); }
 
 }  // extern "C"

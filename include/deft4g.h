@@ -163,6 +163,9 @@ int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_le
  * code lengths of one frequency vector (n <= 288, maxbits <= 15). */
 int d4g_debug_zopfli_table(const uint8_t* raw, size_t n, size_t end, uint16_t* len16, uint16_t* dist16, uint16_t* sublen);
 int d4g_debug_zopfli_code_lengths(const uint32_t* freq, int n, int maxbits, uint32_t* lengths);
+/* Test hook (tests/ only): the header search's 19-symbol code-length trees (limit 7) of n histograms freq[h * 19 + s]:
+ * lengths[h * 19 + s], and limited[h] = 1 where the tree was deeper than 7 and went through the depth limiter. */
+int d4g_debug_cl_tree_lengths(const uint32_t* freq, int n, uint32_t* lengths, int32_t* limited);
 
 #define D4G_MODE_NONE 0
 #define D4G_MODE_CHEAP 1
