@@ -44,15 +44,20 @@ class d4g_encoder_spec(ctypes.Structure):
     _fields_ = [("input", ctypes.c_int32), ("encoder", ctypes.c_int32), ("strategy", ctypes.c_int32)]
 
 
+class d4g_encoder_spec_level(ctypes.Structure):
+    _fields_ = [("input", ctypes.c_int32), ("encoder", ctypes.c_int32), ("strategy", ctypes.c_int32), ("level", ctypes.c_int32)]
+
+
 ENC_JVM, ENC_JZLIB = 0, 1                                   # D4G_ENC_*: JavaCompressor / JZLibCompressor
 STRATEGY_DEFAULT, STRATEGY_FILTERED, STRATEGY_HUFFMAN_ONLY = 0, 1, 2
+STRATEGY_RLE, STRATEGY_FIXED = 3, 4                         # zlib's Z_RLE / Z_FIXED (the level entry points only)
 
 EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4g_batch_run", "d4g_batch_stream_result",
            "d4g_batch_copy_output", "d4g_batch_copy_decoded", "d4g_batch_checksums", "d4g_batch_parse", "d4g_batch_stats", "d4g_batch_destroy", "d4g_optimise_streams",
            "d4g_size_bits_fallback", "d4g_inflate", "d4g_free", "d4g_batch_create_encode", "d4g_batch_run_encode", "d4g_deflate_streams",
            "d4g_compress", "d4g_recompress_streams", "d4g_batch_run_recompress", "d4g_batch_recompress_result", "d4g_zopfli_streams",
            "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
-           "d4g_batch_create_on", "d4g_optimise_streams_sharded"]
+           "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level"]
 
 
 def load_library(path=None):
@@ -111,6 +116,12 @@ def load_library(path=None):
     L.d4g_deflate_streams.restype = ctypes.c_int
     L.d4g_deflate_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+    L.d4g_batch_create_encode_level.restype = ctypes.c_void_p
+    L.d4g_batch_create_encode_level.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t,
+                                                ctypes.POINTER(d4g_encoder_spec_level)]
+    L.d4g_deflate_streams_level.restype = ctypes.c_int
+    L.d4g_deflate_streams_level.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
     L.d4g_zopfli_streams.restype = ctypes.c_int
     L.d4g_zopfli_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
@@ -309,7 +320,9 @@ class Batch:
 class EncodeBatch(Batch):
     """Streams produced by the LZ77 encoder kernels (d4g_batch_create_encode): one output per (input, encoder, strategy)
     spec — the Compressor objects of C/CompressionUtil.java:44-78.  run(optimise=False) leaves the encoder's output as it
-    is (SingleCompressor.compressSingle); optimise=True also applies Deft.optimiseDeflateStream to every output."""
+    is (SingleCompressor.compressSingle); optimise=True also applies Deft.optimiseDeflateStream to every output.
+    A spec may also be (input, encoder, strategy, level) — zlib levels -1, 1..9 (d4g_batch_create_encode_level); a
+    3-tuple next to those means level 9."""
 
     def __init__(self, inputs, specs, lib=None):  # noqa: super().__init__ deliberately not called: a different constructor
         self.L = lib or _need()
@@ -318,10 +331,16 @@ class EncodeBatch(Batch):
         nin = len(self._keep)
         arr = (ctypes.c_char_p * max(1, nin))(*self._keep)
         lens = (ctypes.c_size_t * max(1, nin))(*[len(s) for s in self._keep])
-        sp = (d4g_encoder_spec * max(1, self.n))(*[d4g_encoder_spec(*t) for t in specs])
-        self.h = self.L.d4g_batch_create_encode(nin, arr, lens, self.n, sp)
+        if any(len(t) == 4 for t in specs):
+            sp = (d4g_encoder_spec_level * max(1, self.n))(*[d4g_encoder_spec_level(*(tuple(t) + (9,) * (4 - len(t)))) for t in specs])
+            self.h = self.L.d4g_batch_create_encode_level(nin, arr, lens, self.n, sp)
+            what = "d4g_batch_create_encode_level: "
+        else:
+            sp = (d4g_encoder_spec * max(1, self.n))(*[d4g_encoder_spec(*t) for t in specs])
+            self.h = self.L.d4g_batch_create_encode(nin, arr, lens, self.n, sp)
+            what = "d4g_batch_create_encode: "
         if not self.h:
-            raise RuntimeError("d4g_batch_create_encode: " + self.L.d4g_last_error().decode())
+            raise RuntimeError(what + self.L.d4g_last_error().decode())
 
     def run(self, optimise=False, merge_blocks=True):
         rc = self.L.d4g_batch_run_encode(self.h, 1 if optimise else 0, 1 if merge_blocks else 0)
@@ -330,8 +349,9 @@ class EncodeBatch(Batch):
         return self
 
 
-def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None):
-    """SingleCompressor.compressSingle for every input (d4g_deflate_streams)."""
+def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None, level=9):
+    """SingleCompressor.compressSingle for every input (d4g_deflate_streams); at another zlib level (-1, 1..9) or with
+    STRATEGY_RLE / STRATEGY_FIXED through d4g_deflate_streams_level."""
     L = lib or _need()
     n = len(inputs)
     keep = [bytes(s) for s in inputs]
@@ -339,9 +359,12 @@ def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None
     lens = (ctypes.c_size_t * max(1, n))(*[len(s) for s in keep])
     out = (ctypes.c_void_p * max(1, n))()
     olen = (ctypes.c_size_t * max(1, n))()
-    rc = L.d4g_deflate_streams(n, arr, lens, encoder, strategy, out, olen)
+    if level == 9 and strategy in (STRATEGY_DEFAULT, STRATEGY_FILTERED, STRATEGY_HUFFMAN_ONLY):
+        rc, what = L.d4g_deflate_streams(n, arr, lens, encoder, strategy, out, olen), "d4g_deflate_streams: "
+    else:
+        rc, what = L.d4g_deflate_streams_level(n, arr, lens, encoder, level, strategy, out, olen), "d4g_deflate_streams_level: "
     if rc != 0:
-        raise RuntimeError("d4g_deflate_streams: " + L.d4g_last_error().decode())
+        raise RuntimeError(what + L.d4g_last_error().decode())
     res = []
     for i in range(n):
         res.append(ctypes.string_at(out[i], olen[i]))

@@ -1,4 +1,5 @@
-// d4g_lz77.h — LZ77 match search + lazy parse + block emit, bit-compatible with zlib level 9.
+// d4g_lz77.h — LZ77 match search + lazy parse + block emit, bit-compatible with zlib level 9 and,
+// through the level entry points, with zlib levels 1-8 and the Z_RLE / Z_FIXED strategies.
 //
 // The reference owns no match finder: its recompress modes call java.util.zip.Deflater(BEST_COMPRESSION, nowrap) and
 // jzlib at level 9 with strategies DEFAULT / FILTERED / HUFFMAN_ONLY (C/JavaCompressor.java:36-49,
@@ -42,6 +43,13 @@
 #define LZ_DEFAULT 0
 #define LZ_FILTERED 1
 #define LZ_HUFFMAN_ONLY 2
+#define LZ_RLE 3               // deflate_rle: distance-1 runs, no hash chains
+#define LZ_FIXED 4             // the level's parse; _tr_flush_block never sends dynamic trees
+#define LZ_KIND_SLOW 0         // deflate_slow (levels 4-9): lazy evaluation, every position inserted
+#define LZ_KIND_FAST 1         // deflate_fast (levels 1-3): greedy, long matches' interiors not inserted
+#define LZ_KIND_RLE 2          // deflate_rle
+#define LZ_CHUNK_WORDS (LZ_CHUNK / 32)   // insertion-map words a chunk owns
+#define LZ_BITS_REACH 16       // chunks whose insertion bits a chunk's searches can read (32 KiB / LZ_CHUNK)
 #define LZ_FLAVOR_ZLIB 0
 #define LZ_FLAVOR_JZLIB 1
 
@@ -59,7 +67,10 @@ struct LzStream {           // one uncompressed input
     int32_t nChunks;
 };
 struct LzSortJob { int32_t stream, blk; };
-struct LzParseJob { int32_t stream, firstChunk, metaBase, strategy; };   // meta index of chunk c = metaBase + c
+// meta index of chunk c = metaBase + c.  good / lazy / nice / chain: zlib's configuration_table row of the level
+// (lazy = max_lazy for deflate_slow, max_insert_length for deflate_fast).  insBase: the parse's first insertion-map word
+// (deflate_fast only).
+struct LzParseJob { int32_t stream, firstChunk, metaBase, strategy, good, lazy, nice, chain; long long insBase; };
 struct LzChunkMeta {
     unsigned long long entry, exit;   // packed parse states (lz_pack_state)
     uint32_t ntok, nmatch;
@@ -67,6 +78,8 @@ struct LzChunkMeta {
     uint32_t pad;                     // the chunk's last token
     uint32_t dcost;                   // sum over the chunk's matches of 5 + extra bits of the distance code (jzlib's early-flush bound)
     uint32_t pad2;
+    int32_t ranPass;                  // deflate_fast: the pass of the chunk's last run (0 = speculative)
+    int32_t chainStart;               // deflate_fast: first chunk of the wave's run in that pass
 };
 
 // parse state at a loop top of deflate_slow: position, match_available, match_length carried from the previous
@@ -187,7 +200,23 @@ struct LzCtx {
     LzChunkMeta* meta;
     uint32_t* chunkTok;       // LZ_CHUNK + 2 token words per chunk
     int32_t* errors;
+    uint32_t* insLive;        // deflate_fast insertion maps: every chunk's latest bits (LZ_CHUNK_WORDS words per chunk)
+    const uint32_t* insFrozen;   // ... as they were when the pass began (what exact re-runs read)
+    int32_t* insChg;          // per chunk: the last pass in which its bits changed (-1: never)
 };
+
+// deflate_fast's insertion map as a chain walk sees it: bit x - base of w = position x was inserted.  Below own0 (the
+// running chunk's first position) a speculative run assumes every position inserted; an exact run reads the window.
+struct LzBits {
+    const uint32_t* w;
+    long long base, own0;
+    int exact;
+};
+D4G_DEV bool lz_inserted(const LzBits& b, long long x) {
+    if (x < b.base || (x < b.own0 && !b.exact)) return true;   // (below base: out of the window's reach anyway)
+    const long long o = x - b.base;
+    return (b.w[o >> 5] >> (o & 31)) & 1u;
+}
 
 D4G_DEV uint32_t lz_load4(const uint32_t* win, int off) {   // bytes [off, off+4) of the staged window (little endian)
     uint32_t lo = win[off >> 2], hi = win[(off >> 2) + 1];
@@ -201,8 +230,12 @@ D4G_DEV unsigned long long lz_load8(const uint32_t* win, int off) {   // bytes [
     return sh ? (lo >> sh) | ((unsigned long long)win[i + 2] << (64 - sh)) : lo;
 }
 
+// FAST: only inserted positions are chain entries (deflate_fast), and the walk takes the first maxChain of them.
+// nice: zlib stops at the FIRST candidate whose length reaches nice_match (clamped to what is left of the input), even
+// when a later one is longer — within a 64-candidate step that is the first such lane, not the step's maximum.
+template <bool FAST>
 D4G_DEV void lz_search(const LzCtx& c, const LzStream& st, const uint32_t* win, long long w0, long long p, int bestInit, int maxChain,
-                       int& bestLen, int& bestDist) {
+                       int nice, const LzBits& bits, int& bestLen, int& bestDist) {
     const int lane = threadIdx.x & 63;
     const int blk = (int)(p >> 15);
     const int r = c.rank16[st.posBase + p];
@@ -220,22 +253,33 @@ D4G_DEV void lz_search(const LzCtx& c, const LzStream& st, const uint32_t* win, 
         endB = B2 + cntB;
     }
     int total = cntA + cntB;
-    if (total > maxChain) total = maxChain;
+    if (!FAST && total > maxChain) total = maxChain;
     const long long rem = st.len - p;
     const int maxcmp = rem < 258 ? (int)rem : 258;
+    const int niceEff = nice < maxcmp ? nice : maxcmp;
     const uint16_t* SA = c.S16 + st.posBase + (long long)blk * LZ_SORT_BLOCK;
-    int best = bestInit, bd = 0;
+    const unsigned long long below = lane ? (~0ULL >> (64 - lane)) : 0ULL;
+    int best = bestInit, bd = 0, seen = 0;
     for (int i0 = 0; i0 < total; i0 += 64) {
         const int i = i0 + lane;
-        bool ok = i < total;
+        const bool valid = i < total;
         long long cpos = 0;
-        if (ok) {
+        if (valid) {
             if (i < cntA) cpos = (long long)blk * LZ_SORT_BLOCK + SA[r - 1 - i];
             else cpos = (long long)(blk - 1) * LZ_SORT_BLOCK + (SA - LZ_SORT_BLOCK)[endB - 1 - (i - cntA)];
         }
         const int dist = (int)(p - cpos);
+        bool ins = valid;
+        int rank = i, nIns = 0;
+        if (FAST) {
+            if (valid) ins = lz_inserted(bits, cpos);
+            const unsigned long long m = __ballot(ins);
+            rank = seen + __popcll(m & below);
+            nIns = __popcll(m);
+        }
         // zlib: the chain head may be MAX_DIST away, later candidates must be nearer; stream position 0 is NIL
-        ok = ok && dist <= (i == 0 ? LZ_MAX_DIST : LZ_MAX_DIST - 1) && cpos >= 1;
+        const bool inRange = cpos >= 1 && dist <= (rank == 0 ? LZ_MAX_DIST : LZ_MAX_DIST - 1);
+        const bool ok = ins && inRange && rank < maxChain;
         int len = 0;
         if (ok) {
             const int co = po - dist;
@@ -252,33 +296,54 @@ D4G_DEV void lz_search(const LzCtx& c, const LzStream& st, const uint32_t* win, 
                 len = k < maxcmp ? k : maxcmp;
             }
         }
+        const unsigned long long hit = __ballot(ok && len > best && len >= niceEff);
+        if (hit) {   // nice_length (or what is left of the input) reached: the first such candidate ends the walk
+            const int f = __ffsll((long long)hit) - 1;
+            best = __shfl(len, f);
+            bd = __shfl(dist, f);
+            break;
+        }
         int key = (ok && len > best) ? ((len << 8) | (63 - lane)) : 0;
         key = wave_max_i32(key);
         if (key) {
             best = key >> 8;
             bd = __shfl(dist, 63 - (key & 63));
         }
-        if (best >= maxcmp) break;            // nice_length (258, or what is left of the input) reached
-        if (__ballot(!ok && i < total)) break;   // the chain left the window
+        if (FAST) {
+            seen += nIns;
+            if (seen >= maxChain) break;
+            // the chain left the window (entries are nearest first: no later one is nearer)
+            if (__ballot(valid && (ins ? !inRange : (cpos < 1 || dist >= LZ_MAX_DIST)))) break;
+        } else if (__ballot(!ok && valid)) break;   // the chain left the window
     }
     bestLen = best;
     bestDist = bd;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// k_lz_parse: deflate_slow over chunks.  blockDim.x / 64 consecutive chunks of one stream share the staged window.
+// k_lz_parse: deflate_slow / deflate_fast / deflate_rle over chunks.  blockDim.x / 64 consecutive chunks of one stream
+// share the staged window.
 // exact = 0: every chunk but a stream's first starts LZ_WARM positions early from a clean state and records from its
 //            first loop top inside the chunk;  exact = 1 (one wave per job): the chunk starts from its predecessor's
 //            recorded exit state and the wave carries on into the following chunks while they disagree.
+// deflate_fast (KIND == LZ_KIND_FAST) also keeps an insertion map, one bit per position: a chunk writes
+// the bits of its own LZ_CHUNK positions; its searches read them below its position, and below its first position read
+// "inserted" (speculative pass) or the map of the pass's start (insFrozen; exact passes), except for chunks this wave
+// re-ran earlier in the same pass, whose fresh bits it keeps in LDS.  The state packs the position and whether the
+// positions between the chunk's start and it — the inside of the previous chunk's last match — were inserted.
 // ---------------------------------------------------------------------------------------------------------------------
 #define LZ_PARSE_MAXWAVES 16   // 16 chunks share one staged window: 66 KB of LDS, two workgroups = 32 waves per CU
+#define LZ_WIN_BYTES (32768 + LZ_WARM + LZ_PARSE_MAXWAVES * LZ_CHUNK + LZ_WIN_SLACK + 64)
+#define LZ_BITS_WORDS (LZ_WIN_BYTES / 32 + 2)
 // `heads` (exact mode): per chunk, 1 = another workgroup re-runs this chunk in the same pass.  A re-run chunk whose new exit
 // state differs from what its successor started from goes straight on into the successor (re-staging the window), and on,
 // until a chunk's recorded entry equals the exit just produced — or the successor is somebody else's job.  Inputs whose
 // speculative parses never fall into step (one long run: every chunk starts a 258-byte match at a different phase) are
 // thus parsed by one wave in one pass instead of one pass per chunk.
-__global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, const LzParseJob* jobs, int exact, const uint8_t* heads) {
-    __shared__ uint32_t win[(32768 + LZ_WARM + LZ_PARSE_MAXWAVES * LZ_CHUNK + LZ_WIN_SLACK + 64) / 4];
+template <int KIND>
+__global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, const LzParseJob* jobs, int exact, const uint8_t* heads, int pass) {
+    __shared__ uint32_t win[LZ_WIN_BYTES / 4];
+    __shared__ uint32_t insw[KIND == LZ_KIND_FAST ? LZ_BITS_WORDS : 1];
     const LzParseJob job = jobs[blockIdx.x];
     const LzStream st = c.streams[job.stream];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -286,6 +351,8 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
     int tileChunk = job.firstChunk;                 // first chunk of the staged tile
     unsigned long long carry = 0;                   // exact mode, from the second chunk of a chain on: the state to start from
     bool chained = false;
+    long long prevW0 = -1;                          // deflate_fast, exact mode: the previous tile's window start
+    int lastChanged = -LZ_BITS_REACH - 1;           // deflate_fast, exact mode: the wave's last chunk whose bits changed
     for (;;) {
     const long long tile0 = (long long)tileChunk * LZ_CHUNK;
     long long w0 = tile0 - 32768 - LZ_WARM;
@@ -301,6 +368,24 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
         const uint4* src = (const uint4*)(st.data + w0);
         uint4* dst = (uint4*)win;
         for (int i = threadIdx.x; i < nvec; i += blockDim.x) dst[i] = src[i];
+    }
+    if (KIND == LZ_KIND_FAST && exact) {   // (w0 is a multiple of 32 here: tile0 - 33280 or 0)
+        // the bits below the chain's head: the map of the pass's start; the chain's own chunks: the previous tile's LDS
+        // copy, moved down (one wave: each 64-word step reads before it writes, and the shift is >= 1024 words)
+        const long long mapEnd = (long long)st.nChunks * LZ_CHUNK;
+        const long long headPos = (long long)job.firstChunk * LZ_CHUNK;
+        const int sh = prevW0 >= 0 ? (int)((w0 - prevW0) >> 5) : 0;
+        for (int i0 = 0; i0 < LZ_BITS_WORDS; i0 += 64) {
+            const int i = i0 + lane;
+            const long long x = w0 + (long long)i * 32;
+            uint32_t v = 0xffffffffu;
+            if (x < headPos && x < mapEnd) v = c.insFrozen[job.insBase + (x >> 5)];
+            else if (prevW0 >= 0 && i + sh < LZ_BITS_WORDS) v = insw[i + sh];
+            LZ_WAVE_SYNC();
+            if (i < LZ_BITS_WORDS) insw[i] = v;
+            LZ_WAVE_SYNC();
+        }
+        prevW0 = w0;
     }
     __syncthreads();
     int chunk = tileChunk + wave;
@@ -343,13 +428,40 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
         ntok++;
         if ((ntok & 63u) == 0) tokOut[ntok - 64 + lane] = tokbuf;
     };
+    // deflate_fast: this chunk's own insertion bits start as "inserted"; the inside of a long match is cleared
+    uint32_t* own = insw;
+    const long long bw0 = w0;
+    LzBits bits;
+    bits.w = insw; bits.base = bw0; bits.own0 = c0; bits.exact = exact;
+    auto clearBits = [&](long long a, long long b) D4G_LAMBDA_INLINE {   // positions [a, b) not inserted (clipped to the chunk)
+        if (a < c0) a = c0;
+        if (b > c0 + LZ_CHUNK) b = c0 + LZ_CHUNK;
+        if (a >= b) return;
+        const long long wa = (a - bw0) >> 5, wz = (b - 1 - bw0) >> 5;
+        const long long wi = wa + lane;
+        if (wi <= wz) {
+            const long long lo = bw0 + wi * 32;
+            uint32_t m = 0xffffffffu;
+            if (a > lo) m &= ~0u << (a - lo);
+            if (b < lo + 32) m &= ~0u >> (lo + 32 - b);
+            own[wi] &= ~m;
+        }
+        LZ_WAVE_SYNC();
+    };
+    bool lastInterior = false;   // deflate_fast: the last match's inside was inserted
+    if (KIND == LZ_KIND_FAST) {
+        own[((c0 - bw0) >> 5) + lane] = 0xffffffffu;   // LZ_CHUNK_WORDS == 64: one word per lane
+        LZ_WAVE_SYNC();
+        if (rec && p > c0 && !ma) clearBits(c0, p);
+    }
+    if (KIND == LZ_KIND_SLOW) {
     while (p < c1) {
         if (!rec && p >= c0) { rec = true; entry = lz_pack_state(p, ma, ml, md); }
         const int prevLen = ml, prevDist = md;
         ml = 2;
-        if (st.len - p >= 3 && prevLen < 258 && job.strategy != LZ_HUFFMAN_ONLY) {
+        if (st.len - p >= 3 && prevLen < job.lazy && job.strategy != LZ_HUFFMAN_ONLY) {
             int bl, bd;
-            lz_search(c, st, win, w0, p, prevLen, prevLen >= 32 ? 1024 : 4096, bl, bd);
+            lz_search<false>(c, st, win, w0, p, prevLen, prevLen >= job.good ? job.chain >> 2 : job.chain, job.nice, bits, bl, bd);
             if (bl > prevLen) {
                 ml = bl;
                 md = bd;
@@ -376,8 +488,57 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
         ma = 0; ml = 2; md = 0;
         p = st.len;
     }
+    } else {   // deflate_fast / deflate_rle: greedy, one token per loop top, no pending state
+    while (p < c1) {
+        if (!rec && p >= c0) { rec = true; entry = lz_pack_state(p, p > c0 && lastInterior, 2, 0); }
+        const long long rem = st.len - p;
+        int bl = 2, bd = 0;
+        if (KIND == LZ_KIND_FAST) {
+            if (rem >= 3) lz_search<true>(c, st, win, w0, p, 2, job.chain, job.nice, bits, bl, bd);
+        } else if (rem >= 3 && p > 0) {   // deflate_rle: how far the byte before p repeats (eight bytes per lane)
+            const int po = (int)(p - w0);
+            const unsigned long long pat = 0x0101010101010101ULL * wb[po - 1];
+            const unsigned long long x = lane < 33 ? lz_load8(win, po + 8 * lane) ^ pat : 0ULL;
+            const unsigned long long m = __ballot(lane < 33 && x != 0ULL);
+            int run = 264;
+            if (m) {
+                const int f = __ffsll((long long)m) - 1;
+                const unsigned long long xf = __shfl(x, f);
+                run = 8 * f + ((__ffsll((long long)xf) - 1) >> 3);
+            }
+            if (run > 258) run = 258;
+            if (run > rem) run = (int)rem;
+            if (run >= 3) { bl = run; bd = 1; }
+        }
+        if (bl >= 3) {
+            emit((unsigned)bl | ((unsigned)bd << 9), p);
+            if (rec) { nmatch++; dcost += 5u + (unsigned)d4g_dsym_ebits(d4g_dist2sym(bd)); }
+            if (KIND == LZ_KIND_FAST) {
+                // deflate_fast inserts the inside of a match of at most max_insert_length that leaves >= 3 bytes
+                lastInterior = bl <= job.lazy && rem - bl >= 3;
+                if (!lastInterior) clearBits(p + 1, p + bl);
+            }
+            p += bl;
+        } else {
+            emit((unsigned)wb[p - w0], p);
+            p++;
+        }
+    }
+    if (!rec) { rec = true; entry = lz_pack_state(p, p > c0 && lastInterior, 2, 0); }
+    if (p >= st.len) p = st.len;
+    ma = p > c1 && lastInterior;   // (deflate_fast: whether the successor's first positions were inserted)
+    }
     if (ntok & 63u) { if (lane < (int)(ntok & 63u)) tokOut[(ntok & ~63u) + lane] = tokbuf; }
     const unsigned long long exitState = lz_pack_state(p, ma, ml, md);
+    bool bitsChanged = false;
+    if (KIND == LZ_KIND_FAST) {   // publish the chunk's bits; note the pass when they differ from what they were
+        uint32_t* dst = c.insLive + job.insBase + (long long)chunk * LZ_CHUNK_WORDS;
+        const uint32_t v = own[((c0 - bw0) >> 5) + lane];
+        bitsChanged = __ballot(dst[lane] != v) != 0ULL;
+        dst[lane] = v;
+        if (bitsChanged && lane == 0) c.insChg[job.metaBase + chunk] = pass;
+        if (bitsChanged) lastChanged = chunk;
+    }
     if (lane == 0) {
         M->entry = entry;
         M->exit = exitState;
@@ -387,13 +548,16 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
         M->pad = lastTok;   // the chunk's last token (the host needs the stream's last one: match or literal)
         M->dcost = dcost;
         M->pad2 = 0;
+        M->ranPass = pass;
+        M->chainStart = exact ? job.firstChunk : chunk;
     }
     if (!exact) return;
     // exact mode (one wave): does the successor have to follow?
     const int next = chunk + 1;
     if (next >= st.nChunks || heads[job.metaBase + next]) return;
     const unsigned long long nextEntry = (M + 1)->entry;      // (the successor is nobody's job in this pass: its meta is stable)
-    if (nextEntry == exitState) return;
+    // (deflate_fast: bits this wave changed within the successor's reach make it stale too)
+    if (nextEntry == exitState && next - lastChanged > LZ_BITS_REACH) return;
     carry = exitState;
     chained = true;
     chunk = next;
@@ -402,13 +566,21 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
     }
 }
 
-// chunks whose entry state is not their predecessor's exit state (one thread per chunk; list compacted by atomics —
-// order does not matter, every listed chunk is re-run independently)
-__global__ void k_lz_check(const LzChunkMeta* meta, const int32_t* chunkIndex, int nChunksTotal, int32_t* redo, unsigned* nRedo) {
+// chunks that have to be re-run (one thread per chunk; list compacted by atomics — order does not matter, every listed
+// chunk is re-run independently): the entry state is not the predecessor's exit state, or (deflate_fast, bit 31 set
+// when that is the only reason) the insertion bits of a chunk within reach changed after the run read them — a chunk
+// of an earlier chain read the map of its pass's start, one of its own chain the bits of its pass's end
+__global__ void k_lz_check(const LzChunkMeta* meta, const int32_t* chunkIndex, int nChunksTotal, int32_t* redo, unsigned* nRedo,
+                           const uint8_t* chunkFast, const int32_t* insChg) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nChunksTotal) return;
-    if (chunkIndex[i] == 0) return;
-    if (meta[i].entry != meta[i - 1].exit) redo[atomicAdd(nRedo, 1u)] = i;
+    const int k = chunkIndex[i];
+    if (k == 0) return;
+    if (meta[i].entry != meta[i - 1].exit) { redo[atomicAdd(nRedo, 1u)] = i; return; }
+    if (!chunkFast || !chunkFast[i]) return;
+    const int ran = meta[i].ranPass, cs = meta[i].chainStart;
+    for (int d = 1; d <= LZ_BITS_REACH && d <= k; d++)
+        if (insChg[i - d] > ran - 1 + (k - d >= cs ? 1 : 0)) { redo[atomicAdd(nRedo, 1u)] = (int32_t)(i | 0x80000000u); return; }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -510,8 +682,11 @@ struct LzOutStream {           // one emitted deflate stream = (input, strategy,
     long long refBase;         // first back-reference record
     long long blkBase;         // first entry in the block tables
     int32_t nBlocks;
-    int32_t pad;
+    int32_t flags;             // LZ_OUT_FIXED | LZ_OUT_TOP_AT_TOKEN | LZ_OUT_RLE_FILL
 };
+#define LZ_OUT_FIXED 1         // Z_FIXED: no dynamic trees
+#define LZ_OUT_TOP_AT_TOKEN 2  // deflate_fast / deflate_rle tally a token in the iteration whose loop top is its start
+#define LZ_OUT_RLE_FILL 4      // deflate_rle refills the window when lookahead <= MAX_MATCH (the others: < MIN_LOOKAHEAD)
 struct LzFillJob { int32_t out, chunk; long long symBase, refBase; };   // symbols / records before this chunk in its stream
 struct LzBlockDesc {           // per emitted block
     long long symStart, symCount;   // symbols (tokens without the end-of-block) of the stream that the block holds
@@ -593,7 +768,7 @@ __global__ void __launch_bounds__(64) k_lz_fill(LzCtx c, const LzOutStream* outs
                 tok[ti + 1] = make_uint2(256u, (uint32_t)(myPos + len));
                 blocks[o.blkBase + b].uLen = myPos + len;         // end position; the host subtracts uStart
                 blocks[o.blkBase + b].refCount = myRef + (dist ? 1 : 0);   // end record; the host subtracts refStart
-                blocks[o.blkBase + b].lastTop = myPos + 1;
+                blocks[o.blkBase + b].lastTop = myPos + ((o.flags & LZ_OUT_TOP_AT_TOKEN) ? 0 : 1);
             }
         }
         pos += __shfl(il, 63);
@@ -798,15 +973,16 @@ __global__ void __launch_bounds__(64) k_lz_blocks(const LzStream* streams, const
         long long base = 0;
         {
             const long long top = B.isLast ? st.len : B.lastTop;
+            const long long la = (o.flags & LZ_OUT_RLE_FILL) ? 258 : 261;   // the largest lookahead that refills
             while (true) {
-                long long thr = base + 65275;                       // first loop top with lookahead < 262 in a full window
-                if (st.len - base < 65536) { long long a = base + 65274, b2 = st.len - 261; thr = a > b2 ? a : b2; }
+                long long thr = base + 65536 - la;                  // first loop top with lookahead <= la in a full window
+                if (st.len - base < 65536) { long long a = base + 65274, b2 = st.len - la; thr = a > b2 ? a : b2; }
                 if (top >= thr) base += 32768; else break;
             }
         }
         int type;
         if (storedLen + 4 <= best && B.uStart >= base) type = D4G_STORED;
-        else if (staticLenb == best) type = D4G_FIXED;
+        else if ((o.flags & LZ_OUT_FIXED) || staticLenb == best) type = D4G_FIXED;
         else type = D4G_DYNAMIC;
         long long litBits = 0;
         if (type == D4G_FIXED) {

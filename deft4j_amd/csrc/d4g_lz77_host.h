@@ -5,12 +5,51 @@
 // `compressor.compress(data)` followed by `Deft.optimiseDeflateStream(out)` (C/CompressorTask.java:29-35) without
 // serialising and re-parsing the intermediate stream.
 #pragma once
+#include <string>
+#include <tuple>
+
 #include "d4g_host.h"
 #include "d4g_lz77.h"
 
 namespace d4g {
 
 struct LzSpec { int32_t input, encoder, strategy; };   // mirrors d4g_encoder_spec (include/deft4g.h)
+struct LzSpecL { int32_t input, encoder, strategy, level; };   // mirrors d4g_encoder_spec_level; LzSpec = level 9
+
+// zlib 1.2.11's configuration_table (deflate.c): good_length, max_lazy (deflate_fast: max_insert_length), nice_length,
+// max_chain; levels 1-3 run deflate_fast, 4-9 deflate_slow
+struct LzLevelCfg { int good, lazy, nice, chain; };
+inline LzLevelCfg lz_level_cfg(int level) {
+    static const LzLevelCfg t[10] = {{0, 0, 0, 0},     {4, 4, 8, 4},       {4, 5, 16, 8},       {4, 6, 32, 32},     {4, 4, 16, 16},
+                                     {8, 16, 32, 32},  {8, 16, 128, 128},  {8, 32, 128, 256},   {32, 128, 258, 1024}, {32, 258, 258, 4096}};
+    return t[level];
+}
+
+// the parse a spec needs, as a key: specs with equal keys share one parse of their input.  kind -1: none (HUFFMAN_ONLY).
+struct LzParseKey {
+    int input, kind, strategy, level;
+    bool operator<(const LzParseKey& o) const {
+        return std::tie(input, kind, strategy, level) < std::tie(o.input, o.kind, o.strategy, o.level);
+    }
+};
+inline LzParseKey lz_parse_key(const LzSpecL& s) {
+    if (s.strategy == LZ_HUFFMAN_ONLY) return {s.input, -1, 0, 0};
+    if (s.strategy == LZ_RLE) return {s.input, LZ_KIND_RLE, 0, 0};
+    if (s.level <= 3) return {s.input, LZ_KIND_FAST, 0, s.level};   // deflate_fast ignores FILTERED
+    return {s.input, LZ_KIND_SLOW, s.strategy == LZ_FILTERED ? LZ_FILTERED : LZ_DEFAULT, s.level};   // FIXED parses as DEFAULT
+}
+
+// why a spec with a level is refused ("" = accepted); level -1 is zlib's Z_DEFAULT_COMPRESSION (6)
+inline std::string lz_spec_refusal(const LzSpecL& s, size_t nIn) {
+    if (s.input < 0 || (size_t)s.input >= nIn) return "encoder spec: input out of range";
+    if (s.encoder < 0 || s.encoder > 1) return "encoder spec: unknown encoder";
+    if (s.strategy < 0 || s.strategy > LZ_FIXED) return "encoder spec: unknown strategy";
+    if (s.level == 0) return "encoder spec: level 0 is not supported (zlib's deflate_stored output depends on the caller's output buffer)";
+    if (s.level < -1 || s.level > 9) return "encoder spec: level must be -1 or 1..9";
+    if (s.encoder == LZ_FLAVOR_JZLIB && (s.level != 9 || s.strategy > LZ_HUFFMAN_ONLY))
+        return "encoder spec: the jzlib flavour supports level 9 with DEFAULT / FILTERED / HUFFMAN_ONLY only";
+    return "";
+}
 
 // device buffers of the front end that must not outlive it: released before the batch's own phases start, and by the
 // destructor when an exception unwinds the front end
@@ -23,14 +62,27 @@ struct LzScratch {
 
 struct LzFront {
     Batch& B;
-    std::vector<LzSpec> specs;
+    std::vector<LzSpecL> specs;   // levels resolved (-1 -> 6)
     std::vector<i64> rawLen, rawU;
     explicit LzFront(Batch& b) : B(b) {}
 
     void create(size_t nIn, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpec* sp, bool fromDevice = false) {
+        for (size_t i = 0; i < nOut; i++)
+            if (sp[i].input < 0 || (size_t)sp[i].input >= nIn || sp[i].encoder < 0 || sp[i].encoder > 1 || sp[i].strategy < 0 || sp[i].strategy > 2)
+                throw std::runtime_error("bad encoder spec");
+        std::vector<LzSpecL> l(nOut);
+        for (size_t i = 0; i < nOut; i++) l[i] = {sp[i].input, sp[i].encoder, sp[i].strategy, 9};
+        create(nIn, raw, len, nOut, l.data(), fromDevice);
+    }
+    void create(size_t nIn, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpecL* sp, bool fromDevice = false) {
         memset(&B.stats, 0, sizeof(B.stats));
         double t0 = now_ms();
         specs.assign(sp, sp + nOut);
+        for (LzSpecL& s : specs) {
+            const std::string why = lz_spec_refusal(s, nIn);
+            if (!why.empty()) throw std::runtime_error(why);
+            if (s.level == -1) s.level = 6;
+        }
         rawLen.resize(nIn);
         rawU.resize(nIn);
         i64 off = 0;
@@ -41,9 +93,6 @@ struct LzFront {
             off += (((i64)len[i] + 15) & ~15LL) + 512;   // zero padding: the kernels read (never use) a few words past the end
             B.stats.bytes_decoded += (i64)len[i];
         }
-        for (const LzSpec& s : specs)
-            if (s.input < 0 || (size_t)s.input >= nIn || s.encoder < 0 || s.encoder > 1 || s.strategy < 0 || s.strategy > 2)
-                throw std::runtime_error("bad encoder spec");
         B.dU = (uint8_t*)rt_malloc((size_t)off + 1024);
         rt_memset(B.dU, 0, (size_t)off + 1024);
         for (size_t i = 0; i < nIn; i++) {
@@ -77,20 +126,21 @@ struct LzFront {
             i64 nsb = (rawLen[i] + LZ_SORT_BLOCK - 1) / LZ_SORT_BLOCK;
             posTot += nsb * LZ_SORT_BLOCK;
         }
-        // parses needed: (input, strategy) for DEFAULT / FILTERED; HUFFMAN_ONLY needs neither sort nor parse
-        std::map<std::pair<int, int>, int> parseOf;
-        struct Parse { int input, strategy; i64 metaBase; };
+        // parses needed: one per (input, effective parse) — lz_parse_key; HUFFMAN_ONLY needs neither sort nor parse, and
+        // deflate_rle no sort.  deflate_fast parses also get an insertion map (LZ_CHUNK_WORDS words per chunk).
+        std::map<LzParseKey, int> parseOf;
+        struct Parse { int input, kind, strategy, level; i64 metaBase, insBase; };
         std::vector<Parse> parses;
         std::vector<char> needSort(nIn, 0);
-        i64 metaTot = 0;
-        for (const LzSpec& s : specs) {
-            if (s.strategy == LZ_HUFFMAN_ONLY) continue;
-            auto key = std::make_pair((int)s.input, (int)s.strategy);
-            if (parseOf.count(key)) continue;
+        i64 metaTot = 0, insTot = 0;
+        for (const LzSpecL& s : specs) {
+            const LzParseKey key = lz_parse_key(s);
+            if (key.kind < 0 || parseOf.count(key)) continue;
             parseOf[key] = (int)parses.size();
-            parses.push_back({s.input, s.strategy, metaTot});
+            parses.push_back({key.input, key.kind, key.strategy, key.level, metaTot, key.kind == LZ_KIND_FAST ? insTot : -1});
             metaTot += hs[s.input].nChunks;
-            needSort[s.input] = 1;
+            if (key.kind == LZ_KIND_FAST) insTot += (i64)hs[s.input].nChunks * LZ_CHUNK_WORDS;
+            if (key.kind != LZ_KIND_RLE) needSort[s.input] = 1;
         }
         for (size_t i = 0; i < nIn; i++)
             if (needSort[i])
@@ -119,22 +169,56 @@ struct LzFront {
         // ---- 2. parse: speculative pass over every chunk, then exact re-runs until entry == predecessor's exit ----
         LzCtx c;
         c.streams = dStreamsLz; c.S16 = dS16; c.rank16 = dRank; c.bstart = dBstart; c.errors = B.errors();
-        c.meta = nullptr; c.chunkTok = nullptr;
+        c.meta = nullptr; c.chunkTok = nullptr; c.insLive = nullptr; c.insFrozen = nullptr; c.insChg = nullptr;
         if (metaTot > 0) {
             dMeta = tmp.own((LzChunkMeta*)rt_malloc((size_t)metaTot * sizeof(LzChunkMeta)));
             dChunkTok = tmp.own((uint32_t*)rt_malloc((size_t)metaTot * (LZ_CHUNK + 2) * 4 + 64));
             c.meta = dMeta; c.chunkTok = dChunkTok;
+            uint8_t* dFast = nullptr;
+            if (insTot > 0) {
+                c.insLive = tmp.own((uint32_t*)rt_malloc((size_t)insTot * 4 + 64));
+                c.insFrozen = tmp.own((uint32_t*)rt_malloc((size_t)insTot * 4 + 64));
+                c.insChg = tmp.own((int32_t*)rt_malloc((size_t)metaTot * 4 + 16));
+                rt_memset(c.insLive, 0xff, (size_t)insTot * 4);   // a chunk that has not run yet: "every position inserted"
+                rt_memset(c.insChg, 0xff, (size_t)metaTot * 4);   // -1: never changed
+                dFast = tmp.own((uint8_t*)rt_malloc((size_t)metaTot + 16));
+            }
+            auto makeJob = [&](const Parse& P, int firstChunk) {
+                const LzLevelCfg g = lz_level_cfg(P.kind == LZ_KIND_RLE ? 9 : P.level);
+                return LzParseJob{P.input, firstChunk, (int32_t)P.metaBase, P.strategy, g.good, g.lazy, g.nice, g.chain, P.insBase};
+            };
+            // one launch per parse kind (each its own kernel); the jobs are grouped by kind
+            auto launch = [&](std::vector<LzParseJob>& jobs, const std::vector<int>& kindOf, int exact, const uint8_t* dHeadsArg, int pass,
+                              LzParseJob* dJobs) {
+                std::vector<LzParseJob> sorted;
+                size_t cnt[3] = {0, 0, 0};
+                for (int k = 0; k < 3; k++)
+                    for (size_t j = 0; j < jobs.size(); j++)
+                        if (kindOf[j] == k) { sorted.push_back(jobs[j]); cnt[k]++; }
+                rt_h2d(dJobs, sorted.data(), sorted.size() * sizeof(LzParseJob));
+                const unsigned threads = exact ? 64 : 64 * LZ_PARSE_MAXWAVES;
+                size_t off = 0;
+                if (cnt[LZ_KIND_SLOW]) { RT_LAUNCH(k_lz_parse<LZ_KIND_SLOW>, cnt[0], threads, c, dJobs + off, exact, dHeadsArg, pass); B.stats.kernel_launches++; }
+                off += cnt[0];
+                if (cnt[LZ_KIND_FAST]) { RT_LAUNCH(k_lz_parse<LZ_KIND_FAST>, cnt[1], threads, c, dJobs + off, exact, dHeadsArg, pass); B.stats.kernel_launches++; }
+                off += cnt[1];
+                if (cnt[LZ_KIND_RLE]) { RT_LAUNCH(k_lz_parse<LZ_KIND_RLE>, cnt[2], threads, c, dJobs + off, exact, dHeadsArg, pass); B.stats.kernel_launches++; }
+            };
             std::vector<LzParseJob> jobs;
+            std::vector<int> jobKind;
             std::vector<int32_t> chunkIndex((size_t)metaTot), chunkParse((size_t)metaTot);
+            std::vector<uint8_t> chunkFast((size_t)metaTot, 0);
             for (size_t pi = 0; pi < parses.size(); pi++) {
                 const Parse& P = parses[pi];
-                for (int fc = 0; fc < hs[P.input].nChunks; fc += LZ_PARSE_MAXWAVES) jobs.push_back({P.input, fc, (int32_t)P.metaBase, P.strategy});
-                for (int k = 0; k < hs[P.input].nChunks; k++) { chunkIndex[P.metaBase + k] = k; chunkParse[P.metaBase + k] = (int32_t)pi; }
+                for (int fc = 0; fc < hs[P.input].nChunks; fc += LZ_PARSE_MAXWAVES) { jobs.push_back(makeJob(P, fc)); jobKind.push_back(P.kind); }
+                for (int k = 0; k < hs[P.input].nChunks; k++) {
+                    chunkIndex[P.metaBase + k] = k; chunkParse[P.metaBase + k] = (int32_t)pi;
+                    chunkFast[P.metaBase + k] = P.kind == LZ_KIND_FAST;
+                }
             }
+            if (dFast) rt_h2d(dFast, chunkFast.data(), (size_t)metaTot);
             LzParseJob* dJobs = (LzParseJob*)rt_malloc(std::max(jobs.size(), (size_t)metaTot) * sizeof(LzParseJob) + 16);
-            rt_h2d(dJobs, jobs.data(), jobs.size() * sizeof(LzParseJob));
-            RT_LAUNCH(k_lz_parse, jobs.size(), 64 * LZ_PARSE_MAXWAVES, c, dJobs, 0, (const uint8_t*)nullptr);
-            B.stats.kernel_launches++;
+            launch(jobs, jobKind, 0, nullptr, 0, dJobs);
             B.stats.lz_parse_passes = 1;
             int32_t* dIdx = tmp.own((int32_t*)rt_malloc((size_t)metaTot * 4 + 16));
             int32_t* dRedo = tmp.own((int32_t*)rt_malloc((size_t)metaTot * 4 + 16));
@@ -142,10 +226,10 @@ struct LzFront {
             unsigned* dN = tmp.own((unsigned*)rt_malloc(16));
             rt_h2d(dIdx, chunkIndex.data(), (size_t)metaTot * 4);
             std::vector<uint8_t> heads((size_t)metaTot);
-            for (int pass = 0;; pass++) {
+            for (int pass = 1;; pass++) {
                 if (pass > 100000) throw std::runtime_error("lz77 parse did not converge");
                 rt_memset(dN, 0, 4);
-                RT_LAUNCH(k_lz_check, (metaTot + 255) / 256, 256, dMeta, dIdx, (int)metaTot, dRedo, dN);
+                RT_LAUNCH(k_lz_check, (metaTot + 255) / 256, 256, dMeta, dIdx, (int)metaTot, dRedo, dN, (const uint8_t*)dFast, (const int32_t*)c.insChg);
                 B.stats.kernel_launches++;
                 unsigned nr = 0;
                 rt_d2h(&nr, dN, 4);
@@ -154,22 +238,27 @@ struct LzFront {
                 rt_d2h(redo.data(), dRedo, (size_t)nr * 4);
                 // A run of consecutive disagreeing chunks is one job: its first chunk (the head) is re-run from its
                 // predecessor's exit and the wave carries on through the run — and beyond, while exits keep differing
-                // from recorded entries — until it falls into step or reaches another job's head.
+                // from recorded entries — until it falls into step or reaches another job's head.  In the first exact
+                // pass a deflate_fast chunk stale only through insertion bits (bit 31) starts a job of its own: after
+                // the speculative pass nearly every chunk is, and each needs only its predecessors' first-pass bits.
+                // Later, chains of dependent chunks converge faster as one wave than one chunk per pass.
                 std::fill(heads.begin(), heads.end(), 0);
                 std::vector<char> bad((size_t)metaTot, 0);
-                for (unsigned k = 0; k < nr; k++) bad[redo[k]] = 1;
+                for (unsigned k = 0; k < nr; k++) bad[redo[k] & 0x7fffffff] = 1;
                 std::vector<LzParseJob> rj;
+                std::vector<int> rjKind;
                 for (unsigned k = 0; k < nr; k++) {
-                    const int m = redo[k];
-                    if (chunkIndex[m] > 0 && bad[m - 1]) continue;   // inside a run: the run's head gets there
+                    const int m = redo[k] & 0x7fffffff;
+                    const bool bitsOnly = redo[k] < 0;
+                    if (chunkIndex[m] > 0 && bad[m - 1] && !(bitsOnly && pass == 1)) continue;   // inside a run: the run's head gets there
                     const Parse& P = parses[chunkParse[m]];
-                    rj.push_back({P.input, chunkIndex[m], (int32_t)P.metaBase, P.strategy});
+                    rj.push_back(makeJob(P, chunkIndex[m]));
+                    rjKind.push_back(P.kind);
                     heads[m] = 1;
                 }
                 rt_h2d(dHeads, heads.data(), (size_t)metaTot);
-                rt_h2d(dJobs, rj.data(), rj.size() * sizeof(LzParseJob));
-                RT_LAUNCH(k_lz_parse, rj.size(), 64, c, dJobs, 1, (const uint8_t*)dHeads);
-                B.stats.kernel_launches++;
+                if (insTot > 0) rt_d2d((void*)c.insFrozen, c.insLive, (size_t)insTot * 4);   // what this pass's runs read
+                launch(rj, rjKind, 1, dHeads, pass, dJobs);
                 B.stats.lz_parse_passes++;
                 B.stats.lz_chunks_rerun += nr;
             }
@@ -186,13 +275,14 @@ struct LzFront {
         std::vector<i64> outSyms(nOut), outRefs(nOut);
         std::vector<std::vector<i64>> symPreOf(nOut), refPreOf(nOut);
         std::vector<char> lastIsMatchOf(nOut, 0);
+        std::vector<int> kindOf(nOut, -1);
         // jzlib flavour: its early-flush decisions need prefix sums at symbol granularity -> k_lz_split
         std::vector<LzSplitJob> splitJobs;
         std::vector<size_t> splitOut;
         std::vector<i64> preSym, preRef, preDc;
         i64 splitSlots = 0;
         for (size_t oi = 0; oi < nOut; oi++) {
-            const LzSpec& sp = specs[oi];
+            const LzSpecL& sp = specs[oi];
             const LzStream& st = hs[sp.input];
             LzOutStream& o = outs[oi];
             o.stream = sp.input;
@@ -202,8 +292,12 @@ struct LzFront {
             refPre.assign(st.nChunks + 1, 0);
             std::vector<i64> dcPre(st.nChunks + 1, 0);
             bool lastIsMatch = false;
-            if (sp.strategy != LZ_HUFFMAN_ONLY) {
-                const Parse& P = parses[parseOf[std::make_pair((int)sp.input, (int)sp.strategy)]];
+            const LzParseKey pk = lz_parse_key(sp);
+            o.flags = (sp.strategy == LZ_FIXED ? LZ_OUT_FIXED : 0) | (pk.kind == LZ_KIND_FAST || pk.kind == LZ_KIND_RLE ? LZ_OUT_TOP_AT_TOKEN : 0) |
+                      (pk.kind == LZ_KIND_RLE ? LZ_OUT_RLE_FILL : 0);
+            kindOf[oi] = pk.kind;
+            if (pk.kind >= 0) {
+                const Parse& P = parses[parseOf[pk]];
                 o.metaBase = (int32_t)P.metaBase;
                 for (int k = 0; k < st.nChunks; k++) {
                     const LzChunkMeta& m = meta[P.metaBase + k];
@@ -252,7 +346,7 @@ struct LzFront {
         }
         size_t splitIdx = 0;
         for (size_t oi = 0; oi < nOut; oi++) {
-            const LzSpec& sp = specs[oi];
+            const LzSpecL& sp = specs[oi];
             const LzStream& st = hs[sp.input];
             LzOutStream& o = outs[oi];
             const i64 N = outSyms[oi], R = outRefs[oi];
@@ -273,8 +367,8 @@ struct LzFront {
                 // zlib: a block is flushed after LZ_SYMS_PER_BLOCK symbols (lit_bufsize - 1).  The symbol that fills a
                 // block exactly at the end of the input flushes it as a non-last block — and an empty last block
                 // follows — unless it is the literal deflate_slow's epilogue emits after its loop (its flush flag is
-                // ignored); deflate_huff (zlib's HUFFMAN_ONLY) has no such epilogue.
-                const bool epilogueLiteral = sp.strategy != LZ_HUFFMAN_ONLY && !lastIsMatchOf[oi];
+                // ignored); deflate_huff, deflate_fast and deflate_rle have no such epilogue.
+                const bool epilogueLiteral = kindOf[oi] == LZ_KIND_SLOW && !lastIsMatchOf[oi];
                 i64 cur = 0;
                 while (true) {
                     i64 take = std::min<i64>(LZ_SYMS_PER_BLOCK, N - cur);
@@ -289,7 +383,6 @@ struct LzFront {
             o.nBlocks = (int32_t)(blocks.size() - o.blkBase);
             o.tokBase = tokTot;
             o.refBase = refTot;
-            o.pad = 0;
             tokTot += N + o.nBlocks;
             refTot += R;
             for (int k = 0; k < std::max(1, (int)st.nChunks); k++)

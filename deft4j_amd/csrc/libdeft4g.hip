@@ -222,15 +222,8 @@ int d4g_batch_run_encode(d4g_batch* b, int optimise, int merge_blocks) {
     }
 }
 
-int d4g_deflate_streams(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int strategy, uint8_t** out,
-                        size_t* out_len) {
-    enter_ctx(nullptr);
-    if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) { out[i] = nullptr; out_len[i] = 0; }
-    std::vector<d4g_encoder_spec> sp(n);
-    for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy};
-    d4g_batch* b = d4g_batch_create_encode(n, raw, raw_len, n, sp.data());
-    if (!b) return D4G_ERR_RUNTIME;
+// outputs of an encoder batch to malloc'd buffers (d4g_deflate_streams*); destroys the batch
+static int encode_outputs(d4g_batch* b, size_t n, uint8_t** out, size_t* out_len) {
     int rc = d4g_batch_run_encode(b, 0, 0);
     for (size_t i = 0; i < n && rc == D4G_OK; i++) {
         size_t ol = 0;
@@ -246,6 +239,56 @@ int d4g_deflate_streams(size_t n, const uint8_t* const* raw, const size_t* raw_l
     d4g_batch_destroy(b);
     g_err = keep;
     return rc;
+}
+
+d4g_batch* d4g_batch_create_encode_level(size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_out,
+                                         const d4g_encoder_spec_level* spec) {
+    enter_ctx(nullptr);
+    D4G_API_LOCK();
+    if (!ready()) { fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded"); return nullptr; }
+    if ((n_in && (!raw || !raw_len)) || (n_out && !spec)) { fail(D4G_ERR_ARG, "null argument"); return nullptr; }
+    static_assert(sizeof(LzSpecL) == sizeof(d4g_encoder_spec_level), "spec layout");
+    for (size_t i = 0; i < n_out; i++) {
+        const std::string why = lz_spec_refusal(((const LzSpecL*)spec)[i], n_in);
+        if (!why.empty()) { fail(D4G_ERR_ARG, why); return nullptr; }
+    }
+    try {
+        bind_device();
+        std::unique_ptr<d4g_batch> b(new d4g_batch());
+        b->ctx = rt_ctx();
+        b->lz.reset(new LzFront(b->impl));
+        b->lz->create(n_in, raw, raw_len, n_out, (const LzSpecL*)spec);
+        return b.release();
+    } catch (const std::exception& ex) {
+        fail(D4G_ERR_RUNTIME, ex.what());
+        return nullptr;
+    }
+}
+
+int d4g_deflate_streams_level(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy,
+                              uint8_t** out, size_t* out_len) {
+    enter_ctx(nullptr);
+    if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) { out[i] = nullptr; out_len[i] = 0; }
+    const std::string why = lz_spec_refusal(LzSpecL{0, encoder, strategy, level}, 1);
+    if (!why.empty()) return fail(D4G_ERR_ARG, why);
+    std::vector<d4g_encoder_spec_level> sp(n);
+    for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy, level};
+    d4g_batch* b = d4g_batch_create_encode_level(n, raw, raw_len, n, sp.data());
+    if (!b) return D4G_ERR_RUNTIME;
+    return encode_outputs(b, n, out, out_len);
+}
+
+int d4g_deflate_streams(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int strategy, uint8_t** out,
+                        size_t* out_len) {
+    enter_ctx(nullptr);
+    if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) { out[i] = nullptr; out_len[i] = 0; }
+    std::vector<d4g_encoder_spec> sp(n);
+    for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy};
+    d4g_batch* b = d4g_batch_create_encode(n, raw, raw_len, n, sp.data());
+    if (!b) return D4G_ERR_RUNTIME;
+    return encode_outputs(b, n, out, out_len);
 }
 
 int d4g_batch_stream_result(d4g_batch* b, size_t i, int32_t* status, int64_t* saved_bits, size_t* out_len, size_t* consumed,

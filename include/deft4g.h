@@ -140,6 +140,19 @@ int d4g_batch_run_encode(d4g_batch* b, int optimise, int merge_blocks);
 /* SingleCompressor.compressSingle for n inputs with one encoder setting: out[i] is always set (release with d4g_free) */
 int d4g_deflate_streams(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int strategy, uint8_t** out,
                         size_t* out_len);
+/* The same encoders at a compression level (java.util.zip.Deflater / zlib levels): output byte-identical to zlib 1.2.11
+ * deflateInit2(level, Z_DEFLATED, -15, 8, strategy).  Levels 1-3 run deflate_fast, 4-9 deflate_slow with zlib's
+ * configuration table; -1 (Z_DEFAULT_COMPRESSION) means 6.  Strategies add Z_RLE (distance-1 runs, any level) and
+ * Z_FIXED (the level's parse, fixed trees or stored blocks only).  Refused with D4G_ERR_ARG / a NULL batch: level 0
+ * (deflate_stored's blocks depend on the caller's output buffer), levels outside -1..9, and the jzlib flavour at any
+ * level but 9 or with RLE / FIXED.  The result of d4g_batch_create_encode_level runs with d4g_batch_run_encode. */
+#define D4G_STRATEGY_RLE 3
+#define D4G_STRATEGY_FIXED 4
+typedef struct d4g_encoder_spec_level { int32_t input, encoder, strategy, level; } d4g_encoder_spec_level;
+d4g_batch* d4g_batch_create_encode_level(size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_out,
+                                         const d4g_encoder_spec_level* spec);
+int d4g_deflate_streams_level(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy,
+                              uint8_t** out, size_t* out_len);
 
 /* ---- recompress modes (deft4j-cmd/.../cmd/CMDUtil.java:44-50, Optimise.java `--mode`) ----
  * mode = ordinal of RecompressMode: the compressor list CompressionUtil.getCompressors builds for it (:44-78), in list

@@ -17,6 +17,8 @@ public final class NativeDeft {
     public static final int ENC_JVM = 0, ENC_JZLIB = 1;
     /** java.util.zip.Deflater strategy constants map 1:1: DEFAULT_STRATEGY 0, FILTERED 1, HUFFMAN_ONLY 2 */
     public static final int STRATEGY_DEFAULT = 0, STRATEGY_FILTERED = 1, STRATEGY_HUFFMAN_ONLY = 2;
+    /** zlib's Z_RLE and Z_FIXED (deflateStreamsLevel only) */
+    public static final int STRATEGY_RLE = 3, STRATEGY_FIXED = 4;
 
     static {
         System.loadLibrary("deft4g_jni");
@@ -61,6 +63,9 @@ public final class NativeDeft {
 
     /** SingleCompressor.compressSingle for every buffer */
     public static native byte[][] deflateStreams(byte[][] raw, int encoder, int strategy) throws java.io.IOException;
+
+    /** The same at a Deflater / zlib level: -1 (DEFAULT_COMPRESSION = 6) or 1..9; strategies add RLE and FIXED */
+    public static native byte[][] deflateStreamsLevel(byte[][] raw, int encoder, int level, int strategy) throws java.io.IOException;
 
     /** MultiCafeUndZopfliCompressor / MultiJZopfliCompressor.compressWithOptions for every buffer (splitting: 0 FIRST, 1 LAST, 2 NONE) */
     public static native byte[][] zopfliStreams(byte[][] raw, int iterations, int splitting, int maxBlocks, long masterBlock) throws java.io.IOException;

@@ -9,20 +9,30 @@ import com.github.NeRdTheNed.deft4j.NativeDeft;
  * JavaCompressor(strategy) for encoder ENC_JVM (zlib level 9; pinned by the asyoulik fixture), the jzlib restatement for
  * ENC_JZLIB.  CompressionUtil.getCompressors (CompressionUtil.java:44-78) would add
  *     new GpuCompressor(NativeDeft.ENC_JVM, Deflater.DEFAULT_STRATEGY) ...
- * in place of the JavaCompressor / JZLibCompressor entries, keeping the list order.
+ * in place of the JavaCompressor / JZLibCompressor entries, keeping the list order.  The three-argument constructor takes
+ * a Deflater level (-1, 1..9; ENC_JVM only below 9) and also the strategies STRATEGY_RLE / STRATEGY_FIXED.
  */
 public class GpuCompressor implements SingleCompressor {
     private final int encoder;
+    private final int level;
     private final int strategy;
 
     public GpuCompressor(int encoder, int strategy) {
+        this(encoder, 9, strategy);
+    }
+
+    public GpuCompressor(int encoder, int level, int strategy) {
         this.encoder = encoder;
+        this.level = level;
         this.strategy = strategy;
     }
 
     @Override
     public byte[] compressSingle(byte[] uncompressedData) throws IOException {
-        return NativeDeft.deflateStreams(new byte[][] { uncompressedData }, encoder, strategy)[0];
+        if (level == 9 && strategy <= NativeDeft.STRATEGY_HUFFMAN_ONLY) {
+            return NativeDeft.deflateStreams(new byte[][] { uncompressedData }, encoder, strategy)[0];
+        }
+        return NativeDeft.deflateStreamsLevel(new byte[][] { uncompressedData }, encoder, level, strategy)[0];
     }
 
     @Override

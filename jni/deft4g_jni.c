@@ -177,6 +177,22 @@ JNIEXPORT jobjectArray JNICALL JFN(deflateStreams)(JNIEnv* e, jclass c, jobjectA
     return res;
 }
 
+/* byte[][] deflateStreamsLevel(byte[][] raw, int encoder, int level, int strategy): the same at a zlib level (-1, 1..9) */
+JNIEXPORT jobjectArray JNICALL JFN(deflateStreamsLevel)(JNIEnv* e, jclass c, jobjectArray raw, jint encoder, jint level, jint strategy) {
+    (void)c;
+    in_list L = {0};
+    jobjectArray res = NULL;
+    if (pin(e, raw, &L) == 0) {
+        uint8_t** out = calloc((size_t)L.n + 1, sizeof *out);
+        size_t* olen = calloc((size_t)L.n + 1, sizeof *olen);
+        if (d4g_deflate_streams_level((size_t)L.n, L.ptr, L.len, encoder, level, strategy, out, olen) == D4G_OK) res = to_java(e, L.n, out, olen);
+        else throw_io(e, "d4g_deflate_streams_level");
+        free(out); free(olen);
+    }
+    unpin(e, &L);
+    return res;
+}
+
 /* byte[][] zopfliStreams(byte[][] raw, int iterations, int splitting, int maxBlocks, long masterBlock):
  * MultiCafeUndZopfliCompressor / MultiJZopfliCompressor.compressWithOptions for every buffer */
 JNIEXPORT jobjectArray JNICALL JFN(zopfliStreams)(JNIEnv* e, jclass c, jobjectArray raw, jint iterations, jint splitting, jint maxBlocks, jlong masterBlock) {
