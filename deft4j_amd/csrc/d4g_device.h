@@ -70,14 +70,14 @@ D4G_DEV int ref_ebits(uint32_t a) { return (int)((a >> 19) & 31u); }
 // ---------------------------------------------------------------------------------------
 // wave64 / workgroup reductions
 // ---------------------------------------------------------------------------------------
-D4G_DEV long long wave_sum_i64(long long v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+D4G_DEV long long wave_sum_i64(long long v) {   // wraps (the mask hashes sum 64-bit values): added as unsigned
+    for (int m = 32; m >= 1; m >>= 1) v = (long long)((unsigned long long)v + (unsigned long long)__shfl_xor(v, m));
     return v;
 }
 // 32-bit wave sum: row scans and row broadcasts on the DPP path (six v_add_u32), no LDS crossbar trips
 D4G_DEV int wave_sum_i32(int v) {
 #ifdef D4G_HOSTSIM
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    for (int m = 32; m >= 1; m >>= 1) v = (int)((unsigned)v + (unsigned)__shfl_xor(v, m));   // wraps, as v_add_u32 (hash sums)
     return v;
 #else
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1

@@ -484,13 +484,16 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
     if (strict && btype != 2) return;
     if (btype == 0) {
         // DeflateBlockUncompressed.parse — B/deflate/DeflateBlockUncompressed.java:23-36
+        // BitInputStream.readBits returns -1 once EOF is hit (B/io/BitInputStream.java:59-82) and `-1 & 0xffff` is
+        // 0xffff: a cut-off LEN reads as 0xffff, which no NLEN (also 0xffff by then) matches; a cut-off NLEN reads as
+        // 0xffff, which matches LEN == 0.  The reader is then at EOF, so a following block fails its 3-bit read.
         long long r = 0, p = 0;
         if (tid == 0) {
             p = (br.pos() + 7) & ~7LL;
-            if (p + 32 > br.nbits) r = -1;
+            if (p + 16 > br.nbits) r = -1;
             else {
                 br.reset_to(L.inbuf, p);
-                int len = (int)(br.buf & 0xffff), nlen = (int)((br.buf >> 16) & 0xffff);
+                int len = (int)(br.buf & 0xffff), nlen = p + 32 > br.nbits ? 0xffff : (int)((br.buf >> 16) & 0xffff);
                 r = nlen != ((~len) & 0xffff) ? -1 : len;
             }
         }

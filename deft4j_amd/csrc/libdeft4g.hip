@@ -886,7 +886,9 @@ void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* 
     std::vector<Best> best(n);
     auto offer = [&](size_t i, int listIdx, const Batch* owner, int stream) {
         const HStream& s = owner->streams[stream];
-        long long bits = s.sizeBitsIn - s.saved;              // Deft.getSizeBitsFallback of the optimised output
+        // Deft.getSizeBitsFallback of what Deft.optimiseDeflateStream returned: the written optimised stream (a stored
+        // block's padding follows its new position) or, when nothing was saved, the input
+        long long bits = s.saved > 0 ? s.outBits : s.sizeBitsIn;
         Best& b = best[i];
         if (b.listIdx < 0 || bits < b.bits || (bits == b.bits && listIdx < b.listIdx)) { b.bits = bits; b.listIdx = listIdx; b.owner = owner; b.stream = stream; }
     };
@@ -1084,7 +1086,9 @@ static void run_recompress_locked(d4g_batch* b, int mode, int iter, bool merge) 
         const HStream& c2 = b->reopt->streams[k];
         b->reoptIndex[ok[k]] = (int)k;
         if (c2.status != 0) continue;                  // recompStream.parse failed: the original stays (:88)
-        long long recompSize = c2.sizeBitsIn - c2.saved, originalSize = a.sizeBitsIn - a.saved;
+        // recompStream.getSizeBits() / stream.getSizeBits() of the optimised streams (DeflateStream.java:171-182): the
+        // written sizes, in which a stored block's padding follows its new position (sizeBitsIn - saved does not)
+        long long recompSize = c2.outBits, originalSize = a.outBits;
         if (recompSize < originalSize) {               // :94-98
             b->graft[ok[k]] = 1;
             b->recompSaved[ok[k]] = originalSize - recompSize;
