@@ -58,12 +58,163 @@ bool rtp_ctx_ready(int k) {
 #endif
 }
 // HIP's current device is per thread: CompressionUtil's pool threads (and any rank with device != 0) must bind
-// the library's device before allocating or launching.  Called at the top of every entry point (d4g_init / d4g_shutdown hold g_mu;
-// the others run concurrently, each on its calling thread).
+// the library's device before allocating or launching.
 void bind_device() {
 #ifndef D4G_HOSTSIM
     if (rt().ready && rt().device >= 0) RT_CHECK(hipSetDevice(rt().device));
 #endif
+}
+
+// Runs `body` (returns a D4G_* code); whatever it throws becomes D4G_ERR_RUNTIME with its text — nothing crosses extern "C".
+template <class F>
+int to_code(F&& body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(D4G_ERR_RUNTIME, "out of host memory");
+    } catch (const std::exception& ex) {
+        return fail(D4G_ERR_RUNTIME, ex.what());
+    } catch (...) {
+        return fail(D4G_ERR_RUNTIME, "unknown exception");
+    }
+}
+// The guard of every entry point that works on the device, taken once per call: the emulator's lock (before the context,
+// which a second thread must not switch under the first), the batch's context or the thread's, the library initialised,
+// the device bound, then `body` through to_code.  The GPU build takes no lock here.
+template <class F>
+int api(const d4g_batch* b, F&& body) {
+    D4G_API_LOCK();
+    enter_ctx(b);
+    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
+    return to_code([&] {
+        bind_device();
+        return body();
+    });
+}
+
+// Joins its threads on every way out of a scope (a joinable std::thread's destructor calls std::terminate).
+struct Joiner {
+    std::vector<std::thread> threads;
+    void join() {
+        for (std::thread& t : threads)
+            if (t.joinable()) t.join();
+    }
+    ~Joiner() { join(); }
+};
+
+// The caller's result arrays of a one-shot call.  They hold the defined "unchanged" values from the start (out[i] = NULL,
+// out_len[i] = 0, status[i] = D4G_STREAM_UNCHANGED, the optional arrays cleared) and get them back, buffers freed, unless
+// the call commits: a failed call hands back no buffers.
+struct Outputs {
+    size_t n;
+    uint8_t** out;
+    size_t* len;
+    int32_t* status;
+    int64_t* saved;
+    int64_t* recompSaved;
+    int32_t* winner;
+    bool kept = false;
+    Outputs(size_t n, uint8_t** out, size_t* len, int32_t* status = nullptr, int64_t* saved = nullptr, int64_t* recompSaved = nullptr,
+            int32_t* winner = nullptr)
+        : n(n), out(out), len(len), status(status), saved(saved), recompSaved(recompSaved), winner(winner) {
+        reset();
+    }
+    ~Outputs() {
+        if (kept) return;
+        for (size_t i = 0; i < n; i++) free(out[i]);
+        reset();
+    }
+    int commit(int rc) {
+        kept = rc == D4G_OK;
+        return rc;
+    }
+    void reset() {
+        for (size_t i = 0; i < n; i++) {
+            out[i] = nullptr;
+            len[i] = 0;
+            if (status) status[i] = D4G_STREAM_UNCHANGED;
+            if (saved) saved[i] = 0;
+            if (recompSaved) recompSaved[i] = 0;
+            if (winner) winner[i] = -1;
+        }
+    }
+};
+
+// ---- the internal layer: what the public batch calls and the one-shot calls are made of (the guard held by the caller) ----
+std::unique_ptr<d4g_batch> make_batch(size_t n, const uint8_t* const* in, const size_t* in_len) {
+    std::unique_ptr<d4g_batch> b(new d4g_batch());
+    b->ctx = rt_ctx();
+    b->impl.create(n, in, in_len);
+    return b;
+}
+static_assert(sizeof(LzSpec) == sizeof(d4g_encoder_spec), "spec layout");
+static_assert(sizeof(LzSpecL) == sizeof(d4g_encoder_spec_level), "spec layout");
+template <class Spec>   // LzSpec or LzSpecL
+std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const Spec* spec,
+                                        bool fromDevice = false) {
+    std::unique_ptr<d4g_batch> e(new d4g_batch());
+    e->ctx = rt_ctx();
+    e->lz.reset(new LzFront(e->impl));
+    e->lz->create(n, raw, len, nOut, spec, fromDevice);
+    return e;
+}
+// one stream, parsed (and decoded): d4g_size_bits_fallback, d4g_inflate
+std::unique_ptr<d4g_batch> parse_one(const uint8_t* in, size_t len, bool decode) {
+    std::unique_ptr<d4g_batch> b = make_batch(1, &in, &len);
+    engine().init();
+    b->impl.parse_probe();
+    if (decode) b->impl.build_blocks(false, false);
+    return b;
+}
+// a malloc'd copy of n bytes of device memory
+uint8_t* host_copy(const void* src, size_t n) {
+    uint8_t* p = (uint8_t*)malloc(n ? n : 1);
+    if (!p) throw std::bad_alloc();
+    rt_d2h(p, src, n);
+    return p;
+}
+// a malloc'd copy of stream i's final bytes (the grafted recompression where it won)
+uint8_t* final_copy(const d4g_batch& b, size_t i, size_t* len) {
+    const Batch* owner = nullptr;
+    const HStream& s = b.final_stream(i, &owner);
+    *len = (size_t)((s.outBits + 7) / 8);
+    return host_copy(owner->dOut + s.outWordBase, *len);
+}
+int32_t stream_status(const d4g_batch& b, size_t i) {
+    const HStream& s = b.impl.streams[i];
+    const bool grafted = i < b.graft.size() && b.graft[i];
+    return s.status != 0 ? D4G_STREAM_PARSE_ERROR : ((s.saved > 0 || grafted) ? D4G_STREAM_CHANGED : D4G_STREAM_UNCHANGED);
+}
+// the one-shot results of a batch that ran: its stream j goes to slot idx[j] of the caller's arrays (slot j when idx is
+// null); out[] only for changed streams
+void results_into(const d4g_batch& b, const size_t* idx, uint8_t** out, size_t* out_len, int64_t* saved_bits, int32_t* status,
+                  int64_t* recompress_saved) {
+    for (size_t j = 0; j < b.impl.streams.size(); j++) {
+        const size_t i = idx ? idx[j] : j;
+        status[i] = stream_status(b, j);
+        if (status[i] == D4G_STREAM_CHANGED) out[i] = final_copy(b, j, &out_len[i]);
+        if (saved_bits) saved_bits[i] = b.impl.streams[j].status == 0 ? b.impl.streams[j].saved : 0;
+        if (recompress_saved) recompress_saved[i] = j < b.recompSaved.size() ? b.recompSaved[j] : 0;
+    }
+}
+// d4g_optimise_streams on the calling thread's context for the caller's streams idx[0..m) (0..m when idx is null)
+void optimise_into(size_t m, const size_t* idx, const uint8_t* const* in, const size_t* in_len, bool merge, uint8_t** out,
+                   size_t* out_len, int64_t* saved_bits, int32_t* status) {
+    std::vector<const uint8_t*> p(m);
+    std::vector<size_t> l(m);
+    for (size_t j = 0; j < m; j++) { p[j] = in[idx ? idx[j] : j]; l[j] = in_len[idx ? idx[j] : j]; }
+    std::unique_ptr<d4g_batch> b = make_batch(m, p.data(), l.data());
+    b->impl.run(merge);
+    results_into(*b, idx, out, out_len, saved_bits, status, nullptr);
+}
+// an encoder batch's outputs as the encoder emits them, to the caller's out[] (d4g_deflate_streams*)
+int encode_into(d4g_batch& b, uint8_t** out, size_t* out_len) {
+    b.lz->run(false, false);
+    for (size_t i = 0; i < b.impl.streams.size(); i++) {
+        if (b.impl.streams[i].status != 0) return fail(D4G_ERR_ARG, "stream did not parse");
+        out[i] = final_copy(b, i, &out_len[i]);
+    }
+    return D4G_OK;
 }
 }  // namespace
 
@@ -93,31 +244,23 @@ static int init_ctx(int ctx, int device_index) {
 
 int d4g_init(int device_index) {
     std::lock_guard<std::mutex> lk(g_mu);
-    try {
-        int rc = init_ctx(0, device_index);
-        if (rc == D4G_OK && g_nCtx < 1) g_nCtx = 1;
-        rt_ctx() = g_tlsCtx;
-        return rc;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    const int rc = to_code([&] { return init_ctx(0, device_index); });
+    if (rc == D4G_OK && g_nCtx < 1) g_nCtx = 1;
+    rt_ctx() = g_tlsCtx;
+    return rc;
 }
 
 int d4g_init_devices(int n, const int* device_index) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (n < 1 || n > RT_MAX_CTX || !device_index) return fail(D4G_ERR_ARG, "1 to 16 contexts");
-    try {
-        for (int k = 0; k < n; k++) {
-            int rc = init_ctx(k, device_index[k]);
-            if (rc != D4G_OK) { rt_ctx() = g_tlsCtx; return rc; }
-        }
-        g_nCtx = std::max(g_nCtx, n);
-        rt_ctx() = g_tlsCtx;
+    const int rc = to_code([&] {
+        for (int k = 0; k < n; k++)
+            if (int rck = init_ctx(k, device_index[k])) return rck;
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        rt_ctx() = g_tlsCtx;
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
+    if (rc == D4G_OK) g_nCtx = std::max(g_nCtx, n);
+    rt_ctx() = g_tlsCtx;
+    return rc;
 }
 
 int d4g_device_count(void) { return g_nCtx; }
@@ -134,7 +277,7 @@ void d4g_shutdown(void) {
     for (int k = 0; k < RT_MAX_CTX; k++) {
         rt_ctx() = k;
         if (!rt().ready) continue;
-        try {
+        to_code([&] {
             bind_device();
             rt_sync_all();
             engine().release();
@@ -148,8 +291,8 @@ void d4g_shutdown(void) {
             }
             rt().device = -1;
 #endif
-        } catch (const std::exception&) {
-        }
+            return D4G_OK;
+        });
         rt().ready = false;
     }
     g_nCtx = 0;
@@ -158,149 +301,88 @@ void d4g_shutdown(void) {
 }
 
 d4g_batch* d4g_batch_create(size_t n, const uint8_t* const* in, const size_t* in_len) {
-    enter_ctx(nullptr);
-    D4G_API_LOCK();
-    if (!ready()) { fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded"); return nullptr; }
-    try {
-        bind_device();
-        std::unique_ptr<d4g_batch> b(new d4g_batch());
-        b->ctx = rt_ctx();
-        b->impl.create(n, in, in_len);
-        return b.release();
-    } catch (const std::exception& ex) {
-        fail(D4G_ERR_RUNTIME, ex.what());
-        return nullptr;
-    }
+    d4g_batch* b = nullptr;
+    api(nullptr, [&] {
+        b = make_batch(n, in, in_len).release();
+        return D4G_OK;
+    });
+    return b;
 }
 
 int d4g_batch_run(d4g_batch* b, int merge_blocks) {
-    enter_ctx(b);
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    if (!b) return fail(D4G_ERR_ARG, "null batch");
-    if (b->lz) return fail(D4G_ERR_ARG, "encoder batch: use d4g_batch_run_encode");
-    try {
-        bind_device();
+    return api(b, [&] {
+        if (!b) return fail(D4G_ERR_ARG, "null batch");
+        if (b->lz) return fail(D4G_ERR_ARG, "encoder batch: use d4g_batch_run_encode");
         b->impl.run(merge_blocks != 0);
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 d4g_batch* d4g_batch_create_encode(size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_out,
                                    const d4g_encoder_spec* spec) {
-    enter_ctx(nullptr);
-    D4G_API_LOCK();
-    if (!ready()) { fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded"); return nullptr; }
-    if ((n_in && (!raw || !raw_len)) || (n_out && !spec)) { fail(D4G_ERR_ARG, "null argument"); return nullptr; }
-    try {
-        bind_device();
-        static_assert(sizeof(LzSpec) == sizeof(d4g_encoder_spec), "spec layout");
-        std::unique_ptr<d4g_batch> b(new d4g_batch());
-        b->ctx = rt_ctx();
-        b->lz.reset(new LzFront(b->impl));
-        b->lz->create(n_in, raw, raw_len, n_out, (const LzSpec*)spec);
-        return b.release();
-    } catch (const std::exception& ex) {
-        fail(D4G_ERR_RUNTIME, ex.what());
-        return nullptr;
-    }
+    d4g_batch* b = nullptr;
+    api(nullptr, [&] {
+        if ((n_in && (!raw || !raw_len)) || (n_out && !spec)) return fail(D4G_ERR_ARG, "null argument");
+        b = encode_batch(n_in, raw, raw_len, n_out, (const LzSpec*)spec).release();
+        return D4G_OK;
+    });
+    return b;
 }
 
 int d4g_batch_run_encode(d4g_batch* b, int optimise, int merge_blocks) {
-    enter_ctx(b);
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    if (!b || !b->lz) return fail(D4G_ERR_ARG, "not an encoder batch");
-    try {
-        bind_device();
+    return api(b, [&] {
+        if (!b || !b->lz) return fail(D4G_ERR_ARG, "not an encoder batch");
         b->lz->run(optimise != 0, merge_blocks != 0);
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
-}
-
-// outputs of an encoder batch to malloc'd buffers (d4g_deflate_streams*); destroys the batch
-static int encode_outputs(d4g_batch* b, size_t n, uint8_t** out, size_t* out_len) {
-    int rc = d4g_batch_run_encode(b, 0, 0);
-    for (size_t i = 0; i < n && rc == D4G_OK; i++) {
-        size_t ol = 0;
-        d4g_batch_stream_result(b, i, nullptr, nullptr, &ol, nullptr, nullptr);
-        out[i] = (uint8_t*)malloc(ol ? ol : 1);
-        if (!out[i]) { rc = fail(D4G_ERR_RUNTIME, "out of host memory"); break; }
-        rc = d4g_batch_copy_output(b, i, out[i], ol);
-        out_len[i] = ol;
-    }
-    if (rc != D4G_OK)
-        for (size_t i = 0; i < n; i++) { free(out[i]); out[i] = nullptr; out_len[i] = 0; }
-    std::string keep = g_err;
-    d4g_batch_destroy(b);
-    g_err = keep;
-    return rc;
+    });
 }
 
 d4g_batch* d4g_batch_create_encode_level(size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_out,
                                          const d4g_encoder_spec_level* spec) {
-    enter_ctx(nullptr);
-    D4G_API_LOCK();
-    if (!ready()) { fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded"); return nullptr; }
-    if ((n_in && (!raw || !raw_len)) || (n_out && !spec)) { fail(D4G_ERR_ARG, "null argument"); return nullptr; }
-    static_assert(sizeof(LzSpecL) == sizeof(d4g_encoder_spec_level), "spec layout");
-    for (size_t i = 0; i < n_out; i++) {
-        const std::string why = lz_spec_refusal(((const LzSpecL*)spec)[i], n_in);
-        if (!why.empty()) { fail(D4G_ERR_ARG, why); return nullptr; }
-    }
-    try {
-        bind_device();
-        std::unique_ptr<d4g_batch> b(new d4g_batch());
-        b->ctx = rt_ctx();
-        b->lz.reset(new LzFront(b->impl));
-        b->lz->create(n_in, raw, raw_len, n_out, (const LzSpecL*)spec);
-        return b.release();
-    } catch (const std::exception& ex) {
-        fail(D4G_ERR_RUNTIME, ex.what());
-        return nullptr;
-    }
+    d4g_batch* b = nullptr;
+    api(nullptr, [&] {
+        if ((n_in && (!raw || !raw_len)) || (n_out && !spec)) return fail(D4G_ERR_ARG, "null argument");
+        for (size_t i = 0; i < n_out; i++) {
+            const std::string why = lz_spec_refusal(((const LzSpecL*)spec)[i], n_in);
+            if (!why.empty()) return fail(D4G_ERR_ARG, why);
+        }
+        b = encode_batch(n_in, raw, raw_len, n_out, (const LzSpecL*)spec).release();
+        return D4G_OK;
+    });
+    return b;
 }
 
 int d4g_deflate_streams_level(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy,
                               uint8_t** out, size_t* out_len) {
-    enter_ctx(nullptr);
     if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) { out[i] = nullptr; out_len[i] = 0; }
+    Outputs o(n, out, out_len);
     const std::string why = lz_spec_refusal(LzSpecL{0, encoder, strategy, level}, 1);
     if (!why.empty()) return fail(D4G_ERR_ARG, why);
-    std::vector<d4g_encoder_spec_level> sp(n);
-    for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy, level};
-    d4g_batch* b = d4g_batch_create_encode_level(n, raw, raw_len, n, sp.data());
-    if (!b) return D4G_ERR_RUNTIME;
-    return encode_outputs(b, n, out, out_len);
+    return o.commit(api(nullptr, [&] {
+        std::vector<LzSpecL> sp(n);
+        for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy, level};
+        return encode_into(*encode_batch(n, raw, raw_len, n, sp.data()), out, out_len);
+    }));
 }
 
 int d4g_deflate_streams(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int strategy, uint8_t** out,
                         size_t* out_len) {
-    enter_ctx(nullptr);
     if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) { out[i] = nullptr; out_len[i] = 0; }
-    std::vector<d4g_encoder_spec> sp(n);
-    for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy};
-    d4g_batch* b = d4g_batch_create_encode(n, raw, raw_len, n, sp.data());
-    if (!b) return D4G_ERR_RUNTIME;
-    return encode_outputs(b, n, out, out_len);
+    Outputs o(n, out, out_len);
+    return o.commit(api(nullptr, [&] {
+        std::vector<LzSpec> sp(n);
+        for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy};
+        return encode_into(*encode_batch(n, raw, raw_len, n, sp.data()), out, out_len);
+    }));
 }
 
 int d4g_batch_stream_result(d4g_batch* b, size_t i, int32_t* status, int64_t* saved_bits, size_t* out_len, size_t* consumed,
                             int64_t* size_bits_in) {
-    enter_ctx(b);
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     const HStream& s = b->impl.streams[i];
     const Batch* owner = nullptr;
     const HStream& f = b->final_stream(i, &owner);
-    const bool grafted = owner != &b->impl;
-    int st = s.status != 0 ? D4G_STREAM_PARSE_ERROR : ((s.saved > 0 || grafted) ? D4G_STREAM_CHANGED : D4G_STREAM_UNCHANGED);
-    if (status) *status = st;
+    if (status) *status = stream_status(*b, i);
     if (saved_bits) *saved_bits = s.status == 0 ? s.saved : 0;
     if (out_len) *out_len = s.status == 0 ? (size_t)((f.outBits + 7) / 8) : 0;
     if (consumed) *consumed = (size_t)s.consumed;
@@ -309,132 +391,77 @@ int d4g_batch_stream_result(d4g_batch* b, size_t i, int32_t* status, int64_t* sa
 }
 
 int d4g_batch_copy_output(d4g_batch* b, size_t i, uint8_t* dst, size_t cap) {
-    enter_ctx(b);
-    D4G_API_LOCK();
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     if (b->impl.streams[i].status != 0) return fail(D4G_ERR_ARG, "stream did not parse");
     const Batch* owner = nullptr;
     const HStream& s = b->final_stream(i, &owner);
     size_t n = (size_t)((s.outBits + 7) / 8);
     if (cap < n) return fail(D4G_ERR_ARG, "output buffer too small");
-    try {
-        bind_device();
+    return api(b, [&] {
         rt_d2h(dst, (const uint8_t*)(owner->dOut + s.outWordBase), n);
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 int d4g_batch_copy_decoded(d4g_batch* b, size_t i, uint8_t* dst, size_t cap, size_t* len) {
-    enter_ctx(b);
-    D4G_API_LOCK();
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     const HStream& s = b->impl.streams[i];
     if (s.status != 0) return fail(D4G_ERR_ARG, "stream did not parse");
     if (len) *len = (size_t)s.nU;
     if (!dst) return D4G_OK;
     if (cap < (size_t)s.nU) return fail(D4G_ERR_ARG, "output buffer too small");
-    try {
-        bind_device();
+    return api(b, [&] {
         rt_d2h(dst, b->impl.dU + s.uBase, (size_t)s.nU);
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 int d4g_batch_parse(d4g_batch* b) {
-    enter_ctx(b);
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    if (!b) return fail(D4G_ERR_ARG, "null batch");
-    try {
-        bind_device();
+    return api(b, [&] {
+        if (!b) return fail(D4G_ERR_ARG, "null batch");
         if (b->impl.ran) return fail(D4G_ERR_ARG, "batch already ran");
         b->impl.ran = true;
         engine().init();
         b->impl.parse_probe();
         b->impl.build_blocks(false, false);
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 int d4g_batch_checksums(d4g_batch* b, size_t i, uint32_t* crc32, uint32_t* adler32, int64_t* isize) {
-    enter_ctx(b);
-    D4G_API_LOCK();
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     if (b->impl.streams[i].status != 0) return fail(D4G_ERR_ARG, "stream did not parse");
-    try {
-        bind_device();
+    return api(b, [&] {
         b->impl.checksums();
         const D4GCsumOut& o = b->impl.csums[i];
         if (crc32) *crc32 = o.crc32;
         if (adler32) *adler32 = o.adler32;
         if (isize) *isize = o.isize;
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 int d4g_batch_stats(d4g_batch* b, d4g_stats* st) {
-    enter_ctx(b);
     if (!b || !st) return fail(D4G_ERR_ARG, "null argument");
     *st = b->impl.stats;
     return D4G_OK;
 }
 
-void d4g_batch_destroy(d4g_batch* b) {
-    enter_ctx(b);
+void d4g_batch_destroy(d4g_batch* b) {   // deletes the batch whatever state the library is in (after d4g_shutdown too)
     D4G_API_LOCK();
-    try { bind_device(); } catch (const std::exception&) {}
+    enter_ctx(b);
+    try { bind_device(); } catch (...) {}
     delete b;
 }
 
 int d4g_optimise_streams(size_t n, const uint8_t* const* in, const size_t* in_len, int merge_blocks, uint8_t** out,
                          size_t* out_len, int64_t* saved_bits, int32_t* status) {
-    enter_ctx(nullptr);
     if (n && (!in || !in_len || !out || !out_len || !status)) return fail(D4G_ERR_ARG, "null argument");
-    // every result slot is defined whatever happens below: "keep the original" until a stream is known to have changed
-    for (size_t i = 0; i < n; i++) {
-        out[i] = nullptr;
-        out_len[i] = 0;
-        status[i] = D4G_STREAM_UNCHANGED;
-        if (saved_bits) saved_bits[i] = 0;
-    }
-    d4g_batch* b = d4g_batch_create(n, in, in_len);
-    if (!b) return D4G_ERR_RUNTIME;
-    int rc = d4g_batch_run(b, merge_blocks);
-    for (size_t i = 0; i < n && rc == D4G_OK; i++) {
-        int64_t sv = 0;
-        size_t ol = 0;
-        int32_t st = D4G_STREAM_UNCHANGED;
-        d4g_batch_stream_result(b, i, &st, &sv, &ol, nullptr, nullptr);
-        if (st == D4G_STREAM_CHANGED) {
-            out[i] = (uint8_t*)malloc(ol ? ol : 1);
-            if (!out[i]) { rc = fail(D4G_ERR_RUNTIME, "out of host memory"); break; }
-            rc = d4g_batch_copy_output(b, i, out[i], ol);
-            if (rc != D4G_OK) break;
-            out_len[i] = ol;
-        }
-        status[i] = st;
-        if (saved_bits) saved_bits[i] = sv;
-    }
-    if (rc != D4G_OK)   // all-or-nothing: a failed call hands back no buffers
-        for (size_t i = 0; i < n; i++) {
-            free(out[i]);
-            out[i] = nullptr;
-            out_len[i] = 0;
-            status[i] = D4G_STREAM_UNCHANGED;
-            if (saved_bits) saved_bits[i] = 0;
-        }
-    std::string keep = g_err;
-    d4g_batch_destroy(b);
-    g_err = keep;
-    return rc;
+    Outputs o(n, out, out_len, status, saved_bits);
+    return o.commit(api(nullptr, [&] {
+        optimise_into(n, nullptr, in, in_len, merge_blocks != 0, out, out_len, saved_bits, status);
+        return D4G_OK;
+    }));
 }
 
 d4g_batch* d4g_batch_create_on(int context, size_t n, const uint8_t* const* in, const size_t* in_len) {
@@ -449,120 +476,71 @@ d4g_batch* d4g_batch_create_on(int context, size_t n, const uint8_t* const* in, 
 // DeflateFilesContainer.optimise(List<DeflateStream>, boolean) over every initialised context (K/DeflateFilesContainer.java:18-43:
 // the streams are independent): longest-processing-time-first partition by compressed size, one host thread and one batch per
 // context, no exchange between the devices; the outputs are gathered in the caller's arrays (host memory) in stream order.
+// Each worker takes the guard on its own context; the calling thread takes none (in the emulator the workers queue on its lock).
 int d4g_optimise_streams_sharded(size_t n, const uint8_t* const* in, const size_t* in_len, int merge_blocks, uint8_t** out,
                                  size_t* out_len, int64_t* saved_bits, int32_t* status) {
-    enter_ctx(nullptr);
     const int nc = g_nCtx;
     if (nc <= 1) return d4g_optimise_streams(n, in, in_len, merge_blocks, out, out_len, saved_bits, status);
     if (n && (!in || !in_len || !out || !out_len || !status)) return fail(D4G_ERR_ARG, "null argument");
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return in_len[a] > in_len[b]; });
-    std::vector<std::vector<size_t>> shard(nc);
-    std::vector<unsigned long long> load(nc, 0);
-    for (size_t i : order) {
-        int r = 0;
-        for (int k = 1; k < nc; k++) if (load[k] < load[r]) r = k;
-        shard[r].push_back(i);
-        load[r] += in_len[i];
-    }
-    std::vector<int> rcs(nc, D4G_OK);
-    std::vector<std::string> errs(nc);
-    std::vector<std::thread> th;
-    for (int k = 0; k < nc; k++) {
-        std::sort(shard[k].begin(), shard[k].end());
-        th.emplace_back([&, k]() {
-            g_tlsCtx = k;   // this thread works on context k
-            const std::vector<size_t>& idx = shard[k];
-            const size_t m = idx.size();
-            std::vector<const uint8_t*> sin(m);
-            std::vector<size_t> slen(m), solen(m);
-            std::vector<uint8_t*> sout(m);
-            std::vector<int64_t> ssaved(m);
-            std::vector<int32_t> sst(m);
-            for (size_t j = 0; j < m; j++) { sin[j] = in[idx[j]]; slen[j] = in_len[idx[j]]; }
-            rcs[k] = d4g_optimise_streams(m, sin.data(), slen.data(), merge_blocks, sout.data(), solen.data(), ssaved.data(), sst.data());
-            if (rcs[k] != D4G_OK) errs[k] = g_err;
-            for (size_t j = 0; j < m; j++) {
-                out[idx[j]] = sout[j]; out_len[idx[j]] = solen[j]; status[idx[j]] = sst[j];
-                if (saved_bits) saved_bits[idx[j]] = ssaved[j];
-            }
-        });
-    }
-    for (auto& t : th) t.join();
-    int rc = D4G_OK;
-    for (int k = 0; k < nc; k++)
-        if (rcs[k] != D4G_OK) { rc = rcs[k]; g_err = errs[k]; }
-    if (rc != D4G_OK)   // all-or-nothing, like the single-device call
-        for (size_t i = 0; i < n; i++) {
-            free(out[i]);
-            out[i] = nullptr;
-            out_len[i] = 0;
-            status[i] = D4G_STREAM_UNCHANGED;
-            if (saved_bits) saved_bits[i] = 0;
+    Outputs o(n, out, out_len, status, saved_bits);
+    return o.commit(to_code([&] {
+        std::vector<size_t> order(n);
+        for (size_t i = 0; i < n; i++) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return in_len[a] > in_len[b]; });
+        std::vector<std::vector<size_t>> shard(nc);
+        std::vector<unsigned long long> load(nc, 0);
+        for (size_t i : order) {
+            int r = 0;
+            for (int k = 1; k < nc; k++) if (load[k] < load[r]) r = k;
+            shard[r].push_back(i);
+            load[r] += in_len[i];
         }
-    return rc;
+        std::vector<int> rcs(nc, D4G_OK);
+        std::vector<std::string> errs(nc);
+        Joiner workers;
+        for (int k = 0; k < nc; k++) {
+            std::sort(shard[k].begin(), shard[k].end());
+            workers.threads.emplace_back([&, k]() {
+                g_tlsCtx = k;   // this thread works on context k
+                rcs[k] = api(nullptr, [&] {
+                    optimise_into(shard[k].size(), shard[k].data(), in, in_len, merge_blocks != 0, out, out_len, saved_bits, status);
+                    return D4G_OK;
+                });
+                if (rcs[k] != D4G_OK) errs[k].swap(g_err);
+            });
+        }
+        workers.join();
+        int rc = D4G_OK;
+        for (int k = 0; k < nc; k++)
+            if (rcs[k] != D4G_OK) { rc = rcs[k]; g_err.swap(errs[k]); }
+        return rc;
+    }));
 }
 
 int d4g_size_bits_fallback(const uint8_t* in, size_t len, int64_t* bits) {
-    enter_ctx(nullptr);
     if (!in || !bits) return fail(D4G_ERR_ARG, "null argument");
-    const uint8_t* ins[1] = {in};
-    size_t lens[1] = {len};
-    d4g_batch* b = d4g_batch_create(1, ins, lens);
-    if (!b) return D4G_ERR_RUNTIME;
-    int rc;
-    {
-        D4G_API_LOCK();
-        try {
-            bind_device();
-            engine().init();
-            b->impl.parse_probe();
-            const Batch::PStream& o = b->impl.ps[0];
-            *bits = o.status == 0 ? o.sizeBits : (int64_t)len * 8;  // B/Deft.java:48-54
-            rc = D4G_OK;
-        } catch (const std::exception& ex) {
-            rc = fail(D4G_ERR_RUNTIME, ex.what());
-        }
-    }
-    d4g_batch_destroy(b);
-    return rc;
+    return api(nullptr, [&] {
+        std::unique_ptr<d4g_batch> b = parse_one(in, len, false);
+        const Batch::PStream& o = b->impl.ps[0];
+        *bits = o.status == 0 ? o.sizeBits : (int64_t)len * 8;  // B/Deft.java:48-54
+        return D4G_OK;
+    });
 }
 
 int d4g_inflate(const uint8_t* in, size_t len, uint8_t** out, size_t* out_len, size_t* consumed, int32_t* status) {
-    enter_ctx(nullptr);
     if (!in || !out || !out_len || !status) return fail(D4G_ERR_ARG, "null argument");
-    const uint8_t* ins[1] = {in};
-    size_t lens[1] = {len};
-    *out = nullptr;
-    *out_len = 0;
-    d4g_batch* b = d4g_batch_create(1, ins, lens);
-    if (!b) return D4G_ERR_RUNTIME;
-    int rc;
-    {
-        D4G_API_LOCK();
-        try {
-            bind_device();
-            engine().init();
-            b->impl.parse_probe();
-            b->impl.build_blocks(false, false);
-            const Batch::PStream& o = b->impl.ps[0];
-            if (consumed) *consumed = (size_t)o.consumed;
-            if (o.status != 0) {
-                *status = D4G_STREAM_PARSE_ERROR;
-            } else {
-                *status = D4G_STREAM_UNCHANGED;
-                *out = (uint8_t*)malloc(o.nU ? (size_t)o.nU : 1);
-                *out_len = (size_t)o.nU;
-                rt_d2h(*out, b->impl.dU + b->impl.streams[0].uBase, (size_t)o.nU);
-            }
-            rc = D4G_OK;
-        } catch (const std::exception& ex) {
-            rc = fail(D4G_ERR_RUNTIME, ex.what());
+    Outputs o(1, out, out_len);
+    return o.commit(api(nullptr, [&] {
+        std::unique_ptr<d4g_batch> b = parse_one(in, len, true);
+        const Batch::PStream& p = b->impl.ps[0];
+        if (consumed) *consumed = (size_t)p.consumed;
+        *status = p.status != 0 ? D4G_STREAM_PARSE_ERROR : D4G_STREAM_UNCHANGED;
+        if (p.status == 0) {
+            *out = host_copy(b->impl.dU + b->impl.streams[0].uBase, (size_t)p.nU);
+            *out_len = (size_t)p.nU;
         }
-    }
-    d4g_batch_destroy(b);
-    return rc;
+        return D4G_OK;
+    }));
 }
 
 // ---- Zopfli encoder ----
@@ -586,14 +564,10 @@ struct ZfUpload {
 
 int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_len, int iterations, int splitting, int max_blocks,
                        size_t master_block, uint8_t** out, size_t* out_len) {
-    enter_ctx(nullptr);
     if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) { out[i] = nullptr; out_len[i] = 0; }
+    Outputs o(n, out, out_len);
     if (iterations < 1 || splitting < 0 || splitting > 2 || max_blocks < 0 || master_block > ((size_t)8 << 20)) return fail(D4G_ERR_ARG, "bad zopfli options");
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    try {
-        bind_device();
+    return o.commit(api(nullptr, [&] {
         ZfUpload up(n, raw, raw_len);
         ZfFront zf;
         zf.create(n, up.ptr.data(), up.len.data());
@@ -607,26 +581,16 @@ int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_le
             fprintf(stderr, "[zopfli] inputs %zu: table %.1f ms, split %.1f ms, squeeze %.1f ms (%lld blocks, %lld position-iterations), final+emit %.1f ms\n", n,
                     zf.msTable, zf.msSplit, zf.msSqueeze, (long long)zf.squeezeBlocks, (long long)zf.squeezePositions, zf.msEmit);
         for (size_t i = 0; i < n; i++) {
-            const size_t nb = (size_t)((zf.outBits[i] + 7) / 8);
-            out[i] = (uint8_t*)malloc(nb ? nb : 1);
-            if (!out[i]) throw std::runtime_error("out of host memory");
-            rt_d2h(out[i], zf.outWords[i], nb);
-            out_len[i] = nb;
+            out_len[i] = (size_t)((zf.outBits[i] + 7) / 8);
+            out[i] = host_copy(zf.outWords[i], out_len[i]);
         }
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        for (size_t i = 0; i < n; i++) { free(out[i]); out[i] = nullptr; out_len[i] = 0; }
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    }));
 }
 
 int d4g_debug_zopfli_table(const uint8_t* raw, size_t n, size_t end, uint16_t* len16, uint16_t* dist16, uint16_t* sublen) {
-    enter_ctx(nullptr);
     if (!raw || !len16 || !dist16) return fail(D4G_ERR_ARG, "null argument");
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    try {
-        bind_device();
+    return api(nullptr, [&] {
         const uint8_t* rp[1] = {raw};
         size_t rl[1] = {n};
         ZfUpload up(1, rp, rl);
@@ -657,9 +621,7 @@ int d4g_debug_zopfli_table(const uint8_t* raw, size_t n, size_t end, uint16_t* l
             }
         }
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 __global__ void __launch_bounds__(64) k_zf_debug_code_lengths(const uint32_t* freq, int n, int maxbits, uint32_t* out) {
@@ -678,12 +640,8 @@ __global__ void __launch_bounds__(64) k_zf_debug_code_lengths(const uint32_t* fr
 }
 
 int d4g_debug_zopfli_code_lengths(const uint32_t* freq, int n, int maxbits, uint32_t* lengths) {
-    enter_ctx(nullptr);
     if (!freq || !lengths || n < 1 || n > ZF_NUM_LL || maxbits < 1 || maxbits > 15) return fail(D4G_ERR_ARG, "bad argument");
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    try {
-        bind_device();
+    return api(nullptr, [&] {
         LzScratch own;
         uint32_t* dF = own.own((uint32_t*)rt_malloc(n * 4));
         uint32_t* dO = own.own((uint32_t*)rt_malloc(n * 4));
@@ -691,9 +649,7 @@ int d4g_debug_zopfli_code_lengths(const uint32_t* freq, int n, int maxbits, uint
         RT_LAUNCH(k_zf_debug_code_lengths, 1, 64, dF, n, maxbits, dO);
         rt_d2h(lengths, dO, n * 4);
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 __global__ void __launch_bounds__(64) k_debug_cl_tree(const uint32_t* freq, int n, uint32_t* out, int32_t* limited) {
@@ -714,12 +670,8 @@ __global__ void __launch_bounds__(64) k_debug_cl_tree(const uint32_t* freq, int 
 }
 
 int d4g_debug_cl_tree_lengths(const uint32_t* freq, int n, uint32_t* lengths, int32_t* limited) {
-    enter_ctx(nullptr);
     if (!freq || !lengths || !limited || n < 1) return fail(D4G_ERR_ARG, "bad argument");
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    try {
-        bind_device();
+    return api(nullptr, [&] {
         LzScratch own;
         uint32_t* dF = own.own((uint32_t*)rt_malloc((size_t)n * 19 * 4));
         uint32_t* dO = own.own((uint32_t*)rt_malloc((size_t)n * 19 * 4));
@@ -729,9 +681,7 @@ int d4g_debug_cl_tree_lengths(const uint32_t* freq, int n, uint32_t* lengths, in
         rt_d2h(lengths, dO, (size_t)n * 19 * 4);
         rt_d2h(limited, dL, (size_t)n * 4);
         return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    });
 }
 
 void d4g_free(void* p) { free(p); }
@@ -800,15 +750,6 @@ void add_stats(d4g_stats& a, const d4g_stats& o) {
     a.ms_search_kernels += o.ms_search_kernels; a.ms_parse_kernels += o.ms_parse_kernels;
     a.search_bytes_algorithmic += o.search_bytes_algorithmic;
 }
-std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, bool fromDevice, const std::vector<LzSpec>& specs,
-                                        bool merge) {
-    std::unique_ptr<d4g_batch> e(new d4g_batch());
-    e->ctx = rt_ctx();
-    e->lz.reset(new LzFront(e->impl));
-    e->lz->create(n, raw, len, specs.size(), specs.data(), fromDevice);
-    e->lz->run(true, merge);
-    return e;
-}
 // one group of inputs [i0, i1)
 void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* raw, const size_t* len, bool fromDevice,
                     const std::vector<LzSpec>& list, bool merge, const std::function<void()>& afterStart) {
@@ -823,10 +764,7 @@ void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* 
     std::vector<LzSpec> specs;
     for (size_t i = 0; i < n; i++)
         for (int k : lzIdx) { LzSpec s = list[k]; s.input = (int32_t)i; specs.push_back(s); }
-    std::unique_ptr<d4g_batch> e1(new d4g_batch());
-    e1->ctx = rt_ctx();
-    e1->lz.reset(new LzFront(e1->impl));
-    e1->lz->create(n, raw + i0, len + i0, specs.size(), specs.data(), fromDevice);
+    std::unique_ptr<d4g_batch> e1 = encode_batch(n, raw + i0, len + i0, specs.size(), specs.data(), fromDevice);
     // stage 3 starts here, on its own host thread (its own HIP streams): the Zopfli compressors' outputs, encoded on the device
     // and parsed + optimised like any other stream.  A squeeze keeps a handful of waves busy for a long time; the zlib-family
     // stages below fill the rest of the device meanwhile.  It only reads the inputs (e1's dU, stable from create on).
@@ -868,10 +806,9 @@ void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* 
             Z.err = std::current_exception();
         }
     };
-    std::thread zthread;
-    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{zthread};   // also when a stage below throws
+    Joiner zthread;   // also when a stage below throws
 #ifndef D4G_HOSTSIM
-    if (!zIdx.empty()) zthread = std::thread(zopfli_stage);
+    if (!zIdx.empty()) zthread.threads.emplace_back(zopfli_stage);
 #endif
     const bool dbg = env_int("D4G_DEBUG_ZOPFLI", 0) > 0;
     const double tg0 = now_ms();
@@ -928,7 +865,8 @@ void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* 
                 rl[q] = (size_t)e1->lz->rawLen[need[q]];
                 for (int k : hIdx) { LzSpec s = list[k]; s.input = (int32_t)q; sp2.push_back(s); }
             }
-            e2 = encode_batch(need.size(), rp.data(), rl.data(), true, sp2, merge);
+            e2 = encode_batch(need.size(), rp.data(), rl.data(), sp2.size(), sp2.data(), true);
+            e2->lz->run(true, merge);
             add_stats(R.agg, e2->impl.stats);
             R.outputsOptimised += (int64_t)sp2.size();
             for (size_t q = 0; q < need.size(); q++)
@@ -1008,50 +946,12 @@ void compress_run(CompressRun& R, size_t n, const uint8_t* const* raw, const siz
     }
     once();
 }
-uint8_t* copy_stream_out(Batch& b, size_t i, size_t* len) {
-    const HStream& s = b.streams[i];
-    size_t nb = (size_t)((s.outBits + 7) / 8);
-    uint8_t* p = (uint8_t*)malloc(nb ? nb : 1);
-    if (!p) throw std::runtime_error("out of host memory");
-    rt_d2h(p, (const uint8_t*)(b.dOut + s.outWordBase), nb);
-    *len = nb;
-    return p;
-}
-}  // namespace
-
-extern "C" {
-
-int d4g_compress(size_t n, const uint8_t* const* raw, const size_t* raw_len, int mode, int iter, int merge_blocks, uint8_t** out,
-                 size_t* out_len, int32_t* winner) {
-    enter_ctx(nullptr);
-    if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) { out[i] = nullptr; out_len[i] = 0; if (winner) winner[i] = -1; }
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    try {
-        bind_device();
-        std::vector<LzSpec> probe;
-        std::string why;
-        if (!mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
-        CompressRun R;
-        compress_run(R, n, raw, raw_len, false, mode, iter, merge_blocks != 0);
-        for (size_t i = 0; i < n; i++) {
-            out[i] = (uint8_t*)malloc(R.len[i] ? R.len[i] : 1);
-            if (!out[i]) throw std::runtime_error("out of host memory");
-            rt_d2h(out[i], R.dWin + R.off[i], R.len[i]);
-            out_len[i] = R.len[i];
-            if (winner) winner[i] = (int32_t)R.winner[i];
-        }
-        return D4G_OK;
-    } catch (const std::exception& ex) {
-        for (size_t i = 0; i < n; i++) { free(out[i]); out[i] = nullptr; out_len[i] = 0; }
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
-}
-
-// CMDUtil.optimise's per-stream loop on a batch made by d4g_batch_create (locked by the caller)
-static void run_recompress_locked(d4g_batch* b, int mode, int iter, bool merge) {
-    Batch& A = b->impl;
+// CMDUtil.optimise's per-stream loop on a batch made by d4g_batch_create
+int recompress_batch(d4g_batch& b, int mode, int iter, bool merge) {
+    std::vector<LzSpec> probe;
+    std::string why;
+    if (mode != D4G_MODE_NONE && !mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
+    Batch& A = b.impl;
     const size_t n = A.streams.size();
     double t0 = now_ms();
     // container.optimise(mergeBlocks) — CMDUtil.java:70.  In a Zopfli mode only the parse happens here: the search of the originals
@@ -1059,13 +959,13 @@ static void run_recompress_locked(d4g_batch* b, int mode, int iter, bool merge) 
     const bool deferSearch = mode >= D4G_MODE_ZOPFLI;
     A.run_parse(merge);
     if (!deferSearch) A.run_rest(merge);
-    b->graft.assign(n, 0);
-    b->recompSaved.assign(n, 0);
-    b->reoptIndex.assign(n, -1);
+    b.graft.assign(n, 0);
+    b.recompSaved.assign(n, 0);
+    b.reoptIndex.assign(n, -1);
     std::vector<size_t> ok;
     for (size_t i = 0; i < n; i++)
         if (A.streams[i].status == 0) ok.push_back(i);
-    if (mode == D4G_MODE_NONE || ok.empty()) { if (deferSearch) A.run_rest(merge); return; }
+    if (mode == D4G_MODE_NONE || ok.empty()) { if (deferSearch) A.run_rest(merge); return D4G_OK; }
     const double tc0 = now_ms();
     // stream.getUncompressedData() -> compUtil.compress(uncompressed, true) — :83-84; the decoded bytes stay in HBM
     std::vector<const uint8_t*> rp(ok.size());
@@ -1078,20 +978,20 @@ static void run_recompress_locked(d4g_batch* b, int mode, int iter, bool merge) 
     std::vector<const uint8_t*> wp(ok.size());
     std::vector<size_t> wl(ok.size());
     for (size_t k = 0; k < ok.size(); k++) { wp[k] = R.dWin + R.off[k]; wl[k] = R.len[k]; }
-    b->reopt.reset(new Batch());
-    b->reopt->create(ok.size(), wp.data(), wl.data(), true);
-    b->reopt->run(merge);
+    b.reopt.reset(new Batch());
+    b.reopt->create(ok.size(), wp.data(), wl.data(), true);
+    b.reopt->run(merge);
     for (size_t k = 0; k < ok.size(); k++) {
         const HStream& a = A.streams[ok[k]];
-        const HStream& c2 = b->reopt->streams[k];
-        b->reoptIndex[ok[k]] = (int)k;
+        const HStream& c2 = b.reopt->streams[k];
+        b.reoptIndex[ok[k]] = (int)k;
         if (c2.status != 0) continue;                  // recompStream.parse failed: the original stays (:88)
         // recompStream.getSizeBits() / stream.getSizeBits() of the optimised streams (DeflateStream.java:171-182): the
         // written sizes, in which a stored block's padding follows its new position (sizeBitsIn - saved does not)
         long long recompSize = c2.outBits, originalSize = a.outBits;
         if (recompSize < originalSize) {               // :94-98
-            b->graft[ok[k]] = 1;
-            b->recompSaved[ok[k]] = originalSize - recompSize;
+            b.graft[ok[k]] = 1;
+            b.recompSaved[ok[k]] = originalSize - recompSize;
         }
     }
     const d4g_stats& es = R.agg;
@@ -1105,35 +1005,47 @@ static void run_recompress_locked(d4g_batch* b, int mode, int iter, bool merge) 
     A.stats.recompress_outputs_pruned = R.outputsPruned;
     A.stats.ms_zopfli_table = R.msZfTable; A.stats.ms_zopfli_split = R.msZfSplit; A.stats.ms_zopfli_squeeze = R.msZfSqueeze; A.stats.ms_zopfli_emit = R.msZfEmit;
     A.stats.zopfli_blocks = R.zfBlocks; A.stats.zopfli_position_iterations = R.zfPosIter;
-    const d4g_stats* chained[2] = {&es, &b->reopt->stats};
+    const d4g_stats* chained[2] = {&es, &b.reopt->stats};
     for (const d4g_stats* o : chained) {   // the same kernels ran in the chained batches: one set of counters
         A.stats.ms_state_kernels += o->ms_state_kernels; A.stats.state_launches += o->state_launches;
         A.stats.state_tokens_per_round += o->state_tokens_per_round; A.stats.state_bytes_per_round += o->state_bytes_per_round;
         A.stats.kernel_launches += o->kernel_launches; A.stats.rounds += o->rounds;
         A.stats.ms_search_kernels += o->ms_search_kernels; A.stats.ms_parse_kernels += o->ms_parse_kernels;
     }
-    A.stats.search_bytes_algorithmic += es.search_bytes_algorithmic + b->reopt->stats.search_bytes_algorithmic;
+    A.stats.search_bytes_algorithmic += es.search_bytes_algorithmic + b.reopt->stats.search_bytes_algorithmic;
+    return D4G_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int d4g_compress(size_t n, const uint8_t* const* raw, const size_t* raw_len, int mode, int iter, int merge_blocks, uint8_t** out,
+                 size_t* out_len, int32_t* winner) {
+    if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
+    Outputs o(n, out, out_len, nullptr, nullptr, nullptr, winner);
+    return o.commit(api(nullptr, [&] {
+        std::vector<LzSpec> probe;
+        std::string why;
+        if (!mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
+        CompressRun R;
+        compress_run(R, n, raw, raw_len, false, mode, iter, merge_blocks != 0);
+        for (size_t i = 0; i < n; i++) {
+            out[i] = host_copy(R.dWin + R.off[i], R.len[i]);
+            out_len[i] = R.len[i];
+            if (winner) winner[i] = (int32_t)R.winner[i];
+        }
+        return D4G_OK;
+    }));
 }
 
 int d4g_batch_run_recompress(d4g_batch* b, int mode, int iter, int merge_blocks) {
-    enter_ctx(b);
-    D4G_API_LOCK();
-    if (!ready()) return fail(D4G_ERR_NODEVICE, "d4g_init has not succeeded");
-    if (!b || b->lz) return fail(D4G_ERR_ARG, "not a batch of deflate streams");
-    try {
-        bind_device();
-        std::vector<LzSpec> probe;
-        std::string why;
-        if (mode != D4G_MODE_NONE && !mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
-        run_recompress_locked(b, mode, iter, merge_blocks != 0);
-        return D4G_OK;
-    } catch (const std::exception& ex) {
-        return fail(D4G_ERR_RUNTIME, ex.what());
-    }
+    return api(b, [&] {
+        if (!b || b->lz) return fail(D4G_ERR_ARG, "not a batch of deflate streams");
+        return recompress_batch(*b, mode, iter, merge_blocks != 0);
+    });
 }
 
 int d4g_batch_recompress_result(d4g_batch* b, size_t i, int32_t* grafted, int64_t* recompress_saved) {
-    enter_ctx(b);
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     if (grafted) *grafted = i < b->graft.size() ? b->graft[i] : 0;
     if (recompress_saved) *recompress_saved = i < b->recompSaved.size() ? b->recompSaved[i] : 0;
@@ -1142,48 +1054,15 @@ int d4g_batch_recompress_result(d4g_batch* b, size_t i, int32_t* grafted, int64_
 
 int d4g_recompress_streams(size_t n, const uint8_t* const* in, const size_t* in_len, int mode, int iter, int merge_blocks,
                            uint8_t** out, size_t* out_len, int64_t* saved_bits, int64_t* recompress_saved, int32_t* status) {
-    enter_ctx(nullptr);
     if (n && (!in || !in_len || !out || !out_len || !status)) return fail(D4G_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) {
-        out[i] = nullptr; out_len[i] = 0; status[i] = D4G_STREAM_UNCHANGED;
-        if (saved_bits) saved_bits[i] = 0;
-        if (recompress_saved) recompress_saved[i] = 0;
-    }
-    d4g_batch* b = d4g_batch_create(n, in, in_len);
-    if (!b) return D4G_ERR_RUNTIME;
-    int rc = d4g_batch_run_recompress(b, mode, iter, merge_blocks);
-    for (size_t i = 0; i < n && rc == D4G_OK; i++) {
-        int64_t sv = 0, rs = 0;
-        size_t ol = 0;
-        int32_t st = D4G_STREAM_UNCHANGED;
-        d4g_batch_stream_result(b, i, &st, &sv, &ol, nullptr, nullptr);
-        d4g_batch_recompress_result(b, i, nullptr, &rs);
-        if (st == D4G_STREAM_CHANGED) {
-            out[i] = (uint8_t*)malloc(ol ? ol : 1);
-            if (!out[i]) { rc = fail(D4G_ERR_RUNTIME, "out of host memory"); break; }
-            rc = d4g_batch_copy_output(b, i, out[i], ol);
-            if (rc != D4G_OK) break;
-            out_len[i] = ol;
-        }
-        status[i] = st;
-        if (saved_bits) saved_bits[i] = sv;
-        if (recompress_saved) recompress_saved[i] = rs;
-    }
-    if (rc != D4G_OK)
-        for (size_t i = 0; i < n; i++) {
-            free(out[i]); out[i] = nullptr; out_len[i] = 0; status[i] = D4G_STREAM_UNCHANGED;
-            if (saved_bits) saved_bits[i] = 0;
-            if (recompress_saved) recompress_saved[i] = 0;
-        }
-    std::string keep = g_err;
-    d4g_batch_destroy(b);
-    g_err = keep;
-    return rc;
+    Outputs o(n, out, out_len, status, saved_bits, recompress_saved);
+    return o.commit(api(nullptr, [&] {
+        std::unique_ptr<d4g_batch> b = make_batch(n, in, in_len);
+        if (int rc = recompress_batch(*b, mode, iter, merge_blocks != 0)) return rc;
+        results_into(*b, nullptr, out, out_len, saved_bits, status, recompress_saved);
+        return D4G_OK;
+    }));
 }
-
-}  // extern "C"
-
-extern "C" {
 
 #ifdef D4G_HOSTSIM
 // emulator builds only: the closed-form pack summary against the reference-shaped loop, every flag set and run length
@@ -1203,34 +1082,34 @@ long long d4g_test_pack_kinds(void) {
 
 // dev tool: the fused executor's accounting (collected while D4G_FUSED_STATS is set; see k_search_fused); read and cleared
 int d4g_debug_fused_stats(long long* out64) {
-    enter_ctx(nullptr);
-    D4G_API_LOCK();
-    d4g::engine().init();
-    rt_sync_all();
-    rt_d2h(out64, d4g::engine().dOpStats, 64 * 8);
-    rt_memset(d4g::engine().dOpStats, 0, 64 * 8);
-    rt_sync();
-    return 0;
+    return api(nullptr, [&] {
+        engine().init();
+        rt_sync_all();
+        rt_d2h(out64, engine().dOpStats, 64 * 8);
+        rt_memset(engine().dOpStats, 0, 64 * 8);
+        rt_sync();
+        return D4G_OK;
+    });
 }
 
 #ifdef D4G_PROFILE_OPS
 // profiling builds only (scripts/build_profile_lib.sh): cycles and counts per op kind
 int d4g_debug_set_experiment(long long mode) {
-    enter_ctx(nullptr);
-    D4G_API_LOCK();
-    rt_h2d(engine().dOpStats + 63, &mode, 8);
-    rt_sync();
-    return 0;
+    return api(nullptr, [&] {
+        rt_h2d(engine().dOpStats + 63, &mode, 8);
+        rt_sync();
+        return D4G_OK;
+    });
 }
 int d4g_debug_opstats(long long* out64) {
-    enter_ctx(nullptr);
-    D4G_API_LOCK();
-    rt_d2h(out64, engine().dOpStats, 64 * 8);
-    (void)hipMemcpyFromSymbol(out64 + 56, HIP_SYMBOL(d4g_dbg_counters), 7 * 8);
-    (void)hipMemcpyFromSymbol(out64 + 28, HIP_SYMBOL(d4g_dbg_hdr), 4 * 8);
-    (void)hipMemcpyFromSymbol(out64 + 16, HIP_SYMBOL(d4g_dbg_tree), 3 * 8);
-    (void)hipMemcpyFromSymbol(out64 + 34, HIP_SYMBOL(d4g_dbg_pass), 4 * 8);
-    return 0;
+    return api(nullptr, [&] {
+        rt_d2h(out64, engine().dOpStats, 64 * 8);
+        (void)hipMemcpyFromSymbol(out64 + 56, HIP_SYMBOL(d4g_dbg_counters), 7 * 8);
+        (void)hipMemcpyFromSymbol(out64 + 28, HIP_SYMBOL(d4g_dbg_hdr), 4 * 8);
+        (void)hipMemcpyFromSymbol(out64 + 16, HIP_SYMBOL(d4g_dbg_tree), 3 * 8);
+        (void)hipMemcpyFromSymbol(out64 + 34, HIP_SYMBOL(d4g_dbg_pass), 4 * 8);
+        return D4G_OK;
+    });
 }
 #endif
 

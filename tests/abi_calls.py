@@ -69,3 +69,49 @@ def check_one_shot_entry_points(L, O, streams, merge):
         else:
             assert st3 < 0 and dec is None
     return kinds
+
+
+class Slots:
+    """Poisoned result arrays of a one-shot call with n streams: the call must define every slot it is given."""
+
+    def __init__(self, n):
+        self.n = n
+        self.out = (ctypes.c_void_p * n)(*([0xdead] * n))
+        self.len = (ctypes.c_size_t * n)(*([12345] * n))
+        self.status = (ctypes.c_int32 * n)(*([99] * n))
+        self.saved = (ctypes.c_int64 * n)(*([-7] * n))
+        self.rsaved = (ctypes.c_int64 * n)(*([-7] * n))
+        self.winner = (ctypes.c_int32 * n)(*([99] * n))
+
+    def unchanged(self, status=False, saved=False, rsaved=False, winner=False):
+        """every slot of the named arrays holds the "unchanged" value of deft4g.h: out NULL, out_len 0, status
+        D4G_STREAM_UNCHANGED, saved_bits / recompress_saved 0, winner -1"""
+        return all(self.out[i] is None and self.len[i] == 0 and (not status or self.status[i] == 1) and
+                   (not saved or self.saved[i] == 0) and (not rsaved or self.rsaved[i] == 0) and (not winner or self.winner[i] == -1)
+                   for i in range(self.n))
+
+
+def one_shot_calls(L, streams, mode=1, level=6, iterations=3, master_block=8 << 20):
+    """Every one-shot entry point on `streams` with poisoned result arrays: name -> (call, Slots, which arrays to check)."""
+    n = len(streams)
+    keep = [bytes(s) for s in streams]
+    arr = (ctypes.c_char_p * n)(*keep)
+    lens = (ctypes.c_size_t * n)(*[len(s) for s in keep])
+    s = {k: Slots(n) for k in ("optimise", "sharded", "deflate", "level", "zopfli", "compress", "recompress")}
+    return {
+        "d4g_optimise_streams": (lambda: L.d4g_optimise_streams(n, arr, lens, 1, s["optimise"].out, s["optimise"].len, s["optimise"].saved,
+                                                                s["optimise"].status), s["optimise"], dict(status=True, saved=True)),
+        "d4g_optimise_streams_sharded": (lambda: L.d4g_optimise_streams_sharded(n, arr, lens, 1, s["sharded"].out, s["sharded"].len,
+                                                                                s["sharded"].saved, s["sharded"].status),
+                                         s["sharded"], dict(status=True, saved=True)),
+        "d4g_deflate_streams": (lambda: L.d4g_deflate_streams(n, arr, lens, 0, 0, s["deflate"].out, s["deflate"].len), s["deflate"], {}),
+        "d4g_deflate_streams_level": (lambda: L.d4g_deflate_streams_level(n, arr, lens, 0, level, 0, s["level"].out, s["level"].len),
+                                      s["level"], {}),
+        "d4g_zopfli_streams": (lambda: L.d4g_zopfli_streams(n, arr, lens, iterations, 0, 15, master_block, s["zopfli"].out, s["zopfli"].len),
+                               s["zopfli"], {}),
+        "d4g_compress": (lambda: L.d4g_compress(n, arr, lens, mode, 1, 1, s["compress"].out, s["compress"].len, s["compress"].winner),
+                         s["compress"], dict(winner=True)),
+        "d4g_recompress_streams": (lambda: L.d4g_recompress_streams(n, arr, lens, mode, 1, 1, s["recompress"].out, s["recompress"].len,
+                                                                    s["recompress"].saved, s["recompress"].rsaved, s["recompress"].status),
+                                   s["recompress"], dict(status=True, saved=True, rsaved=True)),
+    }

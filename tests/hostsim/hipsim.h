@@ -137,7 +137,7 @@ struct RtGlobals {
     bool ready = false;
 };
 #define RT_MAX_CTX 16
-inline int& rt_ctx() { static int c = 0; return c; }   // (the emulator has one device: every context is the same)
+inline int& rt_ctx() { thread_local int c = 0; return c; }   // per thread, as in d4g_rt.h (the emulator has one device: every context is the same)
 inline RtGlobals& rt() {
     static RtGlobals g;
     return g;

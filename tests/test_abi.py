@@ -68,3 +68,52 @@ def test_jni_shim_and_java_binding_match_the_header():
     assert len(natives) >= 6
     for m in natives:
         assert "JFN(%s)" % m in shim, m
+
+
+def test_device_entry_points_refuse_before_init(lib):
+    """d4g_init never succeeds without a GPU.  Every entry point that needs the device and takes no batch (and those that
+    take one, given NULL: the library check comes first) returns D4G_ERR_NODEVICE with its message, the batch creators a
+    NULL batch; the one-shot calls leave their result arrays "unchanged" (deft4g.h)."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    import abi_calls
+    from deft4j_amd import d4g_encoder_spec, d4g_encoder_spec_level
+    lib.d4g_debug_fused_stats.restype = ctypes.c_int
+    lib.d4g_debug_fused_stats.argtypes = [ctypes.c_void_p]
+    data = [b"\x03\x00", b"abc"]
+    n = len(data)
+    arr = (ctypes.c_char_p * n)(*data)
+    lens = (ctypes.c_size_t * n)(*map(len, data))
+    spec = (d4g_encoder_spec * 1)(d4g_encoder_spec(0, 0, 0))
+    spec_level = (d4g_encoder_spec_level * 1)(d4g_encoder_spec_level(0, 0, 0, 6))
+    nodevice = b"d4g_init has not succeeded"
+
+    def refused(call, want=nodevice):
+        assert lib.d4g_batch_stats(None, None) == -2          # some other message first
+        rc = call()
+        assert lib.d4g_last_error() == want
+        return rc
+
+    assert refused(lambda: lib.d4g_batch_create(n, arr, lens)) is None
+    assert refused(lambda: lib.d4g_batch_create_encode(n, arr, lens, 1, spec)) is None
+    assert refused(lambda: lib.d4g_batch_create_encode_level(n, arr, lens, 1, spec_level)) is None
+    assert refused(lambda: lib.d4g_batch_create_on(0, n, arr, lens), b"no such context (d4g_init_devices)") is None
+    for name, (call, slots, check) in abi_calls.one_shot_calls(lib, data).items():
+        assert refused(call) == -1, name
+        assert slots.unchanged(**check), name
+    out, olen, consumed, status, bits = ctypes.c_void_p(0xdead), ctypes.c_size_t(777), ctypes.c_size_t(0), ctypes.c_int32(99), ctypes.c_int64(0)
+    assert refused(lambda: lib.d4g_inflate(data[0], 2, ctypes.byref(out), ctypes.byref(olen), ctypes.byref(consumed), ctypes.byref(status))) == -1
+    assert out.value is None and olen.value == 0
+    assert refused(lambda: lib.d4g_size_bits_fallback(data[0], 2, ctypes.byref(bits))) == -1
+    u16 = (ctypes.c_uint16 * 8)()
+    u32 = (ctypes.c_uint32 * 19)(*range(19))
+    i32 = (ctypes.c_int32 * 1)()
+    assert refused(lambda: lib.d4g_debug_zopfli_table(b"abc", 3, 0, u16, u16, None)) == -1
+    assert refused(lambda: lib.d4g_debug_zopfli_code_lengths(u32, 4, 15, u32)) == -1
+    assert refused(lambda: lib.d4g_debug_cl_tree_lengths(u32, 1, u32, i32)) == -1
+    assert refused(lambda: lib.d4g_debug_fused_stats((ctypes.c_int64 * 64)())) == -1
+    assert refused(lambda: lib.d4g_batch_run(None, 1)) == -1
+    assert refused(lambda: lib.d4g_batch_run_encode(None, 0, 0)) == -1
+    assert refused(lambda: lib.d4g_batch_parse(None)) == -1
+    assert refused(lambda: lib.d4g_batch_run_recompress(None, 1, 20, 1)) == -1

@@ -368,6 +368,109 @@ def test_contexts_and_the_sharded_one_shot_in_the_emulator(sim):
         D.Batch(streams[:1], lib=L, context=7)
 
 
+def test_sharded_one_shot_from_two_threads_in_the_emulator(sim):
+    """Two host threads call the two-context sharded one-shot at once (four workers, each on its own context, all queued on
+    the emulator's lock): every result is the single-context oracle's."""
+    import threading
+    D, L = sim
+    D.init_devices([0, 0], lib=L)
+    jobs = [[synth.make_stream(n, 40 + 10 * t + k) for k, n in enumerate((700 + 400 * t, 1600, 300))] + [b"\x07", synth.deflate9(b"")]
+            for t in range(2)]
+    want = [[O.optimise(a, True) for a in streams] for streams in jobs]
+    got, errs = {}, []
+
+    def work(t):
+        try:
+            got[t] = D.optimise_streams_sharded(jobs[t], True, lib=L)
+        except Exception as e:  # noqa: BLE001
+            errs.append(e)
+    ts = [threading.Thread(target=work, args=(t,)) for t in range(2)]
+    [t.start() for t in ts]
+    [t.join() for t in ts]
+    assert not errs, errs
+    for t in range(2):
+        outs, saved, status = got[t]
+        assert any(w[0] == 0 for w in want[t])
+        for i, w in enumerate(want[t]):
+            assert status[i] == w[0] and outs[i] == (w[1] if w[0] == 0 else None) and saved[i] == (w[2] if w[0] == 0 else 0), (t, i)
+
+
+def test_single_faults_keep_their_codes_and_messages(sim):
+    """One fault per call through the raw C ABI: each refusal keeps its code (D4G_ERR_ARG -2, D4G_ERR_RUNTIME -3) and its
+    message, a batch creator returns NULL, and a one-shot call leaves its result arrays "unchanged"."""
+    import ctypes
+    import abi_calls
+    from deft4j_amd import d4g_encoder_spec, d4g_encoder_spec_level
+    D, L = sim
+    ARG, RUNTIME = -2, -3
+
+    def refused(rc, code, msg):
+        assert rc == code and L.d4g_last_error() == msg, (rc, L.d4g_last_error())
+
+    def no_batch(b, msg):
+        assert b is None and L.d4g_last_error() == msg, L.d4g_last_error()
+
+    # null arguments
+    for name in ("d4g_optimise_streams", "d4g_optimise_streams_sharded"):
+        refused(getattr(L, name)(1, None, None, 1, None, None, None, None), ARG, b"null argument")
+    refused(L.d4g_deflate_streams(1, None, None, 0, 0, None, None), ARG, b"null argument")
+    refused(L.d4g_deflate_streams_level(1, None, None, 0, 6, 0, None, None), ARG, b"null argument")
+    refused(L.d4g_zopfli_streams(1, None, None, 3, 0, 15, 8 << 20, None, None), ARG, b"null argument")
+    refused(L.d4g_compress(1, None, None, 1, 1, 1, None, None, None), ARG, b"null argument")
+    refused(L.d4g_recompress_streams(1, None, None, 1, 1, 1, None, None, None, None, None), ARG, b"null argument")
+    refused(L.d4g_inflate(None, 0, None, None, None, None), ARG, b"null argument")
+    refused(L.d4g_size_bits_fallback(None, 0, None), ARG, b"null argument")
+    no_batch(L.d4g_batch_create_encode(1, None, None, 0, None), b"null argument")
+    no_batch(L.d4g_batch_create_encode_level(1, None, None, 0, None), b"null argument")
+    refused(L.d4g_debug_zopfli_table(None, 0, 0, None, None, None), ARG, b"null argument")
+    refused(L.d4g_debug_zopfli_code_lengths(None, 0, 0, None), ARG, b"bad argument")
+    refused(L.d4g_debug_cl_tree_lengths(None, 0, None, None), ARG, b"bad argument")
+    refused(L.d4g_batch_run(None, 1), ARG, b"null batch")
+    refused(L.d4g_batch_parse(None), ARG, b"null batch")
+    refused(L.d4g_batch_run_encode(None, 0, 0), ARG, b"not an encoder batch")
+    refused(L.d4g_batch_run_recompress(None, 1, 1, 1), ARG, b"not a batch of deflate streams")
+    refused(L.d4g_batch_stats(None, None), ARG, b"null argument")
+    refused(L.d4g_init_devices(0, None), ARG, b"1 to 16 contexts")
+    refused(L.d4g_set_device(7), ARG, b"no such context (d4g_init_devices)")
+    no_batch(L.d4g_batch_create_on(7, 0, None, None), b"no such context (d4g_init_devices)")
+    # a bad stream index, a stream that did not parse, an output buffer too small, a batch that already ran
+    b = D.Batch([rd("lz-twice-twice.s00.in.deflate"), b"\x07"], lib=L).run(True)
+    h, buf, one = b.h, ctypes.create_string_buffer(1 << 16), ctypes.create_string_buffer(1)
+    u32, i64 = ctypes.c_uint32(), ctypes.c_int64()
+    refused(L.d4g_batch_stream_result(h, 2, None, None, None, None, None), ARG, b"bad stream index")
+    refused(L.d4g_batch_recompress_result(h, 2, None, None), ARG, b"bad stream index")
+    for i, msg in ((2, b"bad stream index"), (1, b"stream did not parse")):
+        refused(L.d4g_batch_copy_output(h, i, buf, len(buf)), ARG, msg)
+        refused(L.d4g_batch_copy_decoded(h, i, buf, len(buf), None), ARG, msg)
+        refused(L.d4g_batch_checksums(h, i, ctypes.byref(u32), ctypes.byref(u32), ctypes.byref(i64)), ARG, msg)
+    refused(L.d4g_batch_copy_output(h, 0, one, 1), ARG, b"output buffer too small")
+    refused(L.d4g_batch_copy_decoded(h, 0, one, 1, None), ARG, b"output buffer too small")
+    refused(L.d4g_batch_parse(h), ARG, b"batch already ran")
+    b.close()
+    b = D.Batch([rd("lz-twice-twice.s00.in.deflate")], lib=L)
+    refused(L.d4g_batch_run_recompress(b.h, 9, 1, 1), ARG, b"mode out of range")
+    b.close()
+    # encoder specs: refused levels (D4G_ERR_ARG), an unknown encoder at level 9 (D4G_ERR_RUNTIME from the front end)
+    raw = (ctypes.c_char_p * 1)(b"abcabcabc")
+    rl = (ctypes.c_size_t * 1)(9)
+    level0 = b"encoder spec: level 0 is not supported (zlib's deflate_stored output depends on the caller's output buffer)"
+    for spec, msg in (((0, 0, 0, 0), level0), ((0, 0, 0, 10), b"encoder spec: level must be -1 or 1..9"),
+                      ((0, 1, 0, 6), b"encoder spec: the jzlib flavour supports level 9 with DEFAULT / FILTERED / HUFFMAN_ONLY only"),
+                      ((1, 0, 0, 6), b"encoder spec: input out of range")):
+        no_batch(L.d4g_batch_create_encode_level(1, raw, rl, 1, ctypes.byref(d4g_encoder_spec_level(*spec))), msg)
+    no_batch(L.d4g_batch_create_encode(1, raw, rl, 1, ctypes.byref(d4g_encoder_spec(0, 5, 0))), b"bad encoder spec")
+    s = abi_calls.Slots(1)
+    refused(L.d4g_deflate_streams(1, raw, rl, 5, 0, s.out, s.len), RUNTIME, b"bad encoder spec")
+    assert s.unchanged()
+    # one-shot calls with one bad option each: a refused level, bad Zopfli options, a mode out of range
+    calls = abi_calls.one_shot_calls(L, [b"abcabcabc", b""], mode=9, level=0, iterations=0)
+    for name, msg in (("d4g_deflate_streams_level", level0), ("d4g_zopfli_streams", b"bad zopfli options"),
+                      ("d4g_compress", b"mode out of range"), ("d4g_recompress_streams", b"mode out of range")):
+        call, slots, check = calls[name]
+        refused(call(), ARG, msg)
+        assert slots.unchanged(**check), name
+
+
 def test_fused_executor_mask_tasks_in_their_any_length_form(sim, monkeypatch):
     """The fused executor's mask tasks have a register form (blocks of up to 16384 back-references) and a chunked form for
     longer (merged) blocks: D4G_FUSED_REG_WORDS=0 sends every block through the chunked form."""
