@@ -8,16 +8,8 @@
 // on the fly from code-length runs, and Huffman construction replays the JDK binary heap
 // in LDS so ties break exactly as java.util.PriorityQueue does.
 #pragma once
+#include "d4g_arch.h"
 #include "d4g_types.h"
-
-#ifndef D4G_HOSTSIM
-#include <hip/hip_runtime.h>
-#endif
-
-#define D4G_DEV __device__ __forceinline__
-// Issue priority of the optimiser's waves (s_setprio): above the default 0, so that they are not starved by an old, always-ready
-// wave of another kernel on the same SIMD (the Zopfli squeeze runs for minutes); serial sections go to 3 and come back here.
-#define D4G_BASE_PRIO 1
 
 // ---------------------------------------------------------------------------------------
 // RFC 1951 symbol arithmetic (B/deflate/Constants.java:9-23,65-128) — closed forms instead
@@ -73,21 +65,6 @@ D4G_DEV int ref_ebits(uint32_t a) { return (int)((a >> 19) & 31u); }
 D4G_DEV long long wave_sum_i64(long long v) {   // wraps (the mask hashes sum 64-bit values): added as unsigned
     for (int m = 32; m >= 1; m >>= 1) v = (long long)((unsigned long long)v + (unsigned long long)__shfl_xor(v, m));
     return v;
-}
-// 32-bit wave sum: row scans and row broadcasts on the DPP path (six v_add_u32), no LDS crossbar trips
-D4G_DEV int wave_sum_i32(int v) {
-#ifdef D4G_HOSTSIM
-    for (int m = 32; m >= 1; m >>= 1) v = (int)((unsigned)v + (unsigned)__shfl_xor(v, m));   // wraps, as v_add_u32 (hash sums)
-    return v;
-#else
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(v, 63);
-#endif
 }
 D4G_DEV long long wave_min_i64(long long v) {
     for (int m = 32; m >= 1; m >>= 1) {
@@ -351,21 +328,6 @@ __device__ int d4g_tree_finish(TreeMem<H, I, MAXN, IDB_, OVL>& m, int stride, in
 // `limit` goes through the serial DFS + limiter of d4g_tree_finish.
 // ---------------------------------------------------------------------------------------
 #define D4G_LAMBDA_INLINE __attribute__((always_inline))
-// The wave's vote on a condition.  (HIP's __ballot takes an int: a bool goes through 0 / 1 and a second compare.)
-#ifdef D4G_HOSTSIM
-D4G_DEV unsigned long long d4g_ballot(bool p) { return __ballot(p ? 1 : 0); }
-#else
-D4G_DEV unsigned long long d4g_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-#endif
-#ifdef D4G_HOSTSIM
-D4G_DEV int d4g_readlane(int v, int k) { return __shfl(v, k); }
-D4G_DEV int d4g_uniform(int v) { return __shfl(v, 0); }
-D4G_DEV void d4g_wave_sync() { (void)__shfl(0, 0); }   // the emulator's lanes are not in lock step: rendezvous
-#else
-D4G_DEV int d4g_readlane(int v, int k) { return __builtin_amdgcn_readlane(v, k); }
-D4G_DEV int d4g_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-D4G_DEV void d4g_wave_sync() { __builtin_amdgcn_wave_barrier(); }  // LDS accesses of one wave are already in order
-#endif
 
 // ---------------------------------------------------------------------------------------
 // The 19-symbol code-length tree of one lane in registers (the header search: one candidate per lane).
@@ -504,6 +466,7 @@ struct D4GWaveHeap {
         if (k < 64) { ww = regW(k); ii = regI(k); }
         else {
             uint64_t e = deep[k];
+            d4g_lockstep();
             ww = (unsigned)d4g_uniform((int)(e >> 32));
             ii = d4g_uniform((int)(uint32_t)e);
         }
@@ -517,13 +480,14 @@ struct D4GWaveHeap {
     D4G_DEV void get2(int k, unsigned& w0o, int& i0o, unsigned& w1o, int& i1o) const {
         if (k >= 64) {
             const uint64_t e0 = deep[k], e1 = deep[k + 1];
+            d4g_lockstep();
             w0o = (unsigned)d4g_uniform((int)(e0 >> 32)); i0o = d4g_uniform((int)(uint32_t)e0);
             w1o = (unsigned)d4g_uniform((int)(e1 >> 32)); i1o = d4g_uniform((int)(uint32_t)e1);
         } else { get(k, w0o, i0o); get(k + 1, w1o, i1o); }
     }
 };
 
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
 __device__ unsigned long long d4g_dbg_tree[4];       // literal/length tree sections: leaves, merges, depths
 __device__ unsigned long long d4g_dbg_counters[8];   // profile builds: [0] wave trees built, [1] of them through the serial limiter, [2] leaves
 #endif
@@ -534,9 +498,7 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
     const int lane = threadIdx.x & 63;
     numSymbols = d4g_uniform(numSymbols);  // tell the compiler what is wave-uniform: the queue code then runs on the scalar unit
     limit = d4g_uniform(limit);
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(3);   // a serial section everyone in the workgroup waits for: issue ahead of the throughput-bound waves
-#endif
+    D4G_SETPRIO(3);   // a serial section everyone in the workgroup waits for: issue ahead of the throughput-bound waves
     D4GWaveHeap hp;
     hp.w0 = 0; hp.i0 = 0;
     hp.deep = (uint64_t*)m.heap;
@@ -602,7 +564,7 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
             hp.put(k, xw, xi);
         }
     };
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     long long tq0 = clock64();
 #endif
     // leaves in symbol order: 64 frequencies per step, the used ones are offered one by one
@@ -630,7 +592,7 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
         }
         index++;
     }
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     long long tq1 = clock64();
 #endif
     int nn = nl;
@@ -651,7 +613,7 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
     unsigned rootW;
     int root;
     pq_remove(rootW, root);
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     long long tq2 = clock64();
     if (lane == 0 && MAXN > 100) {
         atomicAdd(&d4g_dbg_tree[0], (unsigned long long)(tq1 - tq0));
@@ -672,7 +634,7 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
         maxDepth = d > maxDepth ? d : maxDepth;
     }
     maxDepth = wave_max_i32(maxDepth);
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     if (lane == 0 && MAXN > 100) atomicAdd(&d4g_dbg_tree[2], (unsigned long long)(clock64() - tq2));
     if (lane == 0) {
         int slot = MAXN > 100 ? 0 : (MAXN > 20 ? 3 : 5);   // literal/length, distance, code-length trees
@@ -684,9 +646,7 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
     if (maxDepth > limit) {
         int err = 0;
         if (lane == 0) err = d4g_tree_finish(m, 1, 0, nl, root, numSymbols, limit, outLen);
-#ifndef D4G_HOSTSIM
-        __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+        D4G_SETPRIO(D4G_BASE_PRIO);
         return __shfl(err, 0);
     }
 #pragma unroll
@@ -697,9 +657,7 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
             if (v < numSymbols) outLen(v, dep[r]);
         }
     }
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     return 0;
 }
 
@@ -713,18 +671,6 @@ __device__ int d4g_build_tree_wave(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSym
 // level of a poll), several times faster than the general queue above, whose deep slots live in LDS.
 // ---------------------------------------------------------------------------------------
 #define D4G_RP_INF 0xffffffffu
-template <int D> D4G_DEV unsigned d4g_rp_sibling(unsigned v) {   // the value held by the lane 2^(5-D) away
-#ifdef D4G_HOSTSIM
-    return (unsigned)__shfl_xor((int)v, 32 >> D);
-#else
-    if (D == 0) return (unsigned)__shfl_xor((int)v, 32);
-    if (D == 1) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);                  // swap with lane ^ 16
-    if (D == 2) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xf, 0xf, false);    // row_ror:8
-    if (D == 3) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);                  // swap with lane ^ 4
-    if (D == 4) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, false);     // quad_perm [2,3,0,1]
-    return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, false);                  // quad_perm [1,0,3,2]
-#endif
-}
 struct D4GPathHeap {
     unsigned R[7];
     unsigned mA[6];   // 0xff where this lane's slot of level d + 1 is a right child
@@ -792,9 +738,7 @@ template <typename H, typename I, int MAXN, int IDB_, bool OVL, typename FreqFn,
 __device__ int d4g_build_tree_wave_path(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSymbols, int limit, FreqFn freq, OutFn outLen) {
     const int SIDE = TreeMem<H, I, MAXN, IDB_, OVL>::SIDE;
     const int lane = threadIdx.x & 63;
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(3);
-#endif
+    D4G_SETPRIO(3);
     D4GPathHeap hp;
     hp.init();
     int nl = 0;
@@ -854,9 +798,7 @@ __device__ int d4g_build_tree_wave_path(TreeMem<H, I, MAXN, IDB_, OVL>& m, int n
     if (maxDepth > limit) {
         int err = 0;
         if (lane == 0) err = d4g_tree_finish(m, 1, 0, nl, root, numSymbols, limit, outLen);
-#ifndef D4G_HOSTSIM
-        __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+        D4G_SETPRIO(D4G_BASE_PRIO);
         return __shfl(err, 0);
     }
 #pragma unroll
@@ -867,9 +809,7 @@ __device__ int d4g_build_tree_wave_path(TreeMem<H, I, MAXN, IDB_, OVL>& m, int n
             if (v < numSymbols) outLen(v, dep[r]);
         }
     }
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     return 0;
 }
 
@@ -889,22 +829,6 @@ __device__ int d4g_build_tree_wave_path(TreeMem<H, I, MAXN, IDB_, OVL>& m, int n
 // No loop over sift levels, no branches: two cross-lane reads per poll, one per offer.  Results (node arrays in `m`,
 // depths, the limiter path) are those of d4g_build_tree_wave, which is also what larger inputs fall back to.
 // ---------------------------------------------------------------------------------------
-// bit p of x -> bit 2p (p < 32)
-D4G_DEV unsigned long long d4g_spread_bits(unsigned x) {
-#ifdef D4G_HOSTSIM
-    unsigned long long v = x;
-    v = (v | (v << 16)) & 0x0000ffff0000ffffull;
-    v = (v | (v << 8)) & 0x00ff00ff00ff00ffull;
-    v = (v | (v << 4)) & 0x0f0f0f0f0f0f0f0full;
-    v = (v | (v << 2)) & 0x3333333333333333ull;
-    v = (v | (v << 1)) & 0x5555555555555555ull;
-    return v;
-#else
-    unsigned long long o;
-    asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(o) : "s"(x));   // every bit doubled
-    return o & 0x5555555555555555ull;
-#endif
-}
 template <int NREG, typename H, typename I, int MAXN, int IDB_, bool OVL, typename FreqFn, typename OutFn>
 __device__ int d4g_build_tree_wave64(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numSymbols, int limit, FreqFn freq, OutFn outLen) {
     const int SIDE = TreeMem<H, I, MAXN, IDB_, OVL>::SIDE;
@@ -923,9 +847,7 @@ __device__ int d4g_build_tree_wave64(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numS
     total = (unsigned long long)wave_sum_i64((long long)total);
     if (used > 127 || total >= (1ull << 24) - 4) return d4g_build_tree_wave<NREG>(m, numSymbols, limit, freq, outLen);
     if (used > 64) return d4g_build_tree_wave_path(m, numSymbols, limit, freq, outLen);   // (ids stay below 255: at most 127 leaves + 126 merges)
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(3);
-#endif
+    D4G_SETPRIO(3);
     unsigned hv = 0;   // the queue: slot = lane
     int hs = 0;
     const int parentLane = (lane - 1) >> 1;   // (lane 0: -1, masked below)
@@ -1026,18 +948,14 @@ __device__ int d4g_build_tree_wave64(TreeMem<H, I, MAXN, IDB_, OVL>& m, int numS
     if (maxDepth > limit) {
         int err = 0;
         if (lane == 0) err = d4g_tree_finish(m, 1, 0, nl, root, numSymbols, limit, outLen);
-#ifndef D4G_HOSTSIM
-        __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+        D4G_SETPRIO(D4G_BASE_PRIO);
         return __shfl(err, 0);
     }
     if (lane < nl) {
         const int v = m.value[lane];
         if (v < numSymbols) outLen(v, dep);
     }
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     return 0;
 }
 

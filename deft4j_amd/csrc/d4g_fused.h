@@ -43,12 +43,6 @@
 #define D4F_HS_SLOTS 8      // header searches running side by side (one wave each)
 #define D4F_TREE_SLOTS 4   // Huffman rebuilds running side by side (two waves each: literal/length and distance tree)
 
-#ifdef D4G_HOSTSIM
-D4G_DEV void d4f_fence_block() {}
-#else
-D4G_DEV void d4f_fence_block() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
-#endif
-
 // ---- per-block tables in HBM (carved from the block's state slots 1.. — the level executor's slots, unused here) ----
 struct D4FCode {            // 384 B
     uint8_t lens[D4G_NLIT + D4G_NDIST];
@@ -296,7 +290,7 @@ D4G_DEV void d4f_push(int q, int v) {
 // a wave's tree (all lanes call): the wave-wide JDK heap on the GPU; the emulator runs the one-lane form unless asked
 template <int NREG, typename TM, typename FreqFn, typename OutFn>
 __device__ __forceinline__ int d4f_wave_tree(TM& tm, int numSymbols, int limit, FreqFn freq, OutFn out) {
-#if !defined(D4G_HOSTSIM) || defined(D4G_SIM_WAVE_HEAP)
+#ifndef D4G_SERIAL_TREES
     return d4g_build_tree_wave64<NREG>(tm, numSymbols, limit, freq, out);
 #else
     int err = 0;
@@ -402,7 +396,7 @@ D4G_DEV void d4f_finish(int dst, int m, int c, int h, int type, int valid, long 
         D4FSlot s;
         s.m = (int16_t)m; s.c = (int16_t)c; s.h = (int16_t)h; s.valid = (uint8_t)valid; s.type = (uint8_t)type; s.lazy = lazy; s.litlen = litlen;
         F.slot[dst] = s;
-        d4f_fence_block();
+        d4g_fence_block();
         F.slotReady[dst] = 1;
     }
 }
@@ -413,7 +407,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
     int stage = F.opStage[opId];
     if (stage == 255) return false;
     if (!F.slotReady[op.src]) return false;
-    d4f_fence_block();
+    d4g_fence_block();
     const D4FSlot src = F.slot[op.src];
     bool progressed = false;
     auto done = [&](long long key) {
@@ -433,7 +427,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
         if (!src.valid || src.type != D4G_DYNAMIC) { done(D4G_KEY_NONE); return true; }
         if (stage == 0) { d4f_req_hs(src.c); F.opStage[opId] = 1; stage = 1; progressed = true; }
         if (F.hsState[src.c] == 2) {
-            d4f_fence_block();
+            d4g_fence_block();
             done(D4G_MAKE_KEY(src.litlen + (long long)F.hsBits[src.c], (long long)opId * 64 + F.hsLane[src.c]));
         }
         return progressed;
@@ -458,7 +452,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
         }
         const D4FHdrE& e = F.hdrReq[F.opReq[opId]];
         if (e.st == 2) {
-            d4f_fence_block();
+            d4g_fence_block();
             d4f_finish(op.dst, src.m, src.c, e.hOut, src.type, 1, src.litlen);
             done(cand_key(1, src.litlen + F.hdrBits[e.hOut]));
         }
@@ -479,7 +473,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
             if (he.st != 2) break;
             hOut = he.hOut;
         }
-        d4f_fence_block();
+        d4g_fence_block();
         const long long lit = src.litlen - e.saved;
         const long long size = lit + (dyn ? (long long)F.hdrBits[hOut] : 0LL);
         const int valid = (op.arg & 1) ? (d4f_slot_size(src) - size > 0) : 1;
@@ -496,7 +490,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
         if (stage == 1) {
             const D4FPassE& e = F.pass[F.opReq[opId]];
             if (e.st != 2) break;
-            d4f_fence_block();
+            d4g_fence_block();
             const int m2 = e.mOut;
             F.opReq[opId] = (uint16_t)m2;
             d4f_req_tree(m2);
@@ -505,7 +499,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
         if (stage == 2) {
             const int m2 = F.opReq[opId];
             if (F.treeSt[m2] != 2) break;
-            d4f_fence_block();
+            d4g_fence_block();
             const int c2 = F.treeC[m2];
             const int h2 = F.defHdr[c2];
             const long long lit = F.treeLit[m2];
@@ -528,7 +522,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
             if (stage == 1) {
                 const D4FPassE& e = F.pass[F.opReq[opId]];
                 if (e.st != 2) break;
-                d4f_fence_block();
+                d4g_fence_block();
                 const int m2 = e.mOut;
                 F.opReq[opId] = (uint16_t)m2;
                 d4f_req_tree(m2);
@@ -537,7 +531,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
             if (stage == 2) {
                 const int m2 = F.opReq[opId];
                 if (F.treeSt[m2] != 2) break;
-                d4f_fence_block();
+                d4g_fence_block();
                 const int c2 = F.treeC[m2];
                 const int h2 = F.defHdr[c2];
                 const long long lit = F.treeLit[m2];
@@ -569,7 +563,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
         }
         const D4FLeastE& e = F.least[F.opReq[opId]];
         if (e.st == 2) {
-            d4f_fence_block();
+            d4g_fence_block();
             const long long lit = src.litlen + e.delta;
             d4f_finish(op.dst, e.mOut, src.c, src.h, src.type, 1, lit);
             done(cand_key(1, lit + F.hdrBits[src.h]));
@@ -593,7 +587,7 @@ D4F_TASK bool d4f_advance_op(const D4GOp op, int opId, long long* bestKeyP) {
         if (stage == 2) {
             const D4FPassE& e = F.pass[F.opReq[opId]];
             if (e.st != 2) break;
-            d4f_fence_block();
+            d4g_fence_block();
             const long long lit = (src.type == D4G_FIXED ? src.litlen : F.fixdotLit) - e.saved;
             d4f_finish(op.dst, src.m, D4F_CODE_FIXED, 0, D4G_FIXED, 1, lit, 1);
             done(cand_key(1, lit));
@@ -927,7 +921,7 @@ D4F_TASK void d4f_apply_task(int idx) {
         for (int j = 0; j < D4F_NWR; j++) { d[j] = ew[j] & ~mw[j]; cnt += __popcll(d[j]); }
         cnt = wave_sum_i32(cnt);
         if (cnt == 0) {
-            if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4f_fence_block(); e.st = 2; }
+            if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4g_fence_block(); e.st = 2; }
             return;
         }
         int mNew = m;
@@ -936,7 +930,7 @@ D4F_TASK void d4f_apply_task(int idx) {
             d4g_wave_sync();
             mNew = W.misc[0];
             d4g_wave_sync();
-            if (mNew == 0) { if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4f_fence_block(); e.st = 2; } return; }
+            if (mNew == 0) { if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4g_fence_block(); e.st = 2; } return; }
 #pragma unroll
             for (int i = 0; i < D4G_HIST / 64; i++) W.hist[lane + 64 * i] = hr[i];
         }
@@ -972,14 +966,14 @@ D4F_TASK void d4f_apply_task(int idx) {
             if (lane == 0) F.maskFull[mNew] = F.maskFull[m];
             mOut = d4f_publish_mask(c, b, G, mNew, h1, h2, F.maskPop[m] + cnt, W.hist);
         }
-        if (lane == 0) { e.mOut = (int16_t)mOut; e.saved = saved; d4f_fence_block(); e.st = 2; }
+        if (lane == 0) { e.mOut = (int16_t)mOut; e.saved = saved; d4g_fence_block(); e.st = 2; }
         return;
     }
     int cnt = 0;
     for (int w = lane; w < nWords; w += 64) cnt += __popcll(E[w] & ~M[w]);
     cnt = wave_sum_i32(cnt);
     if (cnt == 0) {
-        if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4f_fence_block(); e.st = 2; }
+        if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4g_fence_block(); e.st = 2; }
         return;
     }
     int mNew = m;
@@ -988,7 +982,7 @@ D4F_TASK void d4f_apply_task(int idx) {
         d4g_wave_sync();
         mNew = W.misc[0];
         d4g_wave_sync();
-        if (mNew == 0) { if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4f_fence_block(); e.st = 2; } return; }
+        if (mNew == 0) { if (lane == 0) { e.mOut = (int16_t)m; e.saved = 0; d4g_fence_block(); e.st = 2; } return; }
         for (int i = lane; i < D4G_HIST; i += 64) W.hist[i] = G.hist[(size_t)m * D4G_HIST + i];
     }
     d4f_wave_load_code(W, G.code[code]);
@@ -1020,7 +1014,7 @@ D4F_TASK void d4f_apply_task(int idx) {
         if (lane == 0) F.maskFull[mNew] = F.maskFull[m];
         mOut = d4f_publish_mask(c, b, G, mNew, h1, h2, F.maskPop[m] + cnt, W.hist);
     }
-    if (lane == 0) { e.mOut = (int16_t)mOut; e.saved = saved; d4f_fence_block(); e.st = 2; }
+    if (lane == 0) { e.mOut = (int16_t)mOut; e.saved = saved; d4g_fence_block(); e.st = 2; }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1153,7 +1147,7 @@ D4F_TASK void d4f_least_task(int idx) {
         const int rem = W.misc[1], remSize = W.misc[2], mNew = W.misc[0];
         d4g_wave_sync();
         if (rem < 0 || mNew == 0) {
-            if (lane == 0) { e.mOut = (int16_t)m; e.delta = 0; d4f_fence_block(); e.st = 2; }
+            if (lane == 0) { e.mOut = (int16_t)m; e.delta = 0; d4g_fence_block(); e.st = 2; }
             return;
         }
         // expand the bin: new mask = old | bin mask; the histogram loses the bin's unexpanded records' symbols and gains their bytes
@@ -1210,7 +1204,7 @@ D4F_TASK void d4f_least_task(int idx) {
         d4g_wave_sync();
         if (lane == 0) F.maskFull[mNew] = full | (1u << rem);
         const int mOut = d4f_publish_mask(c, b, G, mNew, h1, h2, F.maskPop[m] + cnt, W.hist);
-        if (lane == 0) { e.mOut = (int16_t)mOut; e.delta = remSize; d4f_fence_block(); e.st = 2; }
+        if (lane == 0) { e.mOut = (int16_t)mOut; e.delta = remSize; d4g_fence_block(); e.st = 2; }
         return;
     }
     d4f_wave_load_code(W, G.code[code]);
@@ -1265,7 +1259,7 @@ D4F_TASK void d4f_least_task(int idx) {
     const int rem = W.misc[1], remSize = W.misc[2], mNew = W.misc[0];
     d4g_wave_sync();
     if (rem < 0 || mNew == 0) {
-        if (lane == 0) { e.mOut = (int16_t)m; e.delta = 0; d4f_fence_block(); e.st = 2; }
+        if (lane == 0) { e.mOut = (int16_t)m; e.delta = 0; d4g_fence_block(); e.st = 2; }
         return;
     }
     // expand the bin: new mask = old | bin mask; the histogram loses the bin's unexpanded records' symbols and gains their bytes
@@ -1307,7 +1301,7 @@ D4F_TASK void d4f_least_task(int idx) {
     d4g_wave_sync();
     if (lane == 0) F.maskFull[mNew] = F.maskFull[m] | (1u << rem);
     const int mOut = d4f_publish_mask(c, b, G, mNew, h1, h2, F.maskPop[m] + cnt, W.hist);
-    if (lane == 0) { e.mOut = (int16_t)mOut; e.delta = remSize; d4f_fence_block(); e.st = 2; }
+    if (lane == 0) { e.mOut = (int16_t)mOut; e.delta = remSize; d4g_fence_block(); e.st = 2; }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1482,7 +1476,7 @@ D4F_TASK void d4f_hdr_task(int idx) {
         if (lane == 0) { dst.nCl = H.nCl; dst.bits = H.bits; dst.base = src.base; F.hdrBits[hNew] = H.bits; }
     }
     d4g_wave_sync();
-    if (lane == 0) { e.hOut = (int16_t)hNew; d4f_fence_block(); e.st = 2; }
+    if (lane == 0) { e.hOut = (int16_t)hNew; d4g_fence_block(); e.st = 2; }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1615,7 +1609,7 @@ D4F_TASK void d4f_tree_publish(int slotIdx) {
         }
     }
     d4g_wave_sync();
-    if (lane == 0) { F.treeC[T.m] = (uint8_t)code; F.treeLit[T.m] = T.litlen; d4f_fence_block(); F.treeSt[T.m] = 2; }
+    if (lane == 0) { F.treeC[T.m] = (uint8_t)code; F.treeLit[T.m] = T.litlen; d4g_fence_block(); F.treeSt[T.m] = 2; }
     d4g_wave_sync();
 }
 
@@ -1689,7 +1683,7 @@ D4F_TASK int d4f_hs_task(int slotIdx, int code) {
     if (lane == 0) {
         F.hsBits[code] = (int32_t)(key >> D4G_KEY_SEQ_BITS);
         F.hsLane[code] = (uint8_t)(key & 63);
-        d4f_fence_block();
+        d4g_fence_block();
         F.hsState[code] = 2;
     }
     d4g_wave_sync();
@@ -1700,13 +1694,6 @@ D4F_TASK int d4f_hs_task(int slotIdx, int code) {
 // Cluster mode (see the notes at D4FClArena): the worker every workgroup runs on a posted command, and the control
 // workgroup's side of the three kinds of step that scale with the block's length.
 // ---------------------------------------------------------------------------------------
-#ifdef D4G_HOSTSIM
-D4G_DEV int d4f_atomic_ld(const int32_t* p) { return *p; }
-D4G_DEV void d4f_atomic_st(int32_t* p, int v) { *p = v; }
-#else
-D4G_DEV int d4f_atomic_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-D4G_DEV void d4f_atomic_st(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
 D4G_DEV D4FClCmd& d4f_cl_cmd() { return d4fLds.cl->slot[(d4fLds.clEpoch - 1) % D4F_CL_SLOTS]; }
 
 // Work on the command in hand until no item is left.  All threads of a workgroup call; any workgroup of the launch may.
@@ -1882,9 +1869,9 @@ D4F_TASK void d4f_cl_begin(int n) {
     if (threadIdx.x == 0) F.clEpoch++;
     __syncthreads();
     D4FClCmd& C = d4f_cl_cmd();
-    for (int i = threadIdx.x; i < (int)(offsetof(D4FClCmd, task) / 4); i += blockDim.x) st_sc1((uint32_t*)&C + i, 0u);
+    for (int i = threadIdx.x; i < (int)(offsetof(D4FClCmd, task) / 4); i += blockDim.x) d4g_st_agent((uint32_t*)&C + i, 0u);
     const int words = (int)(sizeof(D4FClTask) / 4);
-    for (int i = threadIdx.x; i < n * words; i += blockDim.x) st_sc1((uint32_t*)&C.task[0] + i, 0u);
+    for (int i = threadIdx.x; i < n * words; i += blockDim.x) d4g_st_agent((uint32_t*)&C.task[0] + i, 0u);
     d4g_drain_stores();
     __syncthreads();
 }
@@ -1896,20 +1883,20 @@ D4F_TASK void d4f_cl_run() {
     __syncthreads();
     if (threadIdx.x == 0) {
         d4g_release_agent();
-        if (F.clEpoch <= D4F_CL_SLOTS) d4f_atomic_st(&F.cl->epoch, F.clEpoch);   // (beyond the slots: nobody is told, the control workgroup works alone)
+        if (F.clEpoch <= D4F_CL_SLOTS) d4g_st_agent(&F.cl->epoch, F.clEpoch);   // (beyond the slots: nobody is told, the control workgroup works alone)
     }
     __syncthreads();
     d4f_cl_work();
     if (threadIdx.x == 0) {
         const int nItems = C.nItems;
         long long spin = 0;   // (only items some resident workgroup has already taken are outstanding: microseconds; the bound is for a device gone wrong)
-        while (d4f_atomic_ld(&C.done) < nItems && ++spin < (1LL << 25)) d4g_sleep();
-        if (d4f_atomic_ld(&C.done) < nItems) { atomicAdd(F.c.errors, 1); F.fallback = 1; }
+        while (d4g_ld_agent(&C.done) < nItems && ++spin < (1LL << 25)) d4g_sleep();
+        if (d4g_ld_agent(&C.done) < nItems) { atomicAdd(F.c.errors, 1); F.fallback = 1; }
         d4g_acquire_agent();
     }
     __syncthreads();
 }
-D4G_DEV void d4f_cl_set(int32_t* p, int v) { st_sc1((uint32_t*)p, (uint32_t)v); }
+D4G_DEV void d4f_cl_set(int32_t* p, int v) { d4g_st_agent((uint32_t*)p, (uint32_t)v); }
 
 D4F_TASK void d4f_cl_sweep() {
     D4FLds& F = d4fLds;
@@ -1971,7 +1958,7 @@ D4F_TASK void d4f_cl_apply_phase(int nq) {
                     mOut = d4f_publish_mask(c, b, G, T.mNew, T.h1 + F.maskH1[m], T.h2 + F.maskH2[m], F.maskPop[m] + cnt, W.hist);
                 }
             }
-            if (lane == 0) { e.mOut = (int16_t)mOut; e.saved = saved; d4f_fence_block(); e.st = 2; }
+            if (lane == 0) { e.mOut = (int16_t)mOut; e.saved = saved; d4g_fence_block(); e.st = 2; }
         }
         __syncthreads();
     }
@@ -2058,7 +2045,7 @@ D4F_TASK void d4f_cl_least_phase(int nq) {
                 mOut = d4f_publish_mask(c, b, G, mNew, T.h1 + F.maskH1[m], T.h2 + F.maskH2[m], F.maskPop[m] + T.cnt, W.hist);
                 dl = T.pad0[0];
             }
-            if (lane == 0) { e.mOut = (int16_t)mOut; e.delta = dl; d4f_fence_block(); e.st = 2; }
+            if (lane == 0) { e.mOut = (int16_t)mOut; e.delta = dl; d4g_fence_block(); e.st = 2; }
         }
         __syncthreads();
     }
@@ -2263,10 +2250,8 @@ D4F_TASK bool d4f_select(long long best, D4GRoundResult* out) {
         }
         __syncthreads();
         if (threadIdx.x == 0 && S->sizeBits != bestSize) {
-#ifdef D4G_HOSTSIM
-            fprintf(stderr, "fused select: op %d kind %d lane %d assembled to %lld bits (litlen %lld hdr %lld), the search said %lld\n", opId, op.kind, hl,
+            D4G_SIM_LOG("fused select: op %d kind %d lane %d assembled to %lld bits (litlen %lld hdr %lld), the search said %lld\n", opId, op.kind, hl,
                     (long long)S->sizeBits, (long long)S->litlenBits, (long long)S->hdrBits, bestSize);
-#endif
             atomicAdd(c.errors, 1);
         }
         if (mid != 0) {
@@ -2464,7 +2449,7 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
                     for (int k = 0; k < nq - nu; k++) {
                         const int m = F.treeCand[1][k] >> 16, from = F.treeCand[1][k] & 0xffff;
                         F.treeC[m] = F.treeC[from]; F.treeLit[m] = F.treeLit[from];
-                        d4f_fence_block();
+                        d4g_fence_block();
                         F.treeSt[m] = 2;
                     }
                 }
@@ -2534,9 +2519,7 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
 #define D4F_WAVES_PER_SIMD 4
 #endif
 __global__ void __launch_bounds__(512) D4G_WAVES_PER_SIMD(D4F_WAVES_PER_SIMD) k_search_fused(D4GCtx cArg, D4FParams P) {
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     if ((int)blockIdx.x >= cArg.nActive) return;
     d4f_block_init(cArg, P, (int)blockIdx.x, nullptr);
     d4f_block_rounds(P);
@@ -2544,15 +2527,13 @@ __global__ void __launch_bounds__(512) D4G_WAVES_PER_SIMD(D4F_WAVES_PER_SIMD) k_
 
 // One long block, many workgroups: workgroup 0 runs the search, the others work off the commands it posts (D4FClArena).
 __global__ void __launch_bounds__(512) D4G_WAVES_PER_SIMD(D4F_WAVES_PER_SIMD) k_search_cluster(D4GCtx cArg, D4FParams P, D4FClArena* arena, int which) {
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     D4FLds& F = d4fLds;
     d4f_block_init(cArg, P, which, arena);
     if (blockIdx.x == 0) {
         d4f_block_rounds(P);
         __syncthreads();
-        if (threadIdx.x == 0) { d4g_release_agent(); d4f_atomic_st(&arena->epoch, -1); }
+        if (threadIdx.x == 0) { d4g_release_agent(); d4g_st_agent(&arena->epoch, -1); }
         return;
     }
     int seen = 0;
@@ -2560,7 +2541,7 @@ __global__ void __launch_bounds__(512) D4G_WAVES_PER_SIMD(D4F_WAVES_PER_SIMD) k_
         if (threadIdx.x == 0) {
             int e = seen;
             for (long long spin = 0; spin < (1LL << 23); spin++) {   // (a helper that waits this long — seconds — leaves: the control workgroup does not need it)
-                e = d4f_atomic_ld(&arena->epoch);
+                e = d4g_ld_agent(&arena->epoch);
                 if (e != seen) break;
                 d4g_sleep();
             }

@@ -53,12 +53,6 @@
 #define LZ_FLAVOR_ZLIB 0
 #define LZ_FLAVOR_JZLIB 1
 
-#ifdef D4G_HOSTSIM
-#define LZ_WAVE_SYNC() ((void)__ballot(1))
-#else
-#define LZ_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
-#endif
-
 struct LzStream {           // one uncompressed input
     const uint8_t* data;    // in U (16-byte aligned, >= 320 zero bytes after the end)
     long long len;
@@ -157,15 +151,15 @@ __global__ void __launch_bounds__(LZ_SORT_THREADS) k_lz_sort(const LzStream* str
         unsigned h = 0;
         if (valid) h = lz_hash3(d[i], d[i + 1], d[i + 2]);
         unsigned cur = valid ? vt[h] : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (valid) vt[h] = (uint16_t)(0x8000u | (unsigned)lane);
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         unsigned w = valid ? vt[h] : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (valid && (w & 63u) != (unsigned)lane) vt[h] = (uint16_t)(0xC000u | (unsigned)lane);
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         unsigned w2 = valid ? vt[h] : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         bool dup = valid && (w2 & 0x4000u);
         unsigned rank = cur;
         if (valid && !dup) vt[h] = (uint16_t)(cur + 1);
@@ -180,7 +174,7 @@ __global__ void __launch_bounds__(LZ_SORT_THREADS) k_lz_sort(const LzStream* str
             }
             rem &= ~m;
         }
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (valid) {
             Rout[i] = (uint16_t)rank;
             Sout[rank] = (uint16_t)i;
@@ -381,9 +375,9 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
             uint32_t v = 0xffffffffu;
             if (x < headPos && x < mapEnd) v = c.insFrozen[job.insBase + (x >> 5)];
             else if (prevW0 >= 0 && i + sh < LZ_BITS_WORDS) v = insw[i + sh];
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
             if (i < LZ_BITS_WORDS) insw[i] = v;
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
         }
         prevW0 = w0;
     }
@@ -446,12 +440,12 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
             if (b < lo + 32) m &= ~0u >> (lo + 32 - b);
             own[wi] &= ~m;
         }
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
     };
     bool lastInterior = false;   // deflate_fast: the last match's inside was inserted
     if (KIND == LZ_KIND_FAST) {
         own[((c0 - bw0) >> 5) + lane] = 0xffffffffu;   // LZ_CHUNK_WORDS == 64: one word per lane
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (rec && p > c0 && !ma) clearBits(c0, p);
     }
     if (KIND == LZ_KIND_SLOW) {

@@ -3,54 +3,9 @@
 #pragma once
 #include "d4g_device.h"
 
-// Candidate states and masks are handed from workgroup to workgroup inside one launch.  They are
-// written with agent-scope write-through stores and read with agent-scope (L1-bypassing) loads, so the
-// hand-off needs no L2 write-back / L1 invalidate per task (MI355X_MICROARCH.md: "sc1 stores + drained
-// flag", every load of the handed-off bytes an sc1 load).  Tokens and decoded bytes are read-only and
-// keep using plain cached loads.
-#ifdef D4G_HOSTSIM
-D4G_DEV uint32_t ld_sc1(const uint32_t* p) { return *p; }
-D4G_DEV uint64_t ld_sc1(const uint64_t* p) { return *p; }
-D4G_DEV void st_sc1(uint32_t* p, uint32_t v) { *p = v; }
-D4G_DEV void st_sc1(uint64_t* p, uint64_t v) { *p = v; }
-#else
-D4G_DEV uint32_t ld_sc1(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-D4G_DEV uint64_t ld_sc1(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-D4G_DEV void st_sc1(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-D4G_DEV void st_sc1(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
-D4G_DEV int ld_state_i32(const int32_t* p) { return (int)ld_sc1((const uint32_t*)p); }
-// flags that hand work from one workgroup to another inside a launch
-#ifdef D4G_HOSTSIM
-D4G_DEV int d4g_flag_load(const int32_t* p) { return *p; }
-D4G_DEV void d4g_flag_store(int32_t* p, int v) { *p = v; }
-D4G_DEV void d4g_release_agent() {}
-D4G_DEV void d4g_acquire_agent() {}
-D4G_DEV void d4g_drain_stores() {}
-D4G_DEV void d4g_sleep() {}
-#else
-D4G_DEV int d4g_flag_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-D4G_DEV void d4g_flag_store(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-D4G_DEV void d4g_release_agent() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-D4G_DEV void d4g_acquire_agent() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-D4G_DEV void d4g_drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-#ifndef D4G_SPIN_SLEEP
-#define D4G_SPIN_SLEEP 8
-#endif
-D4G_DEV void d4g_sleep() { __builtin_amdgcn_s_sleep(D4G_SPIN_SLEEP); }
-#endif
-
-
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
 __device__ unsigned long long d4g_dbg_pass[4];  // computed replace passes: lookup cycles, loop cycles, count, records
 __device__ unsigned long long d4g_dbg_hdr[4];   // profile builds: header rewrite sections (RLE, code-length tree, tail), count
-// profile builds: a clock read that is not overtaken by (and does not overtake) outstanding LDS / memory operations
-D4G_DEV long long d4g_clock_drained() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    long long t = clock64();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return t;
-}
 #endif
 
 // Header-search memo.  The 56 header candidates of a state depend only on its code lengths, and most of a block's
@@ -104,13 +59,6 @@ struct D4GPassMemo {
     // followed by maskWords u64 (the outgoing mask) and maskWords u64 (the incoming mask: the rest of the key)
 };
 #define D4G_PASSMEMO_HDR_WORDS ((int)(sizeof(D4GPassMemo) / 8))
-
-// occupancy target of a kernel (caps its VGPR budget); the emulator build has no such notion
-#ifdef D4G_HOSTSIM
-#define D4G_WAVES_PER_SIMD(n)
-#else
-#define D4G_WAVES_PER_SIMD(n) __attribute__((amdgpu_waves_per_eu(n, 8)))
-#endif
 
 struct D4GCtx {
     const uint2* tok;         // {token word, decoded-byte offset}
@@ -304,7 +252,7 @@ __device__ __forceinline__ int wg_passmemo_lookup(D4GLds* L, const D4GCtx& c, co
     const uint32_t* lw = (const uint32_t*)S->litLen;   // litLen[288] + distLen[32], contiguous
     for (int i = threadIdx.x; i < (D4G_NLIT + D4G_NDIST) / 4; i += blockDim.x) { a1 += mix1(i, lw[i]); a2 += mix2(i, lw[i]); }
     for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) {
-        unsigned long long m = ld_sc1(maskIn + w);
+        unsigned long long m = d4g_ld_agent(maskIn + w);
         a1 += mix1(1000 + w, m);
         a2 += mix2(1000 + w, m);
     }
@@ -328,14 +276,14 @@ __device__ __forceinline__ int wg_passmemo_lookup(D4GLds* L, const D4GCtx& c, co
                 long long w0 = clock64();
 #endif
                 for (int spin = 0; spin < (1 << 16); spin++) {
-                    st = d4g_flag_load(&e->state);
+                    st = d4g_ld_agent(&e->state);
                     if (st == 2) break;
                     d4g_sleep();
                 }
 #ifdef D4G_PROFILE_OPS
                 if (c.opStats) { atomicAdd((unsigned long long*)&c.opStats[32], (unsigned long long)(clock64() - w0)); atomicAdd((unsigned long long*)&c.opStats[33], 1ULL); }
 #endif
-                if (st == 2 && ld_sc1((const uint64_t*)&e->check) == (uint64_t)h2) { role = 2; idx = k; }
+                if (st == 2 && d4g_ld_agent((const uint64_t*)&e->check) == (uint64_t)h2) { role = 2; idx = k; }
                 break;
             }
         }
@@ -352,14 +300,14 @@ __device__ __forceinline__ int wg_passmemo_lookup(D4GLds* L, const D4GCtx& c, co
     // The hashes only find the entry; what decides is the key itself: codes, comparison mode and incoming mask.
     uint64_t* keyMask = (uint64_t*)entry + D4G_PASSMEMO_HDR_WORDS + b.maskWords;
     if (role == 1) {   // ours: the key goes in now, the result and the flag follow when the pass is done
-        for (int i = threadIdx.x; i < (D4G_NLIT + D4G_NDIST) / 4; i += blockDim.x) st_sc1(&entry->keyCodes[i], lw[i]);
-        for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) st_sc1(keyMask + w, ld_sc1(maskIn + w));
-        if (threadIdx.x == 0) st_sc1((uint32_t*)&entry->keyKind, (uint32_t)kind);
+        for (int i = threadIdx.x; i < (D4G_NLIT + D4G_NDIST) / 4; i += blockDim.x) d4g_st_agent(&entry->keyCodes[i], lw[i]);
+        for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) d4g_st_agent(keyMask + w, d4g_ld_agent(maskIn + w));
+        if (threadIdx.x == 0) d4g_st_agent((uint32_t*)&entry->keyKind, (uint32_t)kind);
     } else if (role == 2) {
         int bad = 0;
-        for (int i = threadIdx.x; i < (D4G_NLIT + D4G_NDIST) / 4; i += blockDim.x) bad |= ld_sc1(&entry->keyCodes[i]) != lw[i];
-        for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) bad |= ld_sc1(keyMask + w) != ld_sc1(maskIn + w);
-        if (threadIdx.x == 0) bad |= ld_state_i32(&entry->keyKind) != kind;
+        for (int i = threadIdx.x; i < (D4G_NLIT + D4G_NDIST) / 4; i += blockDim.x) bad |= d4g_ld_agent(&entry->keyCodes[i]) != lw[i];
+        for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) bad |= d4g_ld_agent(keyMask + w) != d4g_ld_agent(maskIn + w);
+        if (threadIdx.x == 0) bad |= d4g_ld_agent(&entry->keyKind) != kind;
         if (wg_max_i32(bad, L->red)) { role = 0; entry = nullptr; }   // same hashes, different key: compute without the memo
     }
     return role;
@@ -368,10 +316,10 @@ __device__ __forceinline__ int wg_passmemo_lookup(D4GLds* L, const D4GCtx& c, co
 __device__ __forceinline__ void wg_passmemo_apply(D4GLds* L, const D4GBlock& b, const D4GPassMemo* e, uint64_t* maskOut) {
     D4GState* S = &L->st;
     const uint64_t* mm = (const uint64_t*)e + D4G_PASSMEMO_HDR_WORDS;
-    for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) st_sc1(maskOut + w, ld_sc1(mm + w));
-    for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) S->hist[i] += (uint32_t)ld_state_i32(&e->delta[i]);
+    for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) d4g_st_agent(maskOut + w, d4g_ld_agent(mm + w));
+    for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) S->hist[i] += (uint32_t)d4g_ld_agent(&e->delta[i]);
     if (threadIdx.x == 0) {
-        long long saved = (long long)ld_sc1((const uint64_t*)&e->saved);
+        long long saved = (long long)d4g_ld_agent((const uint64_t*)&e->saved);
         S->sizeBits -= saved;
         S->litlenBits -= saved;
     }
@@ -395,7 +343,7 @@ __device__ __forceinline__ void wg_replace_backrefs(D4GLds* L, const D4GCtx& c, 
     const int K = D4G_TOK_ILP;
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     __syncthreads();
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     long long pp0 = d4g_clock_drained(), pp1 = 0, pp2 = 0;
 #endif
     // ---- memo lookup: hashes over both codes, the incoming mask and the comparison mode ----
@@ -412,7 +360,7 @@ __device__ __forceinline__ void wg_replace_backrefs(D4GLds* L, const D4GCtx& c, 
             mine = nullptr;
         }
     }
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     pp1 = d4g_clock_drained();
 #endif
     wg_fill_lit_cost(L);
@@ -431,7 +379,7 @@ __device__ __forceinline__ void wg_replace_backrefs(D4GLds* L, const D4GCtx& c, 
         for (int j = 0; j < K; j++) {
             int w = wbase + j, r = w * 64 + lane;
             int wc = w < nWords ? w : 0, rc = r < nRef ? r : 0;
-            nmw[j] = nWords ? ld_sc1(maskIn + wc) : 0;
+            nmw[j] = nWords ? d4g_ld_agent(maskIn + wc) : 0;
             nrv[j] = nRef ? rf[rc] : make_uint4(0u, 0u, 0u, 0u);
             if (r >= nRef) nrv[j] = make_uint4(0u, 0u, 0u, 0u);
             if (w >= nWords) nmw[j] = 0;
@@ -484,17 +432,17 @@ __device__ __forceinline__ void wg_replace_backrefs(D4GLds* L, const D4GCtx& c, 
         }
         uint64_t nm = d4g_ballot(bit);
         if (lane == 0) {
-            st_sc1(maskOut + w0, nm);
-            if (mine) st_sc1((uint64_t*)mine + D4G_PASSMEMO_HDR_WORDS + w0, nm);
+            d4g_st_agent(maskOut + w0, nm);
+            if (mine) d4g_st_agent((uint64_t*)mine + D4G_PASSMEMO_HDR_WORDS + w0, nm);
         }
     }
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     pp2 = d4g_clock_drained();
 #endif
     long long saved = wg_sum_i64((long long)savedLane, L->red);
     if (threadIdx.x == 0) { S->sizeBits -= saved; S->litlenBits -= saved; }
     __syncthreads();
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     if (threadIdx.x == 0) {
         atomicAdd(&d4g_dbg_pass[0], (unsigned long long)(pp1 - pp0));
         atomicAdd(&d4g_dbg_pass[1], (unsigned long long)(pp2 - pp1));
@@ -503,14 +451,14 @@ __device__ __forceinline__ void wg_replace_backrefs(D4GLds* L, const D4GCtx& c, 
     }
 #endif
     if (mine) {   // publish: histogram deltas, the outgoing mask, then the flag
-        for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) st_sc1((uint32_t*)&mine->delta[i], (uint32_t)((int)S->hist[i] - histBefore[i]));
+        for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) d4g_st_agent((uint32_t*)&mine->delta[i], (uint32_t)((int)S->hist[i] - histBefore[i]));
         if (threadIdx.x == 0) {
-            st_sc1((uint64_t*)&mine->saved, (uint64_t)saved);
-            st_sc1((uint64_t*)&mine->check, (uint64_t)h2);
+            d4g_st_agent((uint64_t*)&mine->saved, (uint64_t)saved);
+            d4g_st_agent((uint64_t*)&mine->check, (uint64_t)h2);
         }
         d4g_drain_stores();
         __syncthreads();
-        if (threadIdx.x == 0) d4g_flag_store(&mine->state, 2);
+        if (threadIdx.x == 0) d4g_st_agent(&mine->state, 2);
     }
 }
 
@@ -636,7 +584,7 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
         if (role != 1) mine = nullptr;
     }
     uint64_t* memoMask = mine ? (uint64_t*)mine + D4G_PASSMEMO_HDR_WORDS : nullptr;
-    if (mine) for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) st_sc1((uint32_t*)&mine->delta[i], 0u);
+    if (mine) for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) d4g_st_agent((uint32_t*)&mine->delta[i], 0u);
     if (threadIdx.x < 64) L->misc[threadIdx.x] = 0;
     if (threadIdx.x < 32) binZ[threadIdx.x] = 0;
     if (threadIdx.x < 4) flags[threadIdx.x] = 0;
@@ -651,7 +599,7 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
     const uint64_t* bmask = c.binMask + b.binMask;
     {
         unsigned pc = 0;
-        for (int w = threadIdx.x; w < nWords; w += blockDim.x) pc += (unsigned)__popcll(ld_sc1(maskIn + w));
+        for (int w = threadIdx.x; w < nWords; w += blockDim.x) pc += (unsigned)__popcll(d4g_ld_agent(maskIn + w));
         if (pc) atomicAdd(npop, pc);
     }
     __syncthreads();
@@ -677,7 +625,7 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
             }
             __syncthreads();
             // correction: the expanded records do not count
-            if (wave < nwq) wave_for_selected(wave, nwq, nWords, nRef, rf, queues + 128 * wave, [&](int w) { return ld_sc1(maskIn + w); },
+            if (wave < nwq) wave_for_selected(wave, nwq, nWords, nRef, rf, queues + 128 * wave, [&](int w) { return d4g_ld_agent(maskIn + w); },
                               [&](int, uint4 rv) {
                                   uint32_t a = rv.x;
                                   int bin = ref_lsym(a) - 257;
@@ -688,7 +636,7 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
                                   if (total >= D4G_NO_CODE) atomicSub(&binZ[bin], total >> 14);
                               });
         } else {
-            if (wave < nwq) wave_for_selected(wave, nwq, nWords, nRef, rf, queues + 128 * wave, [&](int w) { return ~ld_sc1(maskIn + w); },
+            if (wave < nwq) wave_for_selected(wave, nwq, nWords, nRef, rf, queues + 128 * wave, [&](int w) { return ~d4g_ld_agent(maskIn + w); },
                               [&](int, uint4 rv) {
                                   uint32_t a = rv.x;
                                   int bin = ref_lsym(a) - 257;
@@ -724,18 +672,18 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
     auto publish = [&]() D4G_LAMBDA_INLINE {
         if (!mine) return;
         if (threadIdx.x == 0) {
-            st_sc1((uint64_t*)&mine->saved, (uint64_t)(-(long long)(int)flags[3]));
-            st_sc1((uint64_t*)&mine->check, (uint64_t)memoH2);
+            d4g_st_agent((uint64_t*)&mine->saved, (uint64_t)(-(long long)(int)flags[3]));
+            d4g_st_agent((uint64_t*)&mine->check, (uint64_t)memoH2);
         }
         d4g_drain_stores();
         __syncthreads();
-        if (threadIdx.x == 0) d4g_flag_store(&mine->state, 2);
+        if (threadIdx.x == 0) d4g_st_agent(&mine->state, 2);
     };
     if (rem < 0) {
         for (int w = threadIdx.x; w < nWords; w += blockDim.x) {
-            uint64_t v = ld_sc1(maskIn + w);
-            st_sc1(maskOut + w, v);
-            if (mine) st_sc1(memoMask + w, v);
+            uint64_t v = d4g_ld_agent(maskIn + w);
+            d4g_st_agent(maskOut + w, v);
+            if (mine) d4g_st_agent(memoMask + w, v);
         }
         __syncthreads();
         publish();
@@ -744,12 +692,12 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
     // expand the bin: new mask = old | bin mask; the histogram loses the bin's unexpanded records' symbols and gains their bytes
     const uint64_t* bm = bmask + (long long)rem * nWords;
     for (int w = threadIdx.x; w < nWords; w += blockDim.x) {
-        uint64_t v = ld_sc1(maskIn + w) | bm[w];
-        st_sc1(maskOut + w, v);
-        if (mine) st_sc1(memoMask + w, v);
+        uint64_t v = d4g_ld_agent(maskIn + w) | bm[w];
+        d4g_st_agent(maskOut + w, v);
+        if (mine) d4g_st_agent(memoMask + w, v);
     }
     // what the already expanded records of the bin contributed to the static row (they were moved earlier)
-    if (wave < nwq) wave_for_selected(wave, nwq, nWords, nRef, rf, queues + 128 * wave, [&](int w) { return ld_sc1(maskIn + w) & bm[w]; },
+    if (wave < nwq) wave_for_selected(wave, nwq, nWords, nRef, rf, queues + 128 * wave, [&](int w) { return d4g_ld_agent(maskIn + w) & bm[w]; },
                       [&](int, uint4 rv) {
                           uint32_t a = rv.x;
                           atomicAdd(&delta[D4G_BIN_DIST + ref_dsym(a)], 1);
@@ -763,13 +711,13 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
             int moved = (int)row[i] - delta[i];
             if (!moved) continue;
             // (byte values, distance symbols and the bin's length symbol are distinct histogram slots)
-            if (i < 256) { atomicAdd(&S->hist[i], (unsigned)moved); if (mine) st_sc1((uint32_t*)&mine->delta[i], (uint32_t)moved); }
+            if (i < 256) { atomicAdd(&S->hist[i], (unsigned)moved); if (mine) d4g_st_agent((uint32_t*)&mine->delta[i], (uint32_t)moved); }
             else if (i < D4G_BIN_COUNT) {
                 atomicSub(&S->hist[D4G_NLIT + i - D4G_BIN_DIST], (unsigned)moved);
-                if (mine) st_sc1((uint32_t*)&mine->delta[D4G_NLIT + i - D4G_BIN_DIST], (uint32_t)(-moved));
+                if (mine) d4g_st_agent((uint32_t*)&mine->delta[D4G_NLIT + i - D4G_BIN_DIST], (uint32_t)(-moved));
             } else {
                 atomicSub(&S->hist[257 + rem], (unsigned)moved);
-                if (mine) st_sc1((uint32_t*)&mine->delta[257 + rem], (uint32_t)(-moved));
+                if (mine) d4g_st_agent((uint32_t*)&mine->delta[257 + rem], (uint32_t)(-moved));
             }
         }
     }
@@ -794,7 +742,7 @@ __device__ __forceinline__ void t0_build_cl_tree(D4GLds* L) {
 // the same by all lanes of wave 0
 __device__ __forceinline__ void w0_build_cl_tree(D4GLds* L) {
     D4GState* S = &L->st;
-#if !defined(D4G_HOSTSIM) || defined(D4G_SIM_WAVE_HEAP)
+#ifndef D4G_SERIAL_TREES
     TreeMem<uint32_t, uint8_t, 20> tm;
     tm.carve(L->treeCl, 1);
     const int lane = threadIdx.x & 63;
@@ -843,16 +791,14 @@ __device__ __forceinline__ void w0_remove_trailing_header_codes(D4GState* S) {
 __device__ __forceinline__ void wg_rewrite_header(D4GLds* L, int flags) {
     D4GState* S = &L->st;
     __syncthreads();
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
     long long r0 = d4g_clock_drained(), r1 = 0, r2 = 0;
 #endif
     if (S->type != D4G_DYNAMIC) return;
     if (threadIdx.x < 20) L->clFreq[threadIdx.x] = 0;
     __syncthreads();
     if (threadIdx.x < 64) {
-#ifndef D4G_HOSTSIM
-        __builtin_amdgcn_s_setprio(3);   // the workgroup's other waves wait for this one
-#endif
+        D4G_SETPRIO(3);   // the workgroup's other waves wait for this one
         const int lane = threadIdx.x;
         const int nLit = S->nLit, n = nLit + S->nDist;
         auto len = [&](int i) { return i < nLit ? (int)S->litLen[i] : (int)S->distLen[i - nLit]; };
@@ -897,12 +843,12 @@ __device__ __forceinline__ void wg_rewrite_header(D4GLds* L, int flags) {
             base += __shfl(incl, 63);
         }
         if (lane == 0) S->nPairs = base;
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
         r1 = d4g_clock_drained();
 #endif
         // code-length code (Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134) and the header's size
         w0_build_cl_tree(L);
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+#ifdef D4G_PROFILE_OPS
         r2 = d4g_clock_drained();
 #endif
         int hbl = 0;
@@ -915,10 +861,8 @@ __device__ __forceinline__ void wg_rewrite_header(D4GLds* L, int flags) {
         }
         d4g_wave_sync();
         w0_remove_trailing_header_codes(S);
-#ifndef D4G_HOSTSIM
-        __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
-#if defined(D4G_PROFILE_OPS) && !defined(D4G_HOSTSIM)
+        D4G_SETPRIO(D4G_BASE_PRIO);
+#ifdef D4G_PROFILE_OPS
         if (lane == 0) {
             atomicAdd(&d4g_dbg_hdr[0], (unsigned long long)(r1 - r0));
             atomicAdd(&d4g_dbg_hdr[1], (unsigned long long)(r2 - r1));
@@ -1057,11 +1001,11 @@ __device__ __forceinline__ void wg_recode_huffman(D4GLds* L, D4GRecodeMemo* memo
                 if (t == h1) {
                     int st = 0;
                     for (int spin = 0; spin < (1 << 16); spin++) {
-                        st = d4g_flag_load(&e->state);
+                        st = d4g_ld_agent(&e->state);
                         if (st == 2) break;
                         d4g_sleep();
                     }
-                    if (st == 2 && ld_sc1((const uint64_t*)&e->check) == (uint64_t)h2) { role = 2; idx = k; }
+                    if (st == 2 && d4g_ld_agent((const uint64_t*)&e->check) == (uint64_t)h2) { role = 2; idx = k; }
                     break;
                 }
             }
@@ -1074,22 +1018,22 @@ __device__ __forceinline__ void wg_recode_huffman(D4GLds* L, D4GRecodeMemo* memo
         __syncthreads();
         // the hashes only find the entry: a hit is confirmed against the histogram it was built from
         if (role == 1) {
-            for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) st_sc1(&e->key[i], S->hist[i]);
+            for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) d4g_st_agent(&e->key[i], S->hist[i]);
         } else if (role == 2) {
             int bad = 0;
-            for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) bad |= ld_sc1(&e->key[i]) != S->hist[i];
+            for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) bad |= d4g_ld_agent(&e->key[i]) != S->hist[i];
             if (wg_max_i32(bad, L->red)) role = 0;
         }
         if (role == 2) {
-            for (int i = threadIdx.x; i < D4G_RCMEMO_WORDS; i += blockDim.x) ((uint32_t*)S)[16 + i] = ld_sc1(&e->body[i]);
+            for (int i = threadIdx.x; i < D4G_RCMEMO_WORDS; i += blockDim.x) ((uint32_t*)S)[16 + i] = d4g_ld_agent(&e->body[i]);
             if (threadIdx.x == 0) {
                 S->type = D4G_DYNAMIC;
-                S->nLit = ld_state_i32(&e->nLit); S->nDist = ld_state_i32(&e->nDist);
-                S->nCl = ld_state_i32(&e->nCl); S->nPairs = ld_state_i32(&e->nPairs);
-                S->litlenBits = (long long)ld_sc1((const uint64_t*)&e->litlenBits);
-                S->hdrBits = (long long)ld_sc1((const uint64_t*)&e->hdrBits);
+                S->nLit = d4g_ld_agent(&e->nLit); S->nDist = d4g_ld_agent(&e->nDist);
+                S->nCl = d4g_ld_agent(&e->nCl); S->nPairs = d4g_ld_agent(&e->nPairs);
+                S->litlenBits = (long long)d4g_ld_agent((const uint64_t*)&e->litlenBits);
+                S->hdrBits = (long long)d4g_ld_agent((const uint64_t*)&e->hdrBits);
                 S->sizeBits = S->litlenBits + S->hdrBits;
-                if (ld_state_i32(&e->err)) S->flags |= 0x100;
+                if (d4g_ld_agent(&e->err)) S->flags |= 0x100;
             }
             __syncthreads();
             return;
@@ -1109,7 +1053,7 @@ __device__ __forceinline__ void wg_recode_huffman(D4GLds* L, D4GRecodeMemo* memo
     for (int i = threadIdx.x; i < D4G_NLIT; i += blockDim.x) S->litLen[i] = 0;
     for (int i = threadIdx.x; i < D4G_NDIST; i += blockDim.x) S->distLen[i] = 0;
     __syncthreads();
-#if !defined(D4G_HOSTSIM) || defined(D4G_SIM_WAVE_HEAP)
+#ifndef D4G_SERIAL_TREES
     // wave 0 builds the literal/length tree while wave 1 (when there is one) builds the distance tree
     const int wv = d4g_uniform((int)(threadIdx.x >> 6)), ln = threadIdx.x & 63;
     if (wv == 0) {
@@ -1183,18 +1127,18 @@ __device__ __forceinline__ void wg_recode_huffman(D4GLds* L, D4GRecodeMemo* memo
     wg_litlen_bits_from_hist(L);
     wg_rewrite_header(L, F_DEFAULT);
     if (mine) {   // publish the rebuilt part of the state, then the flag
-        for (int i = threadIdx.x; i < D4G_RCMEMO_WORDS; i += blockDim.x) st_sc1(&mine->body[i], ((const uint32_t*)S)[16 + i]);
+        for (int i = threadIdx.x; i < D4G_RCMEMO_WORDS; i += blockDim.x) d4g_st_agent(&mine->body[i], ((const uint32_t*)S)[16 + i]);
         if (threadIdx.x == 0) {
-            st_sc1((uint32_t*)&mine->nLit, (uint32_t)S->nLit); st_sc1((uint32_t*)&mine->nDist, (uint32_t)S->nDist);
-            st_sc1((uint32_t*)&mine->nCl, (uint32_t)S->nCl); st_sc1((uint32_t*)&mine->nPairs, (uint32_t)S->nPairs);
-            st_sc1((uint32_t*)&mine->err, (uint32_t)((S->flags & 0x100) ? 1 : 0));
-            st_sc1((uint64_t*)&mine->litlenBits, (uint64_t)S->litlenBits);
-            st_sc1((uint64_t*)&mine->hdrBits, (uint64_t)S->hdrBits);
-            st_sc1((uint64_t*)&mine->check, (uint64_t)h2);
+            d4g_st_agent((uint32_t*)&mine->nLit, (uint32_t)S->nLit); d4g_st_agent((uint32_t*)&mine->nDist, (uint32_t)S->nDist);
+            d4g_st_agent((uint32_t*)&mine->nCl, (uint32_t)S->nCl); d4g_st_agent((uint32_t*)&mine->nPairs, (uint32_t)S->nPairs);
+            d4g_st_agent((uint32_t*)&mine->err, (uint32_t)((S->flags & 0x100) ? 1 : 0));
+            d4g_st_agent((uint64_t*)&mine->litlenBits, (uint64_t)S->litlenBits);
+            d4g_st_agent((uint64_t*)&mine->hdrBits, (uint64_t)S->hdrBits);
+            d4g_st_agent((uint64_t*)&mine->check, (uint64_t)h2);
         }
         d4g_drain_stores();
         __syncthreads();
-        if (threadIdx.x == 0) d4g_flag_store(&mine->state, 2);
+        if (threadIdx.x == 0) d4g_st_agent(&mine->state, 2);
     }
 #ifdef D4G_PROFILE_OPS
     if (threadIdx.x == 0 && prof) {
@@ -1265,16 +1209,16 @@ D4G_DEV bool d4g_pull_task(const D4GQueue& q, int& cursor, int& opIdx, int& actI
 
 D4G_DEV void wg_load_state(D4GState* S, const D4GState* g) {
     __syncthreads();
-    for (int i = threadIdx.x; i < (int)(sizeof(D4GState) / 4); i += blockDim.x) ((uint32_t*)S)[i] = ld_sc1((const uint32_t*)g + i);
+    for (int i = threadIdx.x; i < (int)(sizeof(D4GState) / 4); i += blockDim.x) ((uint32_t*)S)[i] = d4g_ld_agent((const uint32_t*)g + i);
     __syncthreads();
 }
 D4G_DEV void wg_store_state(D4GState* g, const D4GState* S) {
     __syncthreads();
-    for (int i = threadIdx.x; i < (int)(sizeof(D4GState) / 4); i += blockDim.x) st_sc1((uint32_t*)g + i, ((const uint32_t*)S)[i]);
+    for (int i = threadIdx.x; i < (int)(sizeof(D4GState) / 4); i += blockDim.x) d4g_st_agent((uint32_t*)g + i, ((const uint32_t*)S)[i]);
     __syncthreads();
 }
 D4G_DEV void wg_copy_mask(uint64_t* dst, const uint64_t* src, long long words) {
-    for (long long i = threadIdx.x; i < words; i += blockDim.x) st_sc1(dst + i, ld_sc1(src + i));
+    for (long long i = threadIdx.x; i < words; i += blockDim.x) d4g_st_agent(dst + i, d4g_ld_agent(src + i));
     __syncthreads();
 }
 
@@ -1290,11 +1234,11 @@ __device__ bool wg_wait_slot(const D4GCtx& c, const D4GQueue& q, int blk, int sl
         int ok = 0;
         // bounded: ~1 s in total by default, and every waiter gives up as soon as any other has
         for (long long spin = 0; spin < q.spinLimit; spin++) {
-            if (d4g_flag_load(f) == q.epoch) { ok = 1; break; }
-            if ((spin & 63) == 63 && d4g_flag_load(c.errors + 1) != 0) break;
+            if (d4g_ld_agent(f) == q.epoch) { ok = 1; break; }
+            if ((spin & 63) == 63 && d4g_ld_agent(c.errors + 1) != 0) break;
             d4g_sleep();
         }
-        if (!ok && q.spinLimit >= 0 && d4g_flag_load(f) == q.epoch) ok = 1;
+        if (!ok && q.spinLimit >= 0 && d4g_ld_agent(f) == q.epoch) ok = 1;
         if (!ok) atomicAdd(c.errors + 1, 1);
         *lds = ok;
     }
@@ -1304,7 +1248,7 @@ __device__ bool wg_wait_slot(const D4GCtx& c, const D4GQueue& q, int blk, int sl
 __device__ void wg_publish_slot(const D4GCtx& c, const D4GQueue& q, int blk, int slot) {
     d4g_drain_stores();
     __syncthreads();
-    if (threadIdx.x == 0) d4g_flag_store(q.ready + (long long)blk * c.slotsPerBlock + slot, q.epoch);
+    if (threadIdx.x == 0) d4g_st_agent(q.ready + (long long)blk * c.slotsPerBlock + slot, q.epoch);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1321,14 +1265,14 @@ __device__ __forceinline__ void d4g_exec_state_op(D4GLds* L, const D4GCtx& c, in
     long long* keyp = c.keys + (long long)blk * c.nOps + opId;
     if (op.kind == OP_CAND) {
         if (threadIdx.x == 0) {
-            long long sz = (long long)ld_sc1((const uint64_t*)&src->sizeBits);
-            *keyp = ld_state_i32(&src->valid) ? D4G_MAKE_KEY(sz, (long long)opId * 64) : D4G_KEY_NONE;
+            long long sz = (long long)d4g_ld_agent((const uint64_t*)&src->sizeBits);
+            *keyp = d4g_ld_agent(&src->valid) ? D4G_MAKE_KEY(sz, (long long)opId * 64) : D4G_KEY_NONE;
         }
         return;
     }
     D4GState* dst = state_ptr(c, blk, op.dst);
-    if (!ld_state_i32(&src->valid)) {  // the reference never builds this candidate (null / skipped branch)
-        if (threadIdx.x == 0) { st_sc1((uint32_t*)&dst->valid, 0u); *keyp = D4G_KEY_NONE; }
+    if (!d4g_ld_agent(&src->valid)) {  // the reference never builds this candidate (null / skipped branch)
+        if (threadIdx.x == 0) { d4g_st_agent((uint32_t*)&dst->valid, 0u); *keyp = D4G_KEY_NONE; }
         return;
     }
     wg_load_state(S, src);
@@ -1419,9 +1363,7 @@ __device__ __forceinline__ void d4g_exec_state_op(D4GLds* L, const D4GCtx& c, in
     __syncthreads();
     if (threadIdx.x == 0) {
         if (S->flags & 0x100) {
-#ifdef D4G_HOSTSIM
-            fprintf(stderr, "state op %d kind %d: tree limiter failed\n", opId, op.kind);
-#endif
+            D4G_SIM_LOG("state op %d kind %d: tree limiter failed\n", opId, op.kind);
             atomicAdd(c.errors, 1);
         }
         *keyp = (op.seq >= 0 && S->valid) ? D4G_MAKE_KEY(S->sizeBits, (long long)opId * 64) : D4G_KEY_NONE;
@@ -1458,9 +1400,7 @@ D4G_DEV bool d4g_map_wg(int nActive, int nOpsLevel, int tileGroups, int& blkSlot
 #define D4G_STATE_WAVES 8
 #endif
 __global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_STATE_WAVES) k_exec_state_ops(D4GCtx c, const int32_t* opList, int nOpsLevel) {
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     __shared__ D4GLds L;
     int bs, orel;
     if (!d4g_map_wg(c.nActive, nOpsLevel, c.tileGroups, bs, orel)) return;
@@ -1470,9 +1410,7 @@ __global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_STATE_WAVES) k_exe
 // Same body for the token-pass-only ops (optimise / least-expensive pruning): they have no single-lane
 // section, so they run with wide workgroups (up to 16 waves sweep the block's tokens together).
 __global__ void __launch_bounds__(1024) k_exec_state_ops_wide(D4GCtx c, const int32_t* opList, int nOpsLevel) {
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     __shared__ D4GLds L;
     int bs, orel;
     if (!d4g_map_wg(c.nActive, nOpsLevel, c.tileGroups, bs, orel)) return;
@@ -1485,9 +1423,7 @@ __global__ void __launch_bounds__(1024) k_exec_state_ops_wide(D4GCtx c, const in
 #define D4G_PERSIST_WAVES 4
 #endif
 __global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_PERSIST_WAVES) k_persist_state_ops(D4GCtx c, D4GQueue q) {
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     __shared__ D4GLds L;
     __shared__ int sTask[3], sOk;
     int cursor = 0;
@@ -1508,7 +1444,7 @@ __global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_PERSIST_WAVES) k_p
         if (ok) d4g_exec_state_op(&L, c, blk, opId);
         else if (threadIdx.x == 0) {
             c.keys[(long long)blk * c.nOps + opId] = D4G_KEY_NONE;
-            if (op.dst >= 0) st_sc1((uint32_t*)&state_ptr(c, blk, op.dst)->valid, 0u);
+            if (op.dst >= 0) d4g_st_agent((uint32_t*)&state_ptr(c, blk, op.dst)->valid, 0u);
         }
         if (op.dst >= 0) wg_publish_slot(c, q, blk, op.dst);
     }
@@ -1535,13 +1471,6 @@ struct D4GHdrLds {
     uint8_t fbLen[19];
 };
 
-// a wave-uniform value in a scalar register (in the emulator, where this would be a wave collective, the value itself)
-#ifdef D4G_HOSTSIM
-D4G_DEV int d4g_scalar(int v) { return v; }
-#else
-D4G_DEV int d4g_scalar(int v) { return __builtin_amdgcn_readfirstlane(v); }
-#endif
-
 // count += cnt for the wave-uniform symbol v < 16 of counts packed two per register
 D4G_DEV void d4g_cl_count(uint32_t (&f2)[8], int v, uint32_t cnt) {
     const uint32_t add = cnt << (16 * (v & 1));
@@ -1567,16 +1496,7 @@ D4G_DEV bool d4g_cl_lengths(D4GHdrLds* H, int lane, FreqFn freq, D4GClLens& len)
 #pragma unroll
         for (int s = 16; s < 19; s++) len.hi |= (uint32_t)H->fbLen[s] << (4 * (s - 16));
     };
-#ifdef D4G_HOSTSIM
-    if (deep) rebuild();   // the emulator's lanes run one at a time between wave collectives
-#else
-    unsigned long long need = d4g_ballot(deep);
-    while (need) {
-        const int l = __ffsll((long long)need) - 1;
-        need &= need - 1;
-        if (lane == l) rebuild();
-    }
-#endif
+    d4g_lanes_in_turn(deep, lane, rebuild);
     return deep;
 }
 
@@ -1600,7 +1520,7 @@ __device__ __forceinline__ long long d4g_hdr_candidate_body(D4GHdrLds* H, int la
         for (int j = 0; j < 8; j++) f2[j] = base2[j];
         c16 = base16; c17 = base17; c18 = base18;
         for (int r = 0; r < nRuns; r++) {
-            const int v = d4g_scalar(H->runV[r]);
+            const int v = d4g_uniform(H->runV[r]);
             d4g_pack_kinds(v, H->runL[r], flags,
                            [&](int sym, int, int, int cnt) { if (sym == 16) c16 += cnt; else if (sym == 17) c17 += cnt; else c18 += cnt; },
                            [&](int cnt) { d4g_cl_count(f2, v, (uint32_t)cnt); });
@@ -1629,7 +1549,7 @@ __device__ __forceinline__ long long d4g_hdr_candidate_body(D4GHdrLds* H, int la
             uint32_t z = 0;
             c16 = base16; c17 = base17; c18 = base18;
             for (int r = 0; r < nRuns; r++) {
-                const int v = d4g_scalar(H->runV[r]);
+                const int v = d4g_uniform(H->runV[r]);
                 const int lv = c0.get(v);
                 int addV = 0;
                 d4g_pack_kinds(v, H->runL[r], flags,
@@ -1666,7 +1586,7 @@ __device__ __forceinline__ long long d4g_hdr_candidate_body(D4GHdrLds* H, int la
         const int a16 = c0.get(16), a17 = c0.get(17), a18 = c0.get(18), a0 = c0.get(0);
         const int b16 = c1.get(16), b17 = c1.get(17), b18 = c1.get(18), b0 = c1.get(0);
         for (int r = 0; r < nRuns; r++) {
-            const int v = d4g_scalar(H->runV[r]);
+            const int v = d4g_uniform(H->runV[r]);
             const int av = c0.get(v), bv = c1.get(v);
             d4g_pack_kinds(v, H->runL[r], flags,
                            [&](int sym, int run, int, int cnt) {
@@ -1710,17 +1630,17 @@ __device__ void d4g_exec_hdr_search(D4GHdrLds& H, uint8_t* comb, const D4GCtx& c
     long long hs0 = d4g_clock_drained();
 #endif
     __syncthreads();
-    if (!ld_state_i32(&base->valid) || ld_state_i32(&base->type) != D4G_DYNAMIC) {
+    if (!d4g_ld_agent(&base->valid) || d4g_ld_agent(&base->type) != D4G_DYNAMIC) {
         if (lane == 0) *keyp = D4G_KEY_NONE;
         return;
     }
-    int nLit = ld_state_i32(&base->nLit), n = nLit + ld_state_i32(&base->nDist);
+    int nLit = d4g_ld_agent(&base->nLit), n = nLit + d4g_ld_agent(&base->nDist);
     // code lengths word by word (litLen and distLen are 4-byte aligned, contiguous in the state)
-    for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) ((uint32_t*)H.lens)[i] = ld_sc1((const uint32_t*)base->litLen + i);
+    for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) ((uint32_t*)H.lens)[i] = d4g_ld_agent((const uint32_t*)base->litLen + i);
     __syncthreads();
     for (int i = lane; i < D4G_NLIT + D4G_NDIST; i += 64) comb[i] = i >= n ? 0 : i < nLit ? H.lens[i] : H.lens[D4G_NLIT + i - nLit];
     __syncthreads();
-    long long baseLitlenBits = (long long)ld_sc1((const uint64_t*)&base->litlenBits);
+    long long baseLitlenBits = (long long)d4g_ld_agent((const uint64_t*)&base->litlenBits);
     // ---- memo lookup: two position-keyed 64-bit hashes of the length set ----
     D4GHsMemo* mine = nullptr;   // the entry this search owns and must publish
     unsigned long long h1 = 0, h2 = 0;
@@ -1748,12 +1668,12 @@ __device__ void d4g_exec_hdr_search(D4GHdrLds& H, uint8_t* comb, const D4GCtx& c
                 if (t == h1) {                             // someone has it or is computing it: wait for the result
                     int st = 0;
                     for (int spin = 0; spin < (1 << 18); spin++) {
-                        st = d4g_flag_load(&e->state);
+                        st = d4g_ld_agent(&e->state);
                         if (st == 2) break;
                         d4g_sleep();
                     }
-                    if (st == 2 && ld_sc1((const uint64_t*)&e->check) == (uint64_t)h2) {
-                        found = ((long long)ld_state_i32(&e->hdr) << 8) | (long long)ld_state_i32(&e->lane);
+                    if (st == 2 && d4g_ld_agent((const uint64_t*)&e->check) == (uint64_t)h2) {
+                        found = ((long long)d4g_ld_agent(&e->hdr) << 8) | (long long)d4g_ld_agent(&e->lane);
                         slot = (int)(e - tab);
                     }
                     break;                                 // (timeout or a hash clash: compute without the memo)
@@ -1769,12 +1689,12 @@ __device__ void d4g_exec_hdr_search(D4GHdrLds& H, uint8_t* comb, const D4GCtx& c
             D4GHsMemo* e = tab + slot;
             const uint32_t* cw = (const uint32_t*)comb;
             if (owner) {
-                for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) st_sc1(&e->key[i], cw[i]);
-                if (lane == 0) { st_sc1((uint32_t*)&e->nLit, (uint32_t)nLit); st_sc1((uint32_t*)&e->n, (uint32_t)n); }
+                for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) d4g_st_agent(&e->key[i], cw[i]);
+                if (lane == 0) { d4g_st_agent((uint32_t*)&e->nLit, (uint32_t)nLit); d4g_st_agent((uint32_t*)&e->n, (uint32_t)n); }
             } else if (found >= 0) {
                 bool bad = false;
-                for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) bad |= ld_sc1(&e->key[i]) != cw[i];
-                if (lane == 0) bad |= ld_state_i32(&e->nLit) != nLit || ld_state_i32(&e->n) != n;
+                for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) bad |= d4g_ld_agent(&e->key[i]) != cw[i];
+                if (lane == 0) bad |= d4g_ld_agent(&e->nLit) != nLit || d4g_ld_agent(&e->n) != n;
                 if (d4g_ballot(bad)) found = -1;             // same hashes, different lengths: compute without the memo
             }
         }
@@ -1843,11 +1763,11 @@ __device__ void d4g_exec_hdr_search(D4GHdrLds& H, uint8_t* comb, const D4GCtx& c
         *keyp = key;
         if (mine) {   // publish: result first, then the flag
             long long bestSize = key >> D4G_KEY_SEQ_BITS;
-            st_sc1((uint32_t*)&mine->hdr, (uint32_t)(int32_t)(bestSize - baseLitlenBits));
-            st_sc1((uint32_t*)&mine->lane, (uint32_t)(key & 63));
-            st_sc1((uint64_t*)&mine->check, (uint64_t)h2);
+            d4g_st_agent((uint32_t*)&mine->hdr, (uint32_t)(int32_t)(bestSize - baseLitlenBits));
+            d4g_st_agent((uint32_t*)&mine->lane, (uint32_t)(key & 63));
+            d4g_st_agent((uint64_t*)&mine->check, (uint64_t)h2);
             d4g_drain_stores();
-            d4g_flag_store(&mine->state, 2);
+            d4g_st_agent(&mine->state, 2);
         }
     }
 #ifdef D4G_PROFILE_OPS
@@ -1861,9 +1781,7 @@ __device__ void d4g_exec_hdr_search(D4GHdrLds& H, uint8_t* comb, const D4GCtx& c
 }
 
 __global__ void __launch_bounds__(64) k_exec_hdr_search(D4GCtx c, const int32_t* opList, int nOpsLevel) {
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     __shared__ D4GHdrLds H;
     __shared__ __attribute__((aligned(16))) uint8_t comb[D4G_NLIT + D4G_NDIST];   // (compared word-wise against the memo's key)
     int bs, orel;
@@ -1872,9 +1790,7 @@ __global__ void __launch_bounds__(64) k_exec_hdr_search(D4GCtx c, const int32_t*
 }
 
 __global__ void __launch_bounds__(64) k_persist_hdr_search(D4GCtx c, D4GQueue q) {
-#ifndef D4G_HOSTSIM
-    __builtin_amdgcn_s_setprio(D4G_BASE_PRIO);
-#endif
+    D4G_SETPRIO(D4G_BASE_PRIO);
     __shared__ D4GHdrLds H;
     __shared__ __attribute__((aligned(16))) uint8_t comb[D4G_NLIT + D4G_NDIST];   // (compared word-wise against the memo's key)
     __shared__ int sTask[3], sOk;
@@ -1909,7 +1825,7 @@ __global__ void __launch_bounds__(256) k_select(D4GCtx c, D4GRoundResult* result
     const D4GBlock b = c.blocks[blk];
     D4GState* S = &L.st;
     D4GState* cur = state_ptr(c, blk, 0);
-    if (d4g_flag_load(c.errors + 1) != 0) {   // a wait of the persistent executor gave up: the keys are incomplete — nothing is selected
+    if (d4g_ld_agent(c.errors + 1) != 0) {   // a wait of the persistent executor gave up: the keys are incomplete — nothing is selected
         if (threadIdx.x == 0) {
             D4GRoundResult r;
             r.curSize = cur->sizeBits; r.bestSize = cur->sizeBits; r.bestSeq = -1; r.improved = -1; r.newType = cur->type; r.pad = 0;
@@ -1940,10 +1856,8 @@ __global__ void __launch_bounds__(256) k_select(D4GCtx c, D4GRoundResult* result
             if (c.hdrPrune[lane]) { wg_replace_rle_runs(&L, true); wg_recode_header(&L); }
             wg_optimise_header(&L);
             if (threadIdx.x == 0 && S->sizeBits != bestSize) {
-#ifdef D4G_HOSTSIM
-                fprintf(stderr, "select: header candidate op %d lane %d materialised to %lld bits (litlen %lld hdr %lld nPairs %d nCl %d nLit %d nDist %d), search said %lld; base size %lld litlen %lld hdr %lld type %d\n", opId, lane, (long long)S->sizeBits, (long long)S->litlenBits, (long long)S->hdrBits, S->nPairs, S->nCl, S->nLit, S->nDist, bestSize,
+                D4G_SIM_LOG("select: header candidate op %d lane %d materialised to %lld bits (litlen %lld hdr %lld nPairs %d nCl %d nLit %d nDist %d), search said %lld; base size %lld litlen %lld hdr %lld type %d\n", opId, lane, (long long)S->sizeBits, (long long)S->litlenBits, (long long)S->hdrBits, S->nPairs, S->nCl, S->nLit, S->nDist, bestSize,
                         (long long)state_ptr(c, blk, slot)->sizeBits, (long long)state_ptr(c, blk, slot)->litlenBits, (long long)state_ptr(c, blk, slot)->hdrBits, state_ptr(c, blk, slot)->type);
-#endif
                 atomicAdd(c.errors, 1);
             }
         }

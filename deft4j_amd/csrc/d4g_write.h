@@ -9,14 +9,6 @@
 #pragma once
 #include "d4g_ops.h"
 
-// LDS writes of a wave's lanes must be visible to its other lanes before they are read back (the LDS executes one wave's
-// operations in order; the barrier keeps the compiler from moving them across)
-#ifdef D4G_HOSTSIM
-#define D4G_WAVE_LDS_SYNC() ((void)__ballot(1))
-#else
-#define D4G_WAVE_LDS_SYNC() __builtin_amdgcn_wave_barrier()
-#endif
-
 struct D4GWriteJob {
     int32_t blk;        // block index (Huffman: its slot 0 is written; stored: only the data range is used)
     int32_t type;       // final type to write
@@ -205,9 +197,7 @@ __global__ void __launch_bounds__(1024) k_write(D4GCtx c, const D4GWriteJob* job
         __syncthreads();
         if (threadIdx.x == 0) {
             if (S->type == D4G_DYNAMIC && hdrTotal != 3 + S->hdrBits) {
-#ifdef D4G_HOSTSIM
-                fprintf(stderr, "write: header wrote %lld bits, state says %lld\n", hdrTotal - 3, (long long)S->hdrBits);
-#endif
+                D4G_SIM_LOG("write: header wrote %lld bits, state says %lld\n", hdrTotal - 3, (long long)S->hdrBits);
                 atomicAdd(c.errors, 1);
             }
             W.base = job.bitStart + hdrTotal;
@@ -260,7 +250,7 @@ __global__ void __launch_bounds__(1024) k_write(D4GCtx c, const D4GWriteJob* job
         const bool staged = nWords <= D4G_STAGE_WORDS;
         uint32_t* stg = W.stage[wave];
         if (staged) for (int k = lane; k < nWords + 2; k += 64) stg[k] = 0;
-        D4G_WAVE_LDS_SYNC();
+        d4g_wave_sync();
         const int rel = (int)(pos - (word0 << 5));
         uint64_t bits = 0;
         int n = 0;
@@ -295,7 +285,7 @@ __global__ void __launch_bounds__(1024) k_write(D4GCtx c, const D4GWriteJob* job
                 return true;
             });
         }
-        D4G_WAVE_LDS_SYNC();
+        d4g_wave_sync();
         if (staged) {
             const bool headShared = (wStart & 31) != 0, tailShared = ((wStart + wBits) & 31) != 0;
             for (int k = lane; k < nWords; k += 64) {
@@ -309,9 +299,7 @@ __global__ void __launch_bounds__(1024) k_write(D4GCtx c, const D4GWriteJob* job
         __syncthreads();
     }
     if (threadIdx.x == 0 && W.base != job.bitStart + 3 + S->sizeBits) {
-#ifdef D4G_HOSTSIM
-        fprintf(stderr, "write: block wrote %lld bits, state says %lld (type %d)\n", W.base - job.bitStart - 3, (long long)S->sizeBits, S->type);
-#endif
+        D4G_SIM_LOG("write: block wrote %lld bits, state says %lld (type %d)\n", W.base - job.bitStart - 3, (long long)S->sizeBits, S->type);
         atomicAdd(c.errors, 1);
     }
 }

@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(ZF_MATCH_THREADS) k_zf_match(const ZfInput* in
                 }
             }
         }
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         // entry: the change points of length >= 3
         int skip = 0;
         while (skip < ncp && (int)(cps[skip] >> 16) < 3) skip++;
@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(ZF_MATCH_THREADS) k_zf_match(const ZfInput* in
             ent[lane] = v;
         }
         if (lane == 0) job.best[pi] = best >= 3 ? (((uint32_t)best << 16) | (uint32_t)bestDist) : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
     }
 }
 
@@ -333,15 +333,15 @@ __global__ void __launch_bounds__(ZF_SORT_THREADS) k_zf_sort(const ZfInput* inpu
         const bool valid = i < nIns;
         const unsigned h = valid ? key[i] : 0u;
         const unsigned cur = valid ? vt[h] : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (valid) vt[h] = (uint16_t)(0x8000u | (unsigned)lane);
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         const unsigned w = valid ? vt[h] : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (valid && (w & 63u) != (unsigned)lane) vt[h] = (uint16_t)(0xC000u | (unsigned)lane);
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         const unsigned w2 = valid ? vt[h] : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         const bool dup = valid && (w2 & 0x4000u);
         unsigned rank = cur;
         if (valid && !dup) vt[h] = (uint16_t)(cur + 1);
@@ -356,7 +356,7 @@ __global__ void __launch_bounds__(ZF_SORT_THREADS) k_zf_sort(const ZfInput* inpu
             }
             rem &= ~m;
         }
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (valid) {
             Rout[i] = (uint16_t)rank;
             Sout[rank] = (uint16_t)i;
@@ -454,7 +454,7 @@ __global__ void __launch_bounds__(ZF_MS_THREADS) k_zf_match_sorted(const ZfInput
                 taken += 64;
             }
         }
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         int skip = 0;
         while (skip < ncp && (int)(cps[skip] >> 16) < 3) skip++;
         const int n3 = ncp - skip;
@@ -480,7 +480,7 @@ __global__ void __launch_bounds__(ZF_MS_THREADS) k_zf_match_sorted(const ZfInput
             ent[lane] = v;
         }
         if (lane == 0) job.best[pi] = best >= 3 ? (((uint32_t)best << 16) | (uint32_t)bestDist) : 0u;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
     }
 }
 
@@ -535,10 +535,10 @@ D4G_DEV uint32_t zf_greedy_walk(const ZfView& v, uint32_t* gb, uint16_t* oLit, u
     };
     for (long long i = v.start; i < v.end; i++) {
         if (i >= bbase + 256) {
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
             for (int k = lane; k < 256; k += 64) gb[k] = i + k < v.end ? zf_best(v, i + k) : 0u;
             bbase = i;
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
         }
         const uint32_t w = gb[i - bbase];
         int leng = (int)(w >> 16), dist = (int)(w & 0xffff);
@@ -600,7 +600,7 @@ D4G_DEV int zf_sort_leaves(const uint32_t* counts, int n, uint32_t* w, uint16_t*
     uint32_t* tc = tmp;
     uint32_t* ti = tmp + n;
     int nz = 0;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int base = 0; base < n; base += 64) {
         const int i = base + lane;
         const uint32_t c = i < n ? counts[i] : 0u;
@@ -612,7 +612,7 @@ D4G_DEV int zf_sort_leaves(const uint32_t* counts, int n, uint32_t* w, uint16_t*
         }
         nz += __popcll(m);
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int p = lane; p < nz; p += 64) {
         const uint32_t c = tc[p];
         int rank = 0;
@@ -620,7 +620,7 @@ D4G_DEV int zf_sort_leaves(const uint32_t* counts, int n, uint32_t* w, uint16_t*
         w[rank] = c;
         sym[rank] = (uint16_t)ti[p];
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     return nz;
 }
 // Package-merge, one lane: level l's list = leaves merged with the pairs of level l-1's list, a pair before a leaf of
@@ -678,17 +678,17 @@ D4G_DEV void zf_pm_wave(const ZfPmRef& r, int maxbits, uint8_t* out) {
     const int lane = threadIdx.x & 63;
     const int m = r.m;
     if (m == 0) return;
-    if (m <= 2) { if (lane < m) out[r.sym[lane]] = 1; LZ_WAVE_SYNC(); return; }
+    if (m <= 2) { if (lane < m) out[r.sym[lane]] = 1; d4g_wave_sync(); return; }
     const int mb = maxbits < m - 1 ? maxbits : m - 1;
     uint32_t* prev = r.list0;
     uint32_t* cur = r.list1;
     for (int i = lane; i < m; i += 64) prev[i] = r.w[i];
     int lenPrev = m;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int l = 1; l < mb; l++) {
         uint32_t* bits = r.bits + l * r.stride;
         for (int k = lane; k < r.stride; k += 64) bits[k] = 0;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         const int np = lenPrev >> 1;
         for (int i = lane; i < m; i += 64) {
             const uint32_t x = r.w[i];
@@ -706,7 +706,7 @@ D4G_DEV void zf_pm_wave(const ZfPmRef& r, int maxbits, uint8_t* out) {
         }
         lenPrev = m + np;
         uint32_t* t = prev; prev = cur; cur = t;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
     }
     int t = 2 * m - 2;
     for (int l = mb - 1; l >= 1; l--) {
@@ -722,13 +722,13 @@ D4G_DEV void zf_pm_wave(const ZfPmRef& r, int maxbits, uint8_t* out) {
         t = 2 * (t - a);
     }
     if (lane == 0) r.lvl[0] = t;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int q = lane; q < m; q += 64) {
         int len = 0;
         for (int l = 0; l < mb; l++) len += r.lvl[l] > q ? 1 : 0;
         out[r.sym[q]] = (uint8_t)len;
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
 }
 D4G_DEV void zf_patch_dist(uint8_t* d) {   // PatchDistanceCodesForBuggyDecoders
     int num = 0;
@@ -832,20 +832,20 @@ D4G_DEV long long zf_data_size(const uint32_t* llc, const uint32_t* dc, const ui
 // header's best use_16/17/18 combination in *combo, and returns tree size + data size.  All lanes of one wave.
 D4G_DEV long long zf_dynamic_lengths(ZfEvalLds& E, int* combo) {
     const int lane = threadIdx.x & 63;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int i = lane; i < ZF_NUM_LL; i += 64) { E.llc2[i] = E.llc[i]; E.ll[i] = 0; E.ll2[i] = 0; }
     if (lane < ZF_NUM_D) { E.dc2[lane] = E.dc[lane]; E.d[lane] = 0; E.d2[lane] = 0; }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     if (lane == 2) zf_optimize_rle(ZF_NUM_LL, E.llc2, E.good);
     if (lane == 3) zf_optimize_rle(ZF_NUM_D, E.dc2, E.goodD);
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     // two passes over one set of package-merge scratch: the plain counts' trees (lit/len on lane 0, distance on lane 1), then the
     // smoothed counts' (a second set would let all four run at once, but the scratch is what bounds the waves per CU)
     for (int pass = 0; pass < 2; pass++) {
         const int mBig = zf_sort_leaves(pass ? E.llc2 : E.llc, ZF_NUM_LL, E.u.pm.big[0].w, E.u.pm.big[0].sym, E.u.pm.big[0].list[1]);
         const int mSmall = zf_sort_leaves(pass ? E.dc2 : E.dc, ZF_NUM_D, E.u.pm.small[0].w, E.u.pm.small[0].sym, E.u.pm.small[0].list[1]);
-        LZ_WAVE_SYNC();
-#ifdef D4G_HOSTSIM
+        d4g_wave_sync();
+#ifdef D4G_SERIAL_TREES
         // (the CPU emulation keeps its test time down with the one-lane builder here; the wave-wide one is compared with the oracle
         // through d4g_debug_zopfli_code_lengths in the same test, and on the GPU every stream is)
         if (lane < 2) {
@@ -863,28 +863,28 @@ D4G_DEV long long zf_dynamic_lengths(ZfEvalLds& E, int* combo) {
             zf_pm_wave(rs, 15, pass ? E.d2 : E.d);
         }
 #endif
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     if (lane == 0) zf_patch_dist(E.d);
     if (lane == 1) zf_patch_dist(E.d2);
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     int ts = 0x7fffffff;
     if (lane < 16) {
         const bool second = lane >= 8;
         ts = zf_tree_size_one(second ? E.ll2 : E.ll, second ? E.d2 : E.d, lane & 7, E.u.cl[lane]);
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     int k1 = lane < 8 ? ((ts << 4) | lane) : 0x7fffffff, k2 = (lane >= 8 && lane < 16) ? ((ts << 4) | (lane & 7)) : 0x7fffffff;
     k1 = -wave_max_i32(-k1);
     k2 = -wave_max_i32(-k2);
     const long long d1 = zf_data_size(E.llc, E.dc, E.ll, E.d), d2 = zf_data_size(E.llc, E.dc, E.ll2, E.d2);
     const long long c1 = (k1 >> 4) + d1, c2 = (k2 >> 4) + d2;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     if (c2 < c1) {
         for (int i = lane; i < ZF_NUM_LL; i += 64) E.ll[i] = E.ll2[i];
         if (lane < ZF_NUM_D) E.d[lane] = E.d2[lane];
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (combo) *combo = k2 & 7;
         return c2;
     }
@@ -909,9 +909,9 @@ D4G_DEV void zf_block_costs(ZfEvalLds& E, long long byteLen, bool wantFixed, lon
         if (lane < 30) s += (long long)(5 + d4g_dsym_ebits(lane)) * E.dc[lane];
         fixedc = 3 + wave_sum_i64(s) + 7;
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     if (lane == 0) E.llc[256] = 1;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     dyn = 3 + zf_dynamic_lengths(E, combo);
 }
 // ZopfliCalculateBlockSizeAutoType: the fixed tree is only priced for stores of at most 1000 symbols
@@ -924,16 +924,16 @@ D4G_DEV long long zf_block_cost_auto(ZfEvalLds& E, long long byteLen, uint32_t s
 struct ZfStore { const uint16_t* lit; const uint16_t* dist; const uint32_t* pos; uint32_t size; };
 D4G_DEV void zf_count_range(ZfEvalLds& E, const ZfStore& s, uint32_t a, uint32_t b) {
     const int lane = threadIdx.x & 63;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int i = lane; i < ZF_NUM_LL; i += 64) E.llc[i] = 0;
     if (lane < ZF_NUM_D) E.dc[lane] = 0;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (uint32_t i = a + lane; i < b; i += 64) {
         const int dd = s.dist[i], l = s.lit[i];
         if (dd == 0) atomicAdd(&E.llc[l], 1u);
         else { atomicAdd(&E.llc[d4g_len2sym(l, 0)], 1u); atomicAdd(&E.dc[d4g_dist2sym(dd)], 1u); }
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
 }
 D4G_DEV long long zf_byte_range(const ZfStore& s, uint32_t a, uint32_t b) {   // ZopfliLZ77GetByteRange
     if (a == b) return 0;
@@ -1047,21 +1047,21 @@ __global__ void __launch_bounds__(ZF_SPLIT_WAVES * 64) k_zf_split(const ZfSplitJ
                 __syncthreads();
                 for (int pi = wave; pi < 9; pi += ZF_SPLIT_WAVES) {
                     const uint32_t at = L.p[pi];
-                    LZ_WAVE_SYNC();
+                    d4g_wave_sync();
                     for (int k = lane; k < NH; k += 64) {
                         uint32_t v = L.HL[k];
                         for (int g = 0; g <= pi; g++) v += L.seg[g][k];
                         if (k < ZF_NUM_LL) E.llc[k] = v; else E.dc[k - ZF_NUM_LL] = v;
                     }
-                    LZ_WAVE_SYNC();
+                    d4g_wave_sync();
                     long long v = zf_block_cost_auto(E, zf_byte_range(s, lstart, at), s.size);
-                    LZ_WAVE_SYNC();
+                    d4g_wave_sync();
                     for (int k = lane; k < NH; k += 64) {
                         uint32_t c = L.HR[k];
                         for (int g = pi + 1; g < 10; g++) c += L.seg[g][k];
                         if (k < ZF_NUM_LL) E.llc[k] = c; else E.dc[k - ZF_NUM_LL] = c;
                     }
-                    LZ_WAVE_SYNC();
+                    d4g_wave_sync();
                     v += zf_block_cost_auto(E, zf_byte_range(s, at, lend), s.size);
                     if (lane == 0) L.vp[pi] = v;
                 }
@@ -1193,10 +1193,10 @@ D4G_DEV void zf_calc_entropy(const uint32_t* count, int n, double* out) {   // Z
     }
 }
 D4G_DEV void zf_calc_stats(ZfSqLds& S) {
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     zf_calc_entropy(S.f, ZF_NUM_LL, S.llsym);
     zf_calc_entropy(S.f + ZF_NUM_LL, ZF_NUM_D, S.dsym);
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
 }
 struct ZfRan { uint32_t w, z; };
 D4G_DEV uint32_t zf_ran(ZfRan& r) {
@@ -1234,47 +1234,26 @@ D4G_DEV double zf_min_cost(const ZfSqLds& S, bool fixedModel) {   // GetCostMode
 // owns (the literal's and the match lengths'), and once per 64 positions the finished lengths are written out and the
 // registers shift.  Everything that does not depend on the running cost — the literal's cost, the change points with the
 // distance part of their cost, the long-run flag — is prepared for 64 positions at a time by all lanes.
-D4G_DEV uint32_t zf_rl(uint32_t v, int l) {
-#ifdef D4G_HOSTSIM
-    return __shfl(v, l);
-#else
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-#endif
-}
 D4G_DEV float zf_u2f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 D4G_DEV uint32_t zf_f2u(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 #define ZF_NQ 10
 // Change points of a position: up to eight match lengths (ascending, at most 258), two to a word; an unused place holds ZF_NOCP.
-// zf_count_below = how many of them are below k: both halves of a word at once with the packed 16-bit instructions (a place is
-// below k when place - k is negative; nothing overflows: every value is below 2^15).
+// zf_count_below (d4g_arch.h) = how many of them are below k.
 #define ZF_NOCP 0x7fffu
 #define ZF_NOCP2 0x7fff7fffu
-D4G_DEV int zf_count_below(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, int k) {
-#ifdef D4G_HOSTSIM
-    return ((int)(c0 & 0xffff) < k) + ((int)(c0 >> 16) < k) + ((int)(c1 & 0xffff) < k) + ((int)(c1 >> 16) < k) +
-           ((int)(c2 & 0xffff) < k) + ((int)(c2 >> 16) < k) + ((int)(c3 & 0xffff) < k) + ((int)(c3 >> 16) < k);
-#else
-    typedef short zf_s2 __attribute__((ext_vector_type(2)));
-    const zf_s2 kk = {(short)k, (short)k};
-    zf_s2 a, b, c, d;
-    __builtin_memcpy(&a, &c0, 4); __builtin_memcpy(&b, &c1, 4); __builtin_memcpy(&c, &c2, 4); __builtin_memcpy(&d, &c3, 4);
-    const zf_s2 t = ((a - kk) >> 15) + ((b - kk) >> 15) + ((c - kk) >> 15) + ((d - kk) >> 15);   // -1 per place below k
-    return -((int)t.x + (int)t.y);
-#endif
-}
 D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
     const ZfView& v = job.v;
     const int lane = threadIdx.x & 63;
     const long long start = v.start, end = v.end;
     const int size = (int)(end - start);
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int k = 3 + lane; k < 259; k += 64) {
         const int lsym = d4g_len2sym(k, 0), lb = d4g_lsym_ebits(lsym);
         S.lbTab[k] = (uint8_t)(fixedModel ? (lsym <= 279 ? 7 : 8) + 5 + lb : lb);
         S.llTab[k] = fixedModel ? 0.0 : S.llsym[lsym];
     }
     const double mincost = zf_min_cost(S, fixedModel);
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     if (lane == 0) job.lengthArray[0] = 0;
     float C[ZF_NQ];
     uint32_t Ln[ZF_NQ];
@@ -1296,7 +1275,7 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
             B += 64;
         }
         if (loaded != B) {
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
             const long long p = start + B + lane;
             rMeta = 0; rCl0 = rCl1 = rCl2 = rCl3 = ZF_NOCP2; rLitLo = rLitHi = 0;
             if (p < end) {
@@ -1326,7 +1305,7 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
                 rMeta = (zf_best(v, p) >> 16) | ((uint32_t)n << 16) | (fl ? 1u << 24 : 0u) | (n == 255 ? 1u << 25 : 0u);
             }
             loaded = B;
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
         }
         // the usual positions of this 64-block in a tight loop over registers 0..5: no long-run flag, at most eight change
         // points.  Anything else leaves the loop for the general code below.
@@ -1339,19 +1318,19 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
             for (int q = 0; q < 6; q++) { cr[q] = C[q]; lr[q] = Ln[q]; }
             const int oTight = oEnd < 63 ? oEnd : 63;
             for (; o < oTight; o++) {
-                const uint32_t meta = zf_rl(rMeta, o);
+                const uint32_t meta = d4g_readlane(rMeta, o);
                 if (__builtin_expect((meta >> 24) != 0u, 0)) break;
                 const int leng = (int)(meta & 0xffff);
                 const int kend = leng >= 3 ? (leng < size - B - o ? leng : size - B - o) : 0;
-                const double cj = (double)zf_u2f(zf_rl(zf_f2u(cr[0]), o));
-                const double ncLit = zf_u2d((unsigned long long)zf_rl(rLitLo, o) | ((unsigned long long)zf_rl(rLitHi, o) << 32)) + cj;
+                const double cj = (double)zf_u2f(d4g_readlane(zf_f2u(cr[0]), o));
+                const double ncLit = zf_u2d((unsigned long long)d4g_readlane(rLitLo, o) | ((unsigned long long)d4g_readlane(rLitHi, o) << 32)) + cj;
                 // the literal: index o + 1 sits in register 0 (position 63, whose literal lands in register 1, is left to the
                 // general code below).  The matches' targets are other lanes (k >= 3): register 0's costs as doubles serve both.
                 const double a0 = (double)cr[0];
                 if (lane == o + 1 && ncLit < a0) { cr[0] = (float)ncLit; lr[0] = 1; }
                 if (__builtin_expect(kend >= 3, 1)) {
                     const double mca = mincost + cj;
-                    const uint32_t c0 = zf_rl(rCl0, o), c1 = zf_rl(rCl1, o), c2 = zf_rl(rCl2, o), c3 = zf_rl(rCl3, o);
+                    const uint32_t c0 = d4g_readlane(rCl0, o), c1 = d4g_readlane(rCl1, o), c2 = d4g_readlane(rCl2, o), c3 = d4g_readlane(rCl3, o);
                     auto relax = [&](int q, float& crq, uint32_t& lrq) D4G_LAMBDA_INLINE {
                         const int k = 64 * q + lane - o;
                         const double cq = q == 0 ? a0 : (double)crq;
@@ -1381,7 +1360,7 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
             if (o >= oEnd) continue;
         }
         const int o = j - B;
-        const uint32_t meta = zf_rl(rMeta, o);
+        const uint32_t meta = d4g_readlane(rMeta, o);
         if (((meta >> 24) & 1u) && !afterShortcut) {
             // inside a long run of one byte: 258 positions take a 258-byte match at distance 1 without searching.
             // index t = s + 258 takes cost[s] + c for the 258 sources s = j .. j + 257: (q, L) <- (q - 4, L - 2) or (q - 5, L + 62)
@@ -1400,8 +1379,8 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
         }
         afterShortcut = false;
         const int leng = (int)(meta & 0xffff), ncp = (int)((meta >> 16) & 0xff);
-        const double cj = (double)zf_u2f(zf_rl(zf_f2u(C[0]), o));
-        const double ncLit = zf_u2d((unsigned long long)zf_rl(rLitLo, o) | ((unsigned long long)zf_rl(rLitHi, o) << 32)) + cj;
+        const double cj = (double)zf_u2f(d4g_readlane(zf_f2u(C[0]), o));
+        const double ncLit = zf_u2d((unsigned long long)d4g_readlane(rLitLo, o) | ((unsigned long long)d4g_readlane(rLitHi, o) << 32)) + cj;
         const int kend = leng >= 3 ? (leng < size - j ? leng : size - j) : 0;
         const double mca = mincost + cj;
         {   // the literal: index o + 1 sits in register 0, or in register 1 when o == 63
@@ -1412,7 +1391,7 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
         if (kend >= 3) {
             if (__builtin_expect(ncp != 255 && o + kend < 128, 1)) {
                 // the usual case: at most eight change points, targets within registers 0 and 1
-                const uint32_t c0 = zf_rl(rCl0, o), c1 = zf_rl(rCl1, o), c2 = zf_rl(rCl2, o), c3 = zf_rl(rCl3, o);
+                const uint32_t c0 = d4g_readlane(rCl0, o), c1 = d4g_readlane(rCl1, o), c2 = d4g_readlane(rCl2, o), c3 = d4g_readlane(rCl3, o);
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
                     if (q == 0 || o + kend >= 64) {
@@ -1431,7 +1410,7 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
             } else {
                 const int qmax = (o + kend) >> 6;
                 uint32_t c0 = ZF_NOCP2, c1 = ZF_NOCP2, c2 = ZF_NOCP2, c3 = ZF_NOCP2;
-                if (ncp != 255) { c0 = zf_rl(rCl0, o); c1 = zf_rl(rCl1, o); c2 = zf_rl(rCl2, o); c3 = zf_rl(rCl3, o); }
+                if (ncp != 255) { c0 = d4g_readlane(rCl0, o); c1 = d4g_readlane(rCl1, o); c2 = d4g_readlane(rCl2, o); c3 = d4g_readlane(rCl3, o); }
 #pragma unroll
                 for (int q = 0; q < 6; q++) {
                     if (q <= qmax) {
@@ -1463,7 +1442,7 @@ D4G_DEV void zf_best_lengths(ZfSqLds& S, const ZfSqJob& job, bool fixedModel) {
         for (int q = 0; q + 1 < ZF_NQ; q++) { C[q] = C[q + 1]; Ln[q] = Ln[q + 1]; }
         B += 64;
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
 }
 
 // TraceBackwards + FollowPath: walk lengthArray back from the end (lane 0, through an LDS window), then look every
@@ -1479,9 +1458,9 @@ D4G_DEV uint32_t zf_trace_follow(ZfSqLds& S, const ZfSqJob& job, int buf) {
     const long long cap = size;
     while (idx > 0) {
         const long long base = idx > 4095 ? idx - 4095 : 0;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         for (long long k = lane; k <= idx - base; k += 64) S.E.u.chunk[k] = job.lengthArray[base + k];
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (lane == 0) {
             while (idx > 0 && idx >= base) {
                 const int l = S.E.u.chunk[idx - base];
@@ -1494,10 +1473,10 @@ D4G_DEV uint32_t zf_trace_follow(ZfSqLds& S, const ZfSqJob& job, int buf) {
         npath = __shfl(npath, 0);
     }
     __threadfence();
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     for (int i = lane; i < ZF_NUM_LL; i += 64) S.E.llc[i] = 0;
     if (lane < ZF_NUM_D) S.E.dc[lane] = 0;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     uint16_t* oLit = buf ? job.lit[1] : job.lit[0];       // (no dynamic indexing: it would pin the whole job struct in scratch memory)
     uint16_t* oDist = buf ? job.dist[1] : job.dist[0];
     uint32_t* oPos = buf ? job.pos[1] : job.pos[0];
@@ -1512,7 +1491,7 @@ D4G_DEV uint32_t zf_trace_follow(ZfSqLds& S, const ZfSqJob& job, int buf) {
         if (dist == 0) atomicAdd(&S.E.llc[litlen], 1u);
         else { atomicAdd(&S.E.llc[d4g_len2sym(litlen, 0)], 1u); atomicAdd(&S.E.dc[d4g_dist2sym(dist)], 1u); }
     }
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     return npath;
 }
 
@@ -1527,21 +1506,16 @@ __global__ void __launch_bounds__(64) k_zf_squeeze(const ZfSqJob* __restrict__ j
         if (lane == 0) outs[blockIdx.x] = {0, n, 0, {0, 0, 0, 0, 0, 0}};
         return;
     }
-#ifdef D4G_HOSTSIM
-#define ZF_CLOCK() 0LL
-#else
-#define ZF_CLOCK() (long long)wall_clock64()
-#endif
     long long cyc[6] = {0, 0, 0, 0, 0, 0};
-    long long tc = ZF_CLOCK(), tn;
+    long long tc = d4g_wall_clock(), tn;
     // first statistics: the greedy parse
     for (int k = lane; k < NH; k += 64) S.f[k] = 0;
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     zf_greedy_walk<false>(job.v, (uint32_t*)S.E.u.chunk, nullptr, nullptr, nullptr, S.f);
-    LZ_WAVE_SYNC();
+    d4g_wave_sync();
     if (lane == 0) S.f[256] = 1;
     zf_calc_stats(S);
-    tn = ZF_CLOCK(); cyc[0] += tn - tc; tc = tn;
+    tn = d4g_wall_clock(); cyc[0] += tn - tc; tc = tn;
     for (int k = lane; k < NH; k += 64) S.fbest[k] = 0;
     ZfRan ran = {1, 2};
     int cur = 0, bestBuf = 0, lastrandomstep = -1;
@@ -1549,14 +1523,14 @@ __global__ void __launch_bounds__(64) k_zf_squeeze(const ZfSqJob* __restrict__ j
     long long bestcost = 0x7fffffffffffffffLL, lastcost = 0;
     for (int it = 0; it < job.iterations; it++) {
         zf_best_lengths(S, job, false);
-        tn = ZF_CLOCK(); cyc[1] += tn - tc; tc = tn;
+        tn = d4g_wall_clock(); cyc[1] += tn - tc; tc = tn;
         const uint32_t n = zf_trace_follow(S, job, cur);
-        tn = ZF_CLOCK(); cyc[2] += tn - tc; tc = tn;
+        tn = d4g_wall_clock(); cyc[2] += tn - tc; tc = tn;
         if (lane == 0) S.E.llc[256] = 1;
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         const long long cost = 3 + zf_dynamic_lengths(S.E, nullptr);
-        LZ_WAVE_SYNC();
-        tn = ZF_CLOCK(); cyc[3] += tn - tc; tc = tn;
+        d4g_wave_sync();
+        tn = d4g_wall_clock(); cyc[3] += tn - tc; tc = tn;
         if (cost < bestcost) {
             for (int k = lane; k < NH; k += 64) S.fbest[k] = S.f[k];
             bestBuf = cur; bestSize = n; bestcost = cost;
@@ -1569,13 +1543,13 @@ __global__ void __launch_bounds__(64) k_zf_squeeze(const ZfSqJob* __restrict__ j
         zf_calc_stats(S);
         if (lastrandomstep != -1) {
             for (int k = lane; k < NH; k += 64) S.f[k] = (uint32_t)((double)S.f[k] * 1.0 + (double)S.flast[k] * 0.5);
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
             if (lane == 0) S.f[256] = 1;
             zf_calc_stats(S);
         }
         if (it > 5 && cost == lastcost) {
             for (int k = lane; k < NH; k += 64) S.f[k] = S.fbest[k];
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
             if (lane == 0) {
                 for (int i = 0; i < ZF_NUM_LL; i++) if ((zf_ran(ran) >> 4) % 3 == 0) S.f[i] = S.f[zf_ran(ran) % ZF_NUM_LL];
                 for (int i = 0; i < ZF_NUM_D; i++) if ((zf_ran(ran) >> 4) % 3 == 0) S.f[ZF_NUM_LL + i] = S.f[ZF_NUM_LL + zf_ran(ran) % ZF_NUM_D];
@@ -1587,7 +1561,7 @@ __global__ void __launch_bounds__(64) k_zf_squeeze(const ZfSqJob* __restrict__ j
             lastrandomstep = it;
         }
         lastcost = cost;
-        tn = ZF_CLOCK(); cyc[4] += tn - tc; tc = tn;
+        tn = d4g_wall_clock(); cyc[4] += tn - tc; tc = tn;
     }
     if (lane == 0) outs[blockIdx.x] = {bestBuf, bestSize, bestcost, {cyc[0], cyc[1], cyc[2], cyc[3], cyc[4], 0}};
 }
@@ -1654,7 +1628,7 @@ __global__ void __launch_bounds__(256) k_zf_emit(const ZfEmitJob* jobs) {
         if (job.btype == 2) {
             zf_count_range(L.E, job.s, job.a, job.b);
             if (lane == 0) L.E.llc[256] = 1;
-            LZ_WAVE_SYNC();
+            d4g_wave_sync();
             zf_dynamic_lengths(L.E, &combo);
             for (int i = lane; i < ZF_NUM_LL; i += 64) L.ll[i] = L.E.ll[i];
             if (lane < ZF_NUM_D) L.d[lane] = L.E.d[lane];
@@ -1662,7 +1636,7 @@ __global__ void __launch_bounds__(256) k_zf_emit(const ZfEmitJob* jobs) {
             for (int i = lane; i < ZF_NUM_LL; i += 64) L.ll[i] = i < 144 ? 8 : (i < 256 ? 9 : (i < 280 ? 7 : 8));
             if (lane < ZF_NUM_D) L.d[lane] = 5;
         }
-        LZ_WAVE_SYNC();
+        d4g_wave_sync();
         if (lane == 0) zf_codes(L.ll, ZF_NUM_LL, L.llcode);
         if (lane == 1) zf_codes(L.d, ZF_NUM_D, L.dcode);
         if (lane == 0) {
