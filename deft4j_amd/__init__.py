@@ -37,7 +37,8 @@ class d4g_stats(ctypes.Structure):
                 ("recompress_outputs", ctypes.c_int64), ("recompress_outputs_pruned", ctypes.c_int64),
                 ("ms_zopfli_table", ctypes.c_double), ("ms_zopfli_split", ctypes.c_double), ("ms_zopfli_squeeze", ctypes.c_double),
                 ("ms_zopfli_emit", ctypes.c_double), ("zopfli_blocks", ctypes.c_int64), ("zopfli_position_iterations", ctypes.c_int64),
-                ("rounds_fused", ctypes.c_int64), ("fused_fallbacks", ctypes.c_int64), ("persist_fallbacks", ctypes.c_int64), ("rounds_cluster", ctypes.c_int64)]
+                ("rounds_fused", ctypes.c_int64), ("fused_fallbacks", ctypes.c_int64), ("persist_fallbacks", ctypes.c_int64), ("rounds_cluster", ctypes.c_int64),
+                ("ms_verify", ctypes.c_double), ("ms_verify_kernels", ctypes.c_double), ("verify_streams", ctypes.c_int64), ("verify_bytes", ctypes.c_int64)]
 
 
 class d4g_encoder_spec(ctypes.Structure):
@@ -48,6 +49,15 @@ class d4g_encoder_spec_level(ctypes.Structure):
     _fields_ = [("input", ctypes.c_int32), ("encoder", ctypes.c_int32), ("strategy", ctypes.c_int32), ("level", ctypes.c_int32)]
 
 
+class d4g_block_info(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int32), ("bfinal", ctypes.c_int32)] + \
+               [(n, ctypes.c_int64) for n in ("bit_pos", "size_bits", "header_bits", "tokens", "decoded_len")]
+
+
+VERIFY_OK, VERIFY_SKIPPED, VERIFY_PARSE, VERIFY_SIZE, VERIFY_LENGTH, VERIFY_BYTES = 0, 1, -1, -2, -3, -4     # D4G_VERIFY_*
+VERDICT_NAMES = {0: "OK", 1: "SKIPPED", -1: "PARSE", -2: "SIZE", -3: "LENGTH", -4: "BYTES"}
+BLOCK_TYPE_NAMES = ("STORED", "FIXED", "DYNAMIC")           # DeflateBlockType, as printBlockInfo prints it
+
 ENC_JVM, ENC_JZLIB = 0, 1                                   # D4G_ENC_*: JavaCompressor / JZLibCompressor
 STRATEGY_DEFAULT, STRATEGY_FILTERED, STRATEGY_HUFFMAN_ONLY = 0, 1, 2
 STRATEGY_RLE, STRATEGY_FIXED = 3, 4                         # zlib's Z_RLE / Z_FIXED (the level entry points only)
@@ -57,7 +67,8 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_size_bits_fallback", "d4g_inflate", "d4g_free", "d4g_batch_create_encode", "d4g_batch_run_encode", "d4g_deflate_streams",
            "d4g_compress", "d4g_recompress_streams", "d4g_batch_run_recompress", "d4g_batch_recompress_result", "d4g_zopfli_streams",
            "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
-           "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level"]
+           "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
+           "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare"]
 
 
 def load_library(path=None):
@@ -151,6 +162,20 @@ def load_library(path=None):
     L.d4g_batch_create_on.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t)]
     L.d4g_optimise_streams_sharded.restype = ctypes.c_int
     L.d4g_optimise_streams_sharded.argtypes = L.d4g_optimise_streams.argtypes
+    L.d4g_batch_verify.restype = ctypes.c_int
+    L.d4g_batch_verify.argtypes = [ctypes.c_void_p]
+    L.d4g_batch_verify_result.restype = ctypes.c_int
+    L.d4g_batch_verify_result.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]
+    L.d4g_verify_streams.restype = ctypes.c_int
+    L.d4g_verify_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_char_p),
+                                     ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]
+    L.d4g_debug_batch_poke_output.restype = ctypes.c_int
+    L.d4g_debug_batch_poke_output.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint8]
+    L.d4g_debug_verify_compare.restype = ctypes.c_int
+    L.d4g_debug_verify_compare.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)]
+    L.d4g_batch_block_info.restype = ctypes.c_int
+    L.d4g_batch_block_info.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(d4g_block_info), ctypes.c_size_t,
+                                       ctypes.POINTER(ctypes.c_size_t)]
     if path is None:
         _lib = L
     return L
@@ -300,6 +325,50 @@ class Batch:
             raise RuntimeError(self.L.d4g_last_error().decode())
         return c.value, a.value, n.value
 
+    def verify(self):
+        """d4g_batch_verify: every stream the library wrote is parsed again in HBM and its decoded bytes compared on the device
+        with the input's.  -> list of {"verdict", "first_mismatch"} (VERIFY_*; see include/deft4g.h)."""
+        rc = self.L.d4g_batch_verify(self.h)
+        if rc != 0:
+            raise RuntimeError("d4g_batch_verify: " + self.L.d4g_last_error().decode())
+        res = []
+        for i in range(self.n):
+            v = ctypes.c_int32()
+            f = ctypes.c_int64()
+            if self.L.d4g_batch_verify_result(self.h, i, ctypes.byref(v), ctypes.byref(f)) != 0:
+                raise RuntimeError(self.L.d4g_last_error().decode())
+            res.append({"verdict": v.value, "first_mismatch": f.value})
+        return res
+
+    def block_info(self, i, final=False):
+        """d4g_batch_block_info -> list of dict(type, bfinal, bit_pos, size_bits, header_bits, tokens, decoded_len), positions and
+        sizes as DeflateStream.printBlockInfo counts them."""
+        n = ctypes.c_size_t()
+        rc = self.L.d4g_batch_block_info(self.h, i, 1 if final else 0, None, 0, ctypes.byref(n))
+        if rc != 0:
+            raise RuntimeError("d4g_batch_block_info: " + self.L.d4g_last_error().decode())
+        arr = (d4g_block_info * max(1, n.value))()
+        rc = self.L.d4g_batch_block_info(self.h, i, 1 if final else 0, arr, n.value, ctypes.byref(n))
+        if rc != 0:
+            raise RuntimeError("d4g_batch_block_info: " + self.L.d4g_last_error().decode())
+        return [{k: getattr(arr[j], k) for k, _ in d4g_block_info._fields_} for j in range(n.value)]
+
+    def locate(self, i, offset, final=True):
+        """Decoded byte `offset` of stream i -> (block index, byte within that block), by the stream's block list."""
+        at = 0
+        blocks = self.block_info(i, final)
+        for k, b in enumerate(blocks):
+            if offset < at + b["decoded_len"]:
+                return k, offset - at
+            at += b["decoded_len"]
+        return len(blocks), offset - at
+
+    def poke_output(self, i, byte_offset, xor_mask):
+        """Test hook (d4g_debug_batch_poke_output): flips bits of stream i's final output in HBM."""
+        rc = self.L.d4g_debug_batch_poke_output(self.h, i, byte_offset, xor_mask)
+        if rc != 0:
+            raise RuntimeError("d4g_debug_batch_poke_output: " + self.L.d4g_last_error().decode())
+
     def stats(self):
         st = d4g_stats()
         self.L.d4g_batch_stats(self.h, ctypes.byref(st))
@@ -370,6 +439,26 @@ def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None
         res.append(ctypes.string_at(out[i], olen[i]))
         L.d4g_free(out[i])
     return res
+
+
+def verify_streams(a, b, lib=None):
+    """d4g_verify_streams: do the raw DEFLATE streams a[i] and b[i] decode to the same bytes?  Both sides are parsed and
+    compared on the device.  -> list of {"verdict", "first_mismatch"}."""
+    L = lib or _need()
+    n = len(a)
+    if len(b) != n:
+        raise ValueError("verify_streams: two lists of the same length")
+    ka, kb = [bytes(s) for s in a], [bytes(s) for s in b]
+    arr_a = (ctypes.c_char_p * max(1, n))(*ka)
+    len_a = (ctypes.c_size_t * max(1, n))(*[len(s) for s in ka])
+    arr_b = (ctypes.c_char_p * max(1, n))(*kb)
+    len_b = (ctypes.c_size_t * max(1, n))(*[len(s) for s in kb])
+    v = (ctypes.c_int32 * max(1, n))()
+    f = (ctypes.c_int64 * max(1, n))()
+    rc = L.d4g_verify_streams(n, arr_a, len_a, arr_b, len_b, v, f)
+    if rc != 0:
+        raise RuntimeError("d4g_verify_streams: " + L.d4g_last_error().decode())
+    return [{"verdict": v[i], "first_mismatch": f[i]} for i in range(n)]
 
 
 ZOPFLI_SPLIT_FIRST, ZOPFLI_SPLIT_LAST, ZOPFLI_SPLIT_NONE = 0, 1, 2     # Options.BlockSplitting (CafeUndZopfli) / blocksplitting[last] (jzopfli)
@@ -516,6 +605,23 @@ class DeflateStream:
 
     def getUncompressedData(self):
         return self._parsed
+
+    def printBlockInfo(self):
+        """DeflateStream.printBlockInfo (:35-51): the reference's text, for the stream as it stands (after optimise(): the
+        optimised stream)."""
+        b, own = self._batch, False
+        if b is None:
+            if self._parsed is None:
+                raise RuntimeError("printBlockInfo() on a stream that did not parse")
+            b, own = Batch([self._data], lib=self._lib).parse(), True
+        try:
+            info = b.block_info(0, final=not own)
+        finally:
+            if own:
+                b.close()
+        lines = "".join("\nBlock %d position %d size %d type %s" % (k, bi["bit_pos"], bi["size_bits"], BLOCK_TYPE_NAMES[bi["type"]])
+                        for k, bi in enumerate(info))
+        return "Stream name: " + self.name + "\nBlock info:" + lines + "\nTotal blocks: %d" % len(info)
 
     def getSizeBits(self):
         if self._batch is not None:

@@ -365,12 +365,14 @@ def detect(data):
     return None
 
 
-def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0):
+def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, verify=False):
     """files: list of bytes.  formats: optional list of container instances / None (auto-detect) / "raw".
     mode: RecompressMode ordinal of `deft4j optimise --mode` (0 NONE, 1 CHEAP, 2 ZOPFLI, 3 ZOPFLI_EXTENSIVE, 4 ZOPFLI_VERY_EXTENSIVE; M/CMDUtil.java:44-50,76-105): above NONE every
     stream is also recompressed and the recompression grafted in where it is smaller.
     Returns [(output bytes or None when unreadable, transcript lines)] — the lines M/CMDUtil.java:64-74 and
-    K/DeflateFilesContainer.java:31-40 print.  Every deflate stream of every file goes to the GPU in one batch."""
+    K/DeflateFilesContainer.java:31-40 print.  Every deflate stream of every file goes to the GPU in one batch.
+    verify: before any file is assembled, every rewritten stream is parsed again on the device and its decoded bytes compared
+    with the original's (Batch.verify); a stream that fails raises RuntimeError naming file, stream, block and offset."""
     conts = []
     for i, f in enumerate(files):
         c = formats[i] if formats and formats[i] is not None else None
@@ -392,6 +394,17 @@ def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0):
     if payloads:
         batch = Batch(payloads, lib=lib)
         batch.run_recompress(mode, merge_blocks) if mode > 0 else batch.run(merge_blocks)
+        if verify:
+            from . import VERDICT_NAMES
+            for q, v in enumerate(batch.verify()):
+                if v["verdict"] < 0:
+                    where = ""
+                    if v["first_mismatch"] >= 0:
+                        blk, byte = batch.locate(q, v["first_mismatch"], final=False)
+                        where = ", decoded byte %d (block %d of the original, byte %d of that block)" % (v["first_mismatch"], blk, byte)
+                    batch.close()
+                    raise RuntimeError("verification failed: file %d, stream %d (%s): verdict %s%s"
+                                       % (owner[q][0], q, owner[q][1], VERDICT_NAMES[v["verdict"]], where))
     results = [(None, ["Failed to read file"]) for _ in files]
     k = 0
     for i, c in enumerate(conts):

@@ -114,6 +114,24 @@ D4G_DEV int wave_sum_i32(int v) {
 #endif
 }
 
+// 32-bit unsigned wave minimum on the same DPP path (lanes a shift does not reach keep the identity ~0u)
+D4G_DEV uint32_t wave_min_u32(uint32_t v) {
+#ifdef D4G_HOSTSIM
+    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m); v = o < v ? o : v; }
+    return v;
+#else
+    int x = (int)v;
+    auto step = [&](int o) { x = (int)((uint32_t)o < (uint32_t)x ? (uint32_t)o : (uint32_t)x); };
+    step(__builtin_amdgcn_update_dpp(-1, x, 0x111, 0xf, 0xf, false));  // row_shr:1
+    step(__builtin_amdgcn_update_dpp(-1, x, 0x112, 0xf, 0xf, false));  // row_shr:2
+    step(__builtin_amdgcn_update_dpp(-1, x, 0x114, 0xf, 0xf, false));  // row_shr:4
+    step(__builtin_amdgcn_update_dpp(-1, x, 0x118, 0xf, 0xf, false));  // row_shr:8
+    step(__builtin_amdgcn_update_dpp(-1, x, 0x142, 0xa, 0xf, false));  // row_bcast:15 into rows 1 and 3
+    step(__builtin_amdgcn_update_dpp(-1, x, 0x143, 0xc, 0xf, false));  // row_bcast:31 into rows 2 and 3
+    return (uint32_t)__builtin_amdgcn_readlane(x, 63);
+#endif
+}
+
 // The value held by the lane 2^(5-D) away (the path-per-lane queue of d4g_device.h)
 template <int D> D4G_DEV unsigned d4g_rp_sibling(unsigned v) {
 #ifdef D4G_HOSTSIM
@@ -145,6 +163,15 @@ D4G_DEV unsigned long long d4g_spread_bits(unsigned x) {
     unsigned long long o;
     asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(o) : "s"(x));   // every bit doubled
     return o & 0x5555555555555555ull;
+#endif
+}
+
+// Byte funnel shift: the 32 bits that start sh (0..3) bytes into the little-endian pair lo, hi (v_alignbyte_b32)
+D4G_DEV uint32_t d4g_alignbyte(uint32_t hi, uint32_t lo, int sh) {
+#ifdef D4G_HOSTSIM
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (sh & 3)));
+#else
+    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)sh);
 #endif
 }
 

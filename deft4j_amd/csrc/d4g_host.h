@@ -649,7 +649,7 @@ struct Batch {
     }
 
     // ---- parse: header scan -> block probes -> chain -> emit -> pointer jumping ----
-    struct PBlock { int type, bfinal; i64 bitPos, endBit, nTok, uLen, sizeBits, nRef; int firstBatch; i64 refSpan = -1; };   // refSpan: records the block occupies in refs even when it is STORED (LZ77 front end)
+    struct PBlock { int type, bfinal; i64 bitPos, endBit, nTok, uLen, sizeBits, nRef; int firstBatch; i64 refSpan = -1; i64 hdrBits = 0; };   // refSpan: records the block occupies in refs even when it is STORED (LZ77 front end)
     struct PStream { int status = 0; std::vector<PBlock> blocks; i64 nTok = 0, nU = 0, consumed = 0, sizeBits = 0; i64 uBaseFixed = -1; };   // uBaseFixed: the decoded bytes already sit in U (LZ77 front end: the raw input)
     std::vector<PStream> ps;
     D4GStreamDesc* dStreams = nullptr;
@@ -742,7 +742,7 @@ struct Batch {
         auto accept = [&](size_t i, i64 bitPos, const D4GProbeOut& o, bool fromScan) {
             PStream& P = ps[i];
             if (o.status != 0 || o.needHist > upos[i]) { P.status = -1; done[i] = 1; return; }
-            P.blocks.push_back({o.type, o.bfinal, bitPos, o.endBit, o.nTok, o.uLen, o.sizeBits, (i64)o.nRef, fromScan ? o.firstBatch : -1});
+            P.blocks.push_back({o.type, o.bfinal, bitPos, o.endBit, o.nTok, o.uLen, o.sizeBits, (i64)o.nRef, fromScan ? o.firstBatch : -1, -1, (i64)o.hdrBits});
             upos[i] += o.uLen;
             P.nTok += o.nTok;
             spos[i] += 3;  // DeflateStream.getSizeBits — :171-182
@@ -1848,5 +1848,80 @@ struct Batch {
         rt_free(dHeads); dHeads = nullptr;
     }
 };
+
+// ---- round-trip verification: the one routine behind d4g_batch_verify, d4g_verify_streams and D4G_VERIFY=1 ----
+// An item is (a raw DEFLATE stream, the bytes it must decode to); both live in device memory unless `bytesOnHost`, where
+// the stream bytes come from the caller's arrays.  The streams go through the ordinary parse path as one batch of their
+// own, then k_verify_compare walks the common prefix of every pair; no decoded byte goes through the host.
+enum { VERIFY_OK = 0, VERIFY_SKIPPED = 1, VERIFY_PARSE = -1, VERIFY_SIZE = -2, VERIFY_LENGTH = -3, VERIFY_BYTES = -4 };
+struct VerifyItem {
+    const uint8_t* bytes = nullptr;   // the stream
+    size_t len = 0;
+    const uint8_t* want = nullptr;    // expected decoded bytes (device)
+    i64 wantLen = 0;
+    i64 wantBits = -1;                // >= 0: the parse must read exactly `len` bytes and this many bits
+    int verdict = VERIFY_SKIPPED;
+    i64 first = -1;
+    std::vector<Batch::PBlock> blocks;   // the stream's block list as parsed (empty when it does not parse)
+};
+struct VerifyTotals { double ms = 0, msKernels = 0; i64 streams = 0, bytes = 0; };
+
+inline void verify_items(std::vector<VerifyItem>& items, bool bytesOnHost, VerifyTotals& T) {
+    const size_t n = items.size();
+    if (!n) return;
+    const double t0 = now_ms();
+    std::vector<const uint8_t*> p(n);
+    std::vector<size_t> l(n);
+    for (size_t i = 0; i < n; i++) { p[i] = items[i].bytes; l[i] = items[i].len; }
+    Batch V;
+    V.create(n, p.data(), l.data(), !bytesOnHost);
+    engine().init();
+    V.parse_probe();
+    V.build_blocks(false, false);
+    std::vector<D4GVerifyPair> pairs;
+    std::vector<size_t> owner;
+    std::vector<long long> base(1, 0);
+    for (size_t i = 0; i < n; i++) {
+        VerifyItem& it = items[i];
+        const Batch::PStream& P = V.ps[i];
+        it.first = -1;
+        if (P.status != 0) { it.verdict = VERIFY_PARSE; continue; }
+        it.blocks = P.blocks;
+        if (it.wantBits >= 0 && (P.consumed != (i64)it.len || P.sizeBits != it.wantBits)) { it.verdict = VERIFY_SIZE; continue; }
+        it.verdict = VERIFY_OK;
+        const i64 common = std::min(P.nU, it.wantLen);
+        T.bytes += common;
+        if (common <= 0) continue;
+        pairs.push_back({V.dU + V.streams[i].uBase, it.want, common});
+        owner.push_back(i);
+        base.push_back(base.back() + (common + D4G_CSUM_TILE - 1) / D4G_CSUM_TILE);
+    }
+    T.streams += (i64)n;
+    T.msKernels += V.msParseKernels;
+    std::vector<unsigned long long> first(pairs.size(), D4G_VERIFY_NONE);
+    if (!pairs.empty()) {
+        const size_t np = pairs.size();
+        D4GVerifyPair* dPairs = (D4GVerifyPair*)rt_malloc(np * sizeof(D4GVerifyPair));
+        long long* dBase = (long long*)rt_malloc((np + 1) * 8);
+        unsigned long long* dFirst = (unsigned long long*)rt_malloc(np * 8);
+        rt_h2d(dPairs, pairs.data(), np * sizeof(D4GVerifyPair));
+        rt_h2d(dBase, base.data(), (np + 1) * 8);
+        rt_memset(dFirst, 0xff, np * 8);
+        RtEvent e0, e1;
+        e0.record();
+        RT_LAUNCH(k_verify_compare, base[np], 256, dPairs, dBase, (int)np, dFirst);
+        e1.record();
+        rt_d2h(first.data(), dFirst, np * 8);
+        T.msKernels += rt_elapsed_ms(e0, e1);
+        rt_free(dPairs); rt_free(dBase); rt_free(dFirst);
+    }
+    for (size_t k = 0; k < pairs.size(); k++)
+        if (first[k] != D4G_VERIFY_NONE) { items[owner[k]].verdict = VERIFY_BYTES; items[owner[k]].first = (i64)first[k]; }
+    for (size_t i = 0; i < n; i++) {   // bytes win over length: a difference inside the common prefix is reported as such
+        VerifyItem& it = items[i];
+        if (it.verdict == VERIFY_OK && V.ps[i].nU != it.wantLen) { it.verdict = VERIFY_LENGTH; it.first = std::min(V.ps[i].nU, it.wantLen); }
+    }
+    T.ms += now_ms() - t0;
+}
 
 }  // namespace d4g

@@ -775,7 +775,7 @@ __global__ void __launch_bounds__(64) k_lz_fill(LzCtx c, const LzOutStream* outs
 // overflow repair, scan_tree, the stored / fixed / dynamic choice of _tr_flush_block, and the block's D4GState.
 // One wave per block; the tree construction itself is sequential work on lane 0's scalar path.
 // ---------------------------------------------------------------------------------------------------------------------
-struct LzBlockOut { int32_t type; int32_t pad; long long sizeBits; long long optLen, staticLen; };
+struct LzBlockOut { int32_t type; int32_t hdrBits; long long sizeBits; long long optLen, staticLen; };
 
 #define LZ_HEAP 573
 struct LzTreeLds {
@@ -1005,7 +1005,7 @@ __global__ void __launch_bounds__(64) k_lz_blocks(const LzStream* streams, const
         S.valid = 1;
         S.maskSlot = 0;
         res[blockIdx.x].type = type;
-        res[blockIdx.x].pad = 0;
+        res[blockIdx.x].hdrBits = type == D4G_DYNAMIC ? (int32_t)S.hdrBits : 0;
         res[blockIdx.x].sizeBits = S.sizeBits;
         res[blockIdx.x].optLen = T.optLen;
         res[blockIdx.x].staticLen = T.staticLen;

@@ -436,6 +436,7 @@ struct LzFront {
                 pb.type = r.type; pb.bfinal = d.isLast; pb.bitPos = 0; pb.endBit = 0;
                 pb.nTok = d.symCount + 1; pb.uLen = d.uLen; pb.sizeBits = r.sizeBits; pb.nRef = d.refCount; pb.firstBatch = -1;
                 pb.refSpan = d.refCount;
+                    pb.hdrBits = r.hdrBits;
                 P.blocks.push_back(pb);
                 P.nTok += pb.nTok;
                 spos += 3;

@@ -46,6 +46,8 @@ struct D4GProbeOut {
     long long needHist;    // max over back-references of (distance - bytes produced so far in the block)
     int32_t nRef;          // back-reference tokens in the block
     int32_t firstBatch;    // first record of the block's verified chunk starts (D4GChunkBatch chain), < 0: none
+    int32_t hdrBits;       // dynamic block: bits of its code-length header (after the 3 block bits), else 0
+    int32_t pad;
 };
 // What the probe learned about a batch of 64 chunks, kept for the emit pass: per lane the verified start (bits from
 // the block's first token) and its counts, so the emit decodes every chunk exactly once.
@@ -467,7 +469,7 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
         br.inBase = base;
         if (tid == 0) br.reset_to(L.inbuf, bitpos);
     };
-    po.nRef = 0; po.firstBatch = -1;
+    po.nRef = 0; po.firstBatch = -1; po.hdrBits = 0; po.pad = 0;
     po.status = -1; po.type = 0; po.bfinal = 0; po.eofHit = 0; po.endBit = 0; po.nTok = 0; po.uLen = 0; po.sizeBits = 0; po.needHist = 0;
     stage(bitPos);
     long long pk = 0;
@@ -811,6 +813,7 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
     po.nTok = (long long)nTok;
     po.uLen = (long long)nU;
     po.sizeBits = S->sizeBits;
+    po.hdrBits = (int32_t)S->hdrBits;
     po.needHist = (long long)needHist;
     po.nRef = (int32_t)nRef;
     po.firstBatch = firstBatch == -2 ? -1 : firstBatch;

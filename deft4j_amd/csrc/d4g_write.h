@@ -548,3 +548,113 @@ __global__ void __launch_bounds__(256) k_csum_combine(const D4GStreamDesc* strea
         outs[blockIdx.x] = o;
     }
 }
+
+// ---------------------------------------------------------------------------------------
+// Round-trip verification: do two decoded byte ranges agree, and where is the first difference?
+// k_verify_compare walks pairs of ranges with the checksum kernels' tiling (one workgroup per D4G_CSUM_TILE bytes of a
+// pair, tileBase = exclusive prefix of the pairs' tile counts).  It is a pure read stream of 2 x len bytes: every lane
+// takes 16 bytes of both sides per step (global_load_dwordx4), four steps' loads are issued before the first compare.
+// The two sides are different allocations, so their 16-byte alignment differs in general: the loop is aligned on `got`;
+// when `want` is off by s bytes its vector is cut out of two neighbouring aligned loads with a byte funnel shift
+// (s & 3, d4g_alignbyte) after a word shift (s >> 2, a template argument: no dynamic register indexing).  Bytes before
+// the first aligned vector and after the last whole one (fewer than 16 each) are compared one per lane.
+// Result: first[pair] = min(first[pair], offset of the first differing byte), one 64-bit atomicMin per wave that found
+// a difference; the host starts every slot at D4G_VERIFY_NONE.  A tile that starts at or beyond an offset already
+// recorded returns at once.  Only the common prefix is compared: a length difference is the host's to report.
+// ---------------------------------------------------------------------------------------
+#define D4G_VERIFY_NONE (~0ull)
+#define D4G_VERIFY_UNROLL 4
+struct D4GVerifyPair { const uint8_t* got; const uint8_t* want; long long len; };
+
+// offset of the first differing byte of two vectors (0..15), 16 when they agree
+D4G_DEV uint32_t verify_first_diff(const uint4& a, const uint4& b) {
+    const uint32_t x0 = a.x ^ b.x, x1 = a.y ^ b.y, x2 = a.z ^ b.z, x3 = a.w ^ b.w;
+    if ((x0 | x1 | x2 | x3) == 0) return 16u;
+    const uint32_t x = x0 ? x0 : x1 ? x1 : x2 ? x2 : x3;
+    const uint32_t w = x0 ? 0u : x1 ? 4u : x2 ? 8u : 12u;
+    return w + (uint32_t)((__ffs((int)x) - 1) >> 3);
+}
+// `want`'s vector v: WS < 0, the sides are aligned alike; else it starts WS words and sh bytes into the aligned vector v
+template <int WS>
+D4G_DEV uint4 verify_want_vec(const uint4* wv, long long v, int sh) {
+    const uint4 lo = wv[v];
+    if (WS < 0) return lo;
+    const uint4 hi = wv[v + 1];
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    constexpr int K = WS < 0 ? 0 : WS;
+    return make_uint4(d4g_alignbyte(w[K + 1], w[K], sh), d4g_alignbyte(w[K + 2], w[K + 1], sh), d4g_alignbyte(w[K + 3], w[K + 2], sh),
+                      d4g_alignbyte(w[K + 4], w[K + 3], sh));
+}
+// the whole vectors of a tile: -> the lane's smallest differing byte offset from the first vector (~0u: none)
+template <int WS>
+D4G_DEV uint32_t verify_body(const uint4* gv, const uint4* wv, long long nvec, int sh) {
+    uint32_t found = ~0u;
+    const long long step = (long long)blockDim.x * D4G_VERIFY_UNROLL;
+    long long v0 = 0;
+    for (; v0 + step <= nvec; v0 += step) {   // (workgroup-uniform trip count: the vote below meets whole waves)
+        uint4 g[D4G_VERIFY_UNROLL], w[D4G_VERIFY_UNROLL];
+#pragma unroll
+        for (int k = 0; k < D4G_VERIFY_UNROLL; k++) g[k] = gv[v0 + threadIdx.x + (long long)k * blockDim.x];
+#pragma unroll
+        for (int k = 0; k < D4G_VERIFY_UNROLL; k++) w[k] = verify_want_vec<WS>(wv, v0 + threadIdx.x + (long long)k * blockDim.x, sh);
+#pragma unroll
+        for (int k = D4G_VERIFY_UNROLL - 1; k >= 0; k--) {
+            const uint32_t d = verify_first_diff(g[k], w[k]);
+            if (d < 16u) found = (uint32_t)(v0 + threadIdx.x + (long long)k * blockDim.x) * 16u + d;
+        }
+        if (d4g_ballot(found != ~0u)) return found;   // the wave's later vectors all lie beyond this one
+    }
+    for (long long v = v0 + threadIdx.x; v < nvec; v += blockDim.x) {
+        const uint32_t d = verify_first_diff(gv[v], verify_want_vec<WS>(wv, v, sh));
+        if (d < 16u) { found = (uint32_t)v * 16u + d; break; }
+    }
+    return found;
+}
+
+__global__ void __launch_bounds__(256) k_verify_compare(const D4GVerifyPair* pairs, const long long* tileBase, int nPairs,
+                                                        unsigned long long* first) {
+    const long long tile = blockIdx.x;
+    int lo = 0, hi = nPairs - 1;  // pair owning this tile
+    while (lo < hi) {
+        int mid = (lo + hi + 1) >> 1;
+        if (tileBase[mid] <= tile) lo = mid; else hi = mid - 1;
+    }
+    const D4GVerifyPair pr = pairs[lo];
+    const long long t0 = (tile - tileBase[lo]) * D4G_CSUM_TILE;
+    if ((unsigned long long)d4g_ld_agent((const uint64_t*)&first[lo]) <= (unsigned long long)t0) return;
+    long long tlen = pr.len - t0;
+    if (tlen > D4G_CSUM_TILE) tlen = D4G_CSUM_TILE;
+    if (tlen <= 0) return;
+    const uint8_t* g = pr.got + t0;
+    const uint8_t* w = pr.want + t0;
+    int head = (int)((16 - ((uintptr_t)g & 15)) & 15);
+    if (head > tlen) head = (int)tlen;
+    const long long nvec = (tlen - head) >> 4;
+    const int tail = (int)(tlen - head - nvec * 16);
+    uint32_t found = ~0u;
+    {   // the bytes outside the whole vectors: head on lanes 0..15, tail on lanes 32..47 of the first wave
+        const int t = (int)threadIdx.x;
+        long long at = -1;
+        if (t < head) at = t;
+        else if (t >= 32 && t - 32 < tail) at = head + nvec * 16 + (t - 32);
+        if (at >= 0 && g[at] != w[at]) found = (uint32_t)at;
+    }
+    if (nvec > 0) {
+        const uint8_t* wb = w + head;
+        const int s = (int)((uintptr_t)wb & 15), sh = s & 3;
+        const uint4* gv = (const uint4*)(g + head);
+        const uint4* wv = (const uint4*)(wb - s);   // (the aligned vectors around want's bytes: never beyond the 16-byte line of a byte of the range)
+        uint32_t f;
+        if (s == 0) f = verify_body<-1>(gv, wv, nvec, 0);
+        else switch (s >> 2) {
+            case 0: f = verify_body<0>(gv, wv, nvec, sh); break;
+            case 1: f = verify_body<1>(gv, wv, nvec, sh); break;
+            case 2: f = verify_body<2>(gv, wv, nvec, sh); break;
+            default: f = verify_body<3>(gv, wv, nvec, sh); break;
+        }
+        if (f != ~0u) { f += (uint32_t)head; found = f < found ? f : found; }
+    }
+    if (d4g_ballot(found != ~0u) == 0) return;
+    const uint32_t m = wave_min_u32(found);
+    if ((threadIdx.x & 63) == 0) atomicMin(&first[lo], (unsigned long long)t0 + m);
+}

@@ -19,6 +19,11 @@ struct d4g_batch {
     std::vector<int> reoptIndex;       // stream -> index in reopt (-1: none)
     std::vector<char> graft;
     std::vector<int64_t> recompSaved;
+    // d4g_batch_verify: verdict and first mismatch per stream, and the final stream's block list as the re-parse read it
+    bool verified = false;
+    std::vector<int32_t> verdict;
+    std::vector<int64_t> firstMismatch;
+    std::vector<std::vector<Batch::PBlock>> finalBlocks;
     // where stream i's final bytes live
     const HStream& final_stream(size_t i, const Batch** owner) const {
         if (i < graft.size() && graft[i]) { *owner = reopt.get(); return reopt->streams[reoptIndex[i]]; }
@@ -185,6 +190,85 @@ int32_t stream_status(const d4g_batch& b, size_t i) {
     const bool grafted = i < b.graft.size() && b.graft[i];
     return s.status != 0 ? D4G_STREAM_PARSE_ERROR : ((s.saved > 0 || grafted) ? D4G_STREAM_CHANGED : D4G_STREAM_UNCHANGED);
 }
+// ---- round-trip verification (verify_items, d4g_host.h) ----
+bool verify_switch() {   // D4G_VERIFY=1: every call that returns rewritten bytes verifies them first
+    const char* v = getenv("D4G_VERIFY");
+    return v && v[0] && !(v[0] == '0' && !v[1]);
+}
+const char* verdict_name(int v) {
+    switch (v) {
+        case VERIFY_OK: return "OK";
+        case VERIFY_SKIPPED: return "SKIPPED";
+        case VERIFY_PARSE: return "PARSE";
+        case VERIFY_SIZE: return "SIZE";
+        case VERIFY_LENGTH: return "LENGTH";
+        default: return "BYTES";
+    }
+}
+static_assert(VERIFY_OK == D4G_VERIFY_OK && VERIFY_SKIPPED == D4G_VERIFY_SKIPPED && VERIFY_PARSE == D4G_VERIFY_PARSE &&
+              VERIFY_SIZE == D4G_VERIFY_SIZE && VERIFY_LENGTH == D4G_VERIFY_LENGTH && VERIFY_BYTES == D4G_VERIFY_BYTES, "verdict values");
+// the first negative verdict as the call's failure
+int verdicts_to_code(const std::vector<VerifyItem>& items, const std::vector<size_t>& index, const char* what) {
+    for (size_t k = 0; k < items.size(); k++)
+        if (items[k].verdict < 0)
+            return fail(D4G_ERR_RUNTIME, std::string(what) + ": verification failed: stream " + std::to_string(index[k]) + " verdict " +
+                                             std::to_string(items[k].verdict) + " (" + verdict_name(items[k].verdict) + ") first mismatch " +
+                                             std::to_string((long long)items[k].first));
+    return D4G_OK;
+}
+// has the library written stream i's final bytes?  (an encoder batch writes every output; an optimiser batch only what changed)
+bool stream_written(const d4g_batch& b, size_t i) {
+    return b.lz ? b.impl.streams[i].status == 0 : stream_status(b, i) == D4G_STREAM_CHANGED;
+}
+// d4g_batch_verify: re-parse every written stream where it lies and compare its decoded bytes with the batch's own
+int batch_verify(d4g_batch& b, const char* what, bool failOnNegative) {
+    const size_t n = b.impl.streams.size();
+    if (n && !b.impl.dOut) return fail(D4G_ERR_ARG, "the batch has not run");
+    b.verdict.assign(n, VERIFY_SKIPPED);
+    b.firstMismatch.assign(n, -1);
+    b.finalBlocks.assign(n, {});
+    std::vector<VerifyItem> items;
+    std::vector<size_t> index;
+    for (size_t i = 0; i < n; i++) {
+        if (!stream_written(b, i)) continue;
+        const HStream& s = b.impl.streams[i];
+        const Batch* owner = nullptr;
+        const HStream& f = b.final_stream(i, &owner);
+        VerifyItem it;
+        it.bytes = (const uint8_t*)(owner->dOut + f.outWordBase);
+        it.len = (size_t)((f.outBits + 7) / 8);
+        it.want = b.impl.dU + s.uBase;
+        it.wantLen = s.nU;
+        it.wantBits = s.sizeBitsIn - s.saved - (i < b.recompSaved.size() ? b.recompSaved[i] : 0);   // what d4g_batch_stream_result lets the caller compute
+        items.push_back(it);
+        index.push_back(i);
+    }
+    VerifyTotals T;
+    verify_items(items, false, T);
+    for (size_t k = 0; k < items.size(); k++) {
+        b.verdict[index[k]] = items[k].verdict;
+        b.firstMismatch[index[k]] = items[k].first;
+        b.finalBlocks[index[k]].swap(items[k].blocks);
+    }
+    b.verified = true;
+    d4g_stats& st = b.impl.stats;
+    st.ms_verify += T.ms; st.ms_verify_kernels += T.msKernels; st.verify_streams += T.streams; st.verify_bytes += T.bytes;
+    return failOnNegative ? verdicts_to_code(items, index, what) : D4G_OK;
+}
+int verify_if_switched(d4g_batch& b, const char* what) { return verify_switch() ? batch_verify(b, what, true) : D4G_OK; }
+// outputs that sit in device memory outside a batch (d4g_compress, d4g_zopfli_streams) against raw inputs already on the device
+int verify_loose(size_t n, const std::function<const uint8_t*(size_t)>& bytes, const std::function<size_t(size_t)>& len,
+                 const std::function<const uint8_t*(size_t)>& want, const size_t* wantLen, const char* what) {
+    std::vector<VerifyItem> items(n);
+    std::vector<size_t> index(n);
+    for (size_t i = 0; i < n; i++) {
+        items[i].bytes = bytes(i); items[i].len = len(i); items[i].want = want(i); items[i].wantLen = (i64)wantLen[i];
+        index[i] = i;
+    }
+    VerifyTotals T;
+    verify_items(items, false, T);
+    return verdicts_to_code(items, index, what);
+}
 // the one-shot results of a batch that ran: its stream j goes to slot idx[j] of the caller's arrays (slot j when idx is
 // null); out[] only for changed streams
 void results_into(const d4g_batch& b, const size_t* idx, uint8_t** out, size_t* out_len, int64_t* saved_bits, int32_t* status,
@@ -205,17 +289,20 @@ void optimise_into(size_t m, const size_t* idx, const uint8_t* const* in, const 
     for (size_t j = 0; j < m; j++) { p[j] = in[idx ? idx[j] : j]; l[j] = in_len[idx ? idx[j] : j]; }
     std::unique_ptr<d4g_batch> b = make_batch(m, p.data(), l.data());
     b->impl.run(merge);
+    if (verify_switch() && batch_verify(*b, "d4g_optimise_streams", true) != D4G_OK) throw std::runtime_error(g_err);
     results_into(*b, idx, out, out_len, saved_bits, status, nullptr);
 }
 // an encoder batch's outputs as the encoder emits them, to the caller's out[] (d4g_deflate_streams*)
 int encode_into(d4g_batch& b, uint8_t** out, size_t* out_len) {
     b.lz->run(false, false);
+    if (int rc = verify_if_switched(b, "d4g_deflate_streams")) return rc;
     for (size_t i = 0; i < b.impl.streams.size(); i++) {
         if (b.impl.streams[i].status != 0) return fail(D4G_ERR_ARG, "stream did not parse");
         out[i] = final_copy(b, i, &out_len[i]);
     }
     return D4G_OK;
 }
+
 }  // namespace
 
 extern "C" {
@@ -314,7 +401,7 @@ int d4g_batch_run(d4g_batch* b, int merge_blocks) {
         if (!b) return fail(D4G_ERR_ARG, "null batch");
         if (b->lz) return fail(D4G_ERR_ARG, "encoder batch: use d4g_batch_run_encode");
         b->impl.run(merge_blocks != 0);
-        return D4G_OK;
+        return verify_if_switched(*b, "d4g_batch_run");
     });
 }
 
@@ -333,7 +420,7 @@ int d4g_batch_run_encode(d4g_batch* b, int optimise, int merge_blocks) {
     return api(b, [&] {
         if (!b || !b->lz) return fail(D4G_ERR_ARG, "not an encoder batch");
         b->lz->run(optimise != 0, merge_blocks != 0);
-        return D4G_OK;
+        return verify_if_switched(*b, "d4g_batch_run_encode");
     });
 }
 
@@ -580,6 +667,9 @@ int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_le
         if (env_int("D4G_DEBUG_ZOPFLI", 0))
             fprintf(stderr, "[zopfli] inputs %zu: table %.1f ms, split %.1f ms, squeeze %.1f ms (%lld blocks, %lld position-iterations), final+emit %.1f ms\n", n,
                     zf.msTable, zf.msSplit, zf.msSqueeze, (long long)zf.squeezeBlocks, (long long)zf.squeezePositions, zf.msEmit);
+        if (verify_switch())
+            if (int rc = verify_loose(n, [&](size_t i) { return (const uint8_t*)zf.outWords[i]; }, [&](size_t i) { return (size_t)((zf.outBits[i] + 7) / 8); },
+                                      [&](size_t i) { return up.ptr[i]; }, raw_len, "d4g_zopfli_streams")) return rc;
         for (size_t i = 0; i < n; i++) {
             out_len[i] = (size_t)((zf.outBits[i] + 7) / 8);
             out[i] = host_copy(zf.outWords[i], out_len[i]);
@@ -1029,6 +1119,11 @@ int d4g_compress(size_t n, const uint8_t* const* raw, const size_t* raw_len, int
         if (!mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
         CompressRun R;
         compress_run(R, n, raw, raw_len, false, mode, iter, merge_blocks != 0);
+        if (verify_switch()) {
+            ZfUpload up(n, raw, raw_len);
+            if (int rc = verify_loose(n, [&](size_t i) { return (const uint8_t*)(R.dWin + R.off[i]); }, [&](size_t i) { return R.len[i]; },
+                                      [&](size_t i) { return up.ptr[i]; }, raw_len, "d4g_compress")) return rc;
+        }
         for (size_t i = 0; i < n; i++) {
             out[i] = host_copy(R.dWin + R.off[i], R.len[i]);
             out_len[i] = R.len[i];
@@ -1041,7 +1136,8 @@ int d4g_compress(size_t n, const uint8_t* const* raw, const size_t* raw_len, int
 int d4g_batch_run_recompress(d4g_batch* b, int mode, int iter, int merge_blocks) {
     return api(b, [&] {
         if (!b || b->lz) return fail(D4G_ERR_ARG, "not a batch of deflate streams");
-        return recompress_batch(*b, mode, iter, merge_blocks != 0);
+        if (int rc = recompress_batch(*b, mode, iter, merge_blocks != 0)) return rc;
+        return verify_if_switched(*b, "d4g_batch_run_recompress");
     });
 }
 
@@ -1059,9 +1155,124 @@ int d4g_recompress_streams(size_t n, const uint8_t* const* in, const size_t* in_
     return o.commit(api(nullptr, [&] {
         std::unique_ptr<d4g_batch> b = make_batch(n, in, in_len);
         if (int rc = recompress_batch(*b, mode, iter, merge_blocks != 0)) return rc;
+        if (int rc = verify_if_switched(*b, "d4g_recompress_streams")) return rc;
         results_into(*b, nullptr, out, out_len, saved_bits, status, recompress_saved);
         return D4G_OK;
     }));
+}
+
+// ---- round-trip verification and per-block info ----
+int d4g_batch_verify(d4g_batch* b) {
+    return api(b, [&] {
+        if (!b) return fail(D4G_ERR_ARG, "null batch");
+        return batch_verify(*b, "d4g_batch_verify", false);
+    });
+}
+
+int d4g_batch_verify_result(d4g_batch* b, size_t i, int32_t* verdict, int64_t* first_mismatch) {
+    if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
+    if (!b->verified) return fail(D4G_ERR_ARG, "the batch has not been verified (d4g_batch_verify)");
+    if (verdict) *verdict = b->verdict[i];
+    if (first_mismatch) *first_mismatch = b->firstMismatch[i];
+    return D4G_OK;
+}
+
+int d4g_verify_streams(size_t n, const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b, const size_t* b_len,
+                       int32_t* verdict, int64_t* first_mismatch) {
+    if (n && (!a || !a_len || !b || !b_len || !verdict)) return fail(D4G_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) { verdict[i] = D4G_VERIFY_SKIPPED; if (first_mismatch) first_mismatch[i] = -1; }
+    return api(nullptr, [&] {
+        std::unique_ptr<d4g_batch> A = make_batch(n, a, a_len);   // side a: parsed and decoded; its bytes stay in HBM
+        engine().init();
+        A->impl.parse_probe();
+        A->impl.build_blocks(false, false);
+        std::vector<VerifyItem> items;
+        std::vector<size_t> index;
+        for (size_t i = 0; i < n; i++) {
+            if (A->impl.ps[i].status != 0) continue;
+            VerifyItem it;
+            it.bytes = b[i]; it.len = b_len[i];
+            it.want = A->impl.dU + A->impl.streams[i].uBase; it.wantLen = A->impl.streams[i].nU;
+            items.push_back(it);
+            index.push_back(i);
+        }
+        VerifyTotals T;
+        verify_items(items, true, T);
+        for (size_t k = 0; k < items.size(); k++) {
+            verdict[index[k]] = items[k].verdict;
+            if (first_mismatch) first_mismatch[index[k]] = items[k].first;
+        }
+        return D4G_OK;
+    });
+}
+
+int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint8_t xor_mask) {
+    if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
+    if (!b->impl.dOut || b->impl.streams[i].status != 0) return fail(D4G_ERR_ARG, "stream has no output");
+    const Batch* owner = nullptr;
+    const HStream& f = b->final_stream(i, &owner);
+    if (byte_offset >= (size_t)((f.outBits + 7) / 8)) return fail(D4G_ERR_ARG, "offset outside the stream's output");
+    return api(b, [&] {
+        uint8_t* at = (uint8_t*)(owner->dOut + f.outWordBase) + byte_offset;
+        uint8_t v = 0;
+        rt_d2h(&v, at, 1);
+        v ^= xor_mask;
+        rt_h2d(at, &v, 1);
+        rt_sync();
+        return D4G_OK;
+    });
+}
+
+int d4g_debug_verify_compare(const uint8_t* x, size_t x_skew, const uint8_t* y, size_t y_skew, size_t len, int64_t* first) {
+    if ((len && (!x || !y)) || !first || x_skew > 15 || y_skew > 15) return fail(D4G_ERR_ARG, "bad argument");
+    return api(nullptr, [&] {
+        LzScratch own;
+        uint8_t* dX = own.own((uint8_t*)rt_malloc(len + 64));
+        uint8_t* dY = own.own((uint8_t*)rt_malloc(len + 64));
+        rt_h2d(dX + x_skew, x, len);
+        rt_h2d(dY + y_skew, y, len);
+        const D4GVerifyPair pr = {dX + x_skew, dY + y_skew, (long long)len};
+        const long long base[2] = {0, ((long long)len + D4G_CSUM_TILE - 1) / D4G_CSUM_TILE};
+        D4GVerifyPair* dPair = own.own((D4GVerifyPair*)rt_malloc(sizeof(pr)));
+        long long* dBase = own.own((long long*)rt_malloc(16));
+        unsigned long long* dFirst = own.own((unsigned long long*)rt_malloc(8));
+        rt_h2d(dPair, &pr, sizeof(pr));
+        rt_h2d(dBase, base, 16);
+        rt_memset(dFirst, 0xff, 8);
+        if (base[1]) RT_LAUNCH(k_verify_compare, base[1], 256, dPair, dBase, 1, dFirst);
+        unsigned long long f = 0;
+        rt_d2h(&f, dFirst, 8);
+        *first = f == D4G_VERIFY_NONE ? -1 : (int64_t)f;
+        return D4G_OK;
+    });
+}
+
+int d4g_batch_block_info(d4g_batch* b, size_t i, int which, d4g_block_info* out, size_t cap, size_t* n_blocks) {
+    if (!b || i >= b->impl.streams.size() || i >= b->impl.ps.size()) return fail(D4G_ERR_ARG, "bad stream index (or the batch has not been parsed)");
+    if ((which != 0 && which != 1) || (cap && !out)) return fail(D4G_ERR_ARG, "bad argument");
+    if (b->impl.ps[i].status != 0) return fail(D4G_ERR_ARG, "stream did not parse");
+    const std::vector<Batch::PBlock>* list = &b->impl.ps[i].blocks;
+    if (which == 1 && b->impl.dOut && stream_written(*b, i) && (b->lz == nullptr || b->impl.streams[i].saved > 0)) {
+        // the final stream's blocks are read off the bytes that were written (the search's states are gone after a run)
+        if (!b->verified)
+            if (int rc = d4g_batch_verify(b)) return rc;
+        if (b->finalBlocks[i].empty()) return fail(D4G_ERR_RUNTIME, "the final stream does not parse");
+        list = &b->finalBlocks[i];
+    }
+    i64 pos = 0;   // DeflateStream.printBlockInfo (B/deflate/DeflateStream.java:35-51)
+    for (size_t k = 0; k < list->size(); k++) {
+        const Batch::PBlock& pb = (*list)[k];
+        pos += 3;
+        i64 size = pb.sizeBits;
+        if (pb.type == D4G_STORED) {
+            const i64 c = pos % 8;
+            size = (pb.uLen + 4) * 8 + (c == 0 ? 0 : 8 - c);
+        }
+        if (k < cap) out[k] = d4g_block_info{pb.type, pb.bfinal, pos - 3, size + 3, pb.type == D4G_DYNAMIC ? pb.hdrBits : 0, pb.nTok, pb.uLen};
+        pos += size;
+    }
+    if (n_blocks) *n_blocks = list->size();
+    return D4G_OK;
 }
 
 #ifdef D4G_HOSTSIM

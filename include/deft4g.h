@@ -76,6 +76,10 @@ typedef struct d4g_stats {
     int64_t persist_fallbacks;
     /* optimiseBlock rounds of long merged blocks run by the cluster kernel (the whole device on one block) */
     int64_t rounds_cluster;
+    /* round-trip verification (d4g_batch_verify, D4G_VERIFY=1): wall clock; device time of the re-parse of the written
+     * streams plus the byte compare (HIP events); streams verified; decoded bytes compared */
+    double ms_verify, ms_verify_kernels;
+    int64_t verify_streams, verify_bytes;
 } d4g_stats;
 
 /* Select the HIP device (one process per GPU) and create the library's stream.
@@ -204,6 +208,50 @@ int d4g_batch_run_recompress(d4g_batch* b, int mode, int iter, int merge_blocks)
 int d4g_batch_recompress_result(d4g_batch* b, size_t i, int32_t* grafted, int64_t* recompress_saved);
 int d4g_recompress_streams(size_t n, const uint8_t* const* in, const size_t* in_len, int mode, int iter, int merge_blocks,
                            uint8_t** out, size_t* out_len, int64_t* saved_bits, int64_t* recompress_saved, int32_t* status);
+
+/* ---- round-trip verification: does what the library wrote decode to what it read? ----
+ * d4g_batch_verify, valid after d4g_batch_run / _run_recompress / _run_encode: every stream whose final bytes the
+ * library produced (status D4G_STREAM_CHANGED, a grafted recompression included; every output of an encoder batch) is
+ * parsed again where it lies in HBM, the parse must read exactly out_len bytes and size_bits_in - saved_bits
+ * (- recompress_saved) bits, and its decoded bytes are compared on the device with the batch's own decoded bytes of the
+ * input (an encoder batch: the raw input).  No decoded byte goes through the host.  The call returns 0 when it could do
+ * its work, whatever the verdicts.  first_mismatch: the byte offset for BYTES, the shorter length for LENGTH, else -1.
+ * The checks run in the order PARSE, SIZE, BYTES, LENGTH: the compare covers the common prefix, so a differing byte
+ * inside it is reported as BYTES even when the lengths differ too (bytes win over length).
+ * d4g_verify_streams, usable on its own: do the raw DEFLATE streams a[i] and b[i] decode to the same bytes?  PARSE: b[i]
+ * does not parse; SKIPPED: a[i] does not.  (No SIZE verdict: b[i] may be followed by other data.)
+ * D4G_VERIFY=1 in the environment: every run call and every one-shot call that returns rewritten bytes verifies them
+ * before it returns; a negative verdict makes the call fail with D4G_ERR_RUNTIME (d4g_last_error names the stream, the
+ * verdict and the offset; a one-shot call hands back no buffers).  Unset or 0: no extra launch, no extra allocation. */
+#define D4G_VERIFY_OK 0
+#define D4G_VERIFY_SKIPPED 1      /* unchanged or unparsable input: the library wrote nothing */
+#define D4G_VERIFY_PARSE (-1)
+#define D4G_VERIFY_SIZE (-2)
+#define D4G_VERIFY_LENGTH (-3)
+#define D4G_VERIFY_BYTES (-4)
+int d4g_batch_verify(d4g_batch* b);
+int d4g_batch_verify_result(d4g_batch* b, size_t i, int32_t* verdict, int64_t* first_mismatch);
+int d4g_verify_streams(size_t n, const uint8_t* const* a, const size_t* a_len, const uint8_t* const* b, const size_t* b_len,
+                       int32_t* verdict, int64_t* first_mismatch);
+/* Test hook (tests/ only): XORs xor_mask into byte byte_offset of stream i's final output in HBM after a run, so that a
+ * test can show the verifier saying no.  It writes inside the stream's own output bytes only: any other offset is
+ * D4G_ERR_ARG. */
+int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint8_t xor_mask);
+/* Test hook (tests/ only): the compare kernel alone on two host buffers of len bytes, placed x_skew and y_skew (0..15)
+ * bytes past a 16-byte boundary of device memory: *first = offset of the first differing byte, -1 when they agree.
+ * (Every decoded range the library itself compares starts on a 16-byte boundary; the kernel does not rely on it.) */
+int d4g_debug_verify_compare(const uint8_t* x, size_t x_skew, const uint8_t* y, size_t y_skew, size_t len, int64_t* first);
+
+/* ---- per-block info: DeflateStream.printBlockInfo (B/deflate/DeflateStream.java:35-51) ----
+ * which = 0: stream i as parsed (an encoder batch: as the encoder emitted it); 1: the final stream (the input's list
+ * when the stream is unchanged; read off the written bytes otherwise, which verifies the batch if that has not happened).
+ * bit_pos = position of the block's 3 header bits, size_bits = its size including them, as printBlockInfo counts them
+ * (a stored block's padding follows its position); header_bits = a dynamic block's code-length header (else 0);
+ * tokens includes the end-of-block symbol (0 for a stored block).  cap smaller than the count fills cap entries and
+ * still sets *n_blocks. */
+typedef struct d4g_block_info { int32_t type, bfinal; int64_t bit_pos, size_bits, header_bits, tokens, decoded_len; } d4g_block_info;
+int d4g_batch_block_info(d4g_batch* b, size_t i, int which /* 0 = input as parsed, 1 = final stream */, d4g_block_info* out, size_t cap,
+                         size_t* n_blocks);
 
 /* ---- one-shot wrappers ----
  * Deft.optimiseDeflateStream for n streams: out[i]/out_len[i] are set only when status[i] ==

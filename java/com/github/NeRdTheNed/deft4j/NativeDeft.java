@@ -77,6 +77,10 @@ public final class NativeDeft {
     public static native byte[][] recompressStreams(byte[][] in, int mode, int iter, boolean mergeBlocks, long[] savedBits, long[] recompressSaved,
             int[] status) throws java.io.IOException;
 
+    /** Do a[i] and b[i] decode to the same bytes?  result[i]: 0 OK, 1 skipped (a[i] does not parse), -1 b[i] does not parse, -3 lengths differ,
+     *  -4 bytes differ.  Parsed and compared on the device; the reference has no counterpart. */
+    public static native int[] verifyStreams(byte[][] a, byte[][] b) throws java.io.IOException;
+
     /** Deft.optimiseDeflateStream(byte[], boolean): same contract, including "returns the SAME array when nothing was saved" */
     public static byte[] optimiseDeflateStream(byte[] original, boolean mergeBlocks) {
         final int[] status = new int[1];

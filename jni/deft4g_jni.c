@@ -251,3 +251,24 @@ JNIEXPORT jobjectArray JNICALL JFN(recompressStreams)(JNIEnv* e, jclass c, jobje
     unpin(e, &L);
     return res;
 }
+
+/* int[] verifyStreams(byte[][] a, byte[][] b): do a[i] and b[i] decode to the same bytes?  Entry i is a D4G_VERIFY_*
+ * verdict (0 OK, 1 SKIPPED: a[i] does not parse, -1 PARSE: b[i] does not, -3 LENGTH, -4 BYTES); both sides are parsed and
+ * compared on the device.  The reference has no counterpart. */
+JNIEXPORT jintArray JNICALL JFN(verifyStreams)(JNIEnv* e, jclass c, jobjectArray a, jobjectArray b) {
+    (void)c;
+    in_list A = {0}, B = {0};
+    jintArray res = NULL;
+    if (pin(e, a, &A) == 0 && pin(e, b, &B) == 0 && A.n == B.n) {
+        int32_t* verdict = calloc((size_t)A.n + 1, sizeof *verdict);
+        int64_t* first = calloc((size_t)A.n + 1, sizeof *first);
+        if (verdict && first && d4g_verify_streams((size_t)A.n, A.ptr, A.len, B.ptr, B.len, verdict, first) == D4G_OK) {
+            res = (*e)->NewIntArray(e, A.n);
+            if (res) (*e)->SetIntArrayRegion(e, res, 0, A.n, (const jint*)verdict);
+        } else throw_io(e, "d4g_verify_streams");
+        free(verdict); free(first);
+    } else if (!(*e)->ExceptionCheck(e)) throw_io(e, "verifyStreams: two lists of the same length");
+    unpin(e, &A);
+    unpin(e, &B);
+    return res;
+}
