@@ -68,7 +68,8 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_compress", "d4g_recompress_streams", "d4g_batch_run_recompress", "d4g_batch_recompress_result", "d4g_zopfli_streams",
            "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
            "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
-           "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare"]
+           "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
+           "d4g_debug_device_blocks"]
 
 
 def load_library(path=None):
@@ -173,6 +174,8 @@ def load_library(path=None):
     L.d4g_debug_batch_poke_output.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint8]
     L.d4g_debug_verify_compare.restype = ctypes.c_int
     L.d4g_debug_verify_compare.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)]
+    L.d4g_debug_device_blocks.restype = ctypes.c_int
+    L.d4g_debug_device_blocks.argtypes = [ctypes.POINTER(ctypes.c_int64)]
     L.d4g_batch_block_info.restype = ctypes.c_int
     L.d4g_batch_block_info.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(d4g_block_info), ctypes.c_size_t,
                                        ctypes.POINTER(ctypes.c_size_t)]

@@ -136,9 +136,9 @@ struct Program {
     std::vector<int> slotLevel;
     int nSlots = 1, nMasks = 1, nLevels = 0;
     std::vector<std::vector<int>> stateLevels, hdrLevels;
-    D4GOp* dOps = nullptr;
-    int32_t* dLists = nullptr;
-    int32_t *dStateFlat = nullptr, *dHdrFlat = nullptr;  // level-ordered op ids for the persistent executor
+    RtBuf<D4GOp> dOps;
+    RtBuf<int32_t> dLists;
+    RtBuf<int32_t> dStateFlat, dHdrFlat;  // level-ordered op ids for the persistent executor
     int nStateFlat = 0, nHdrFlat = 0;
     std::vector<std::pair<size_t, int>> stateOff, hdrOff, wideOff;  // per level: (offset into dLists, count)
     int nRequested = 0;  // ops the plain unrolling would have emitted (for the record)
@@ -360,12 +360,11 @@ struct Program {
         for (auto& v : stateLevels) std::stable_sort(v.begin(), v.end(), [&](int x, int y) { return cost(x) > cost(y); });
     }
     void release() {
-        rt_free(dOps); rt_free(dLists); rt_free(dStateFlat); rt_free(dHdrFlat);
-        dOps = nullptr; dLists = nullptr; dStateFlat = nullptr; dHdrFlat = nullptr;
+        dOps.reset(); dLists.reset(); dStateFlat.reset(); dHdrFlat.reset();
         stateOff.clear(); hdrOff.clear(); wideOff.clear();
     }
     void upload() {
-        dOps = (D4GOp*)rt_malloc(ops.size() * sizeof(D4GOp));
+        dOps.alloc(ops.size());
         rt_h2d(dOps, ops.data(), ops.size() * sizeof(D4GOp));
         std::vector<int32_t> lists;
         for (int l = 0; l < nLevels; l++) {
@@ -384,7 +383,7 @@ struct Program {
             hdrOff.push_back({lists.size(), (int)hdrLevels[l].size()});
             lists.insert(lists.end(), hdrLevels[l].begin(), hdrLevels[l].end());
         }
-        dLists = (int32_t*)rt_malloc(lists.size() * sizeof(int32_t));
+        dLists.alloc(lists.size());
         rt_h2d(dLists, lists.data(), lists.size() * sizeof(int32_t));
         std::vector<int32_t> sf, hf;
         for (int l = 0; l < nLevels; l++) {
@@ -393,8 +392,8 @@ struct Program {
         }
         nStateFlat = (int)sf.size();
         nHdrFlat = (int)hf.size();
-        dStateFlat = (int32_t*)rt_malloc(sf.size() * sizeof(int32_t) + 16);
-        dHdrFlat = (int32_t*)rt_malloc(hf.size() * sizeof(int32_t) + 16);
+        dStateFlat.alloc(sf.size(), 16);
+        dHdrFlat.alloc(hf.size(), 16);
         rt_h2d(dStateFlat, sf.data(), sf.size() * sizeof(int32_t));
         rt_h2d(dHdrFlat, hf.data(), hf.size() * sizeof(int32_t));
         rt_sync();
@@ -431,17 +430,16 @@ static void build_hdr_tables(uint8_t* flags, uint8_t* prune) {
 
 struct Engine {  // per-process device objects shared by all batches
     Program progDyn, progFixed;
-    uint8_t* dHdrTables = nullptr;  // flags[64] + prune[64]
-    long long* dOpStats = nullptr;
-    uint32_t* dCrcTab = nullptr;   // [1024] slice-by-4 CRC-32 tables, then [32] x^(2^k) mod P
+    RtBuf<uint8_t> dHdrTables;  // flags[64] + prune[64]
+    RtBuf<long long> dOpStats;
+    RtBuf<uint32_t> dCrcTab;   // [1024] slice-by-4 CRC-32 tables, then [32] x^(2^k) mod P
     int slotsPerBlock = 0, masksPerBlock = 0, maxOps = 0;
     bool ready = false, built = false;
     // d4g_shutdown: the device objects go back (a later d4g_init may pick another device)
     void release() {
         if (!ready) return;
         progDyn.release(); progFixed.release();
-        rt_free(dHdrTables); rt_free(dOpStats); rt_free(dCrcTab);
-        dHdrTables = nullptr; dOpStats = nullptr; dCrcTab = nullptr;
+        dHdrTables.reset(); dOpStats.reset(); dCrcTab.reset();
         ready = false;
     }
     void init() {
@@ -470,10 +468,9 @@ struct Engine {  // per-process device objects shared by all batches
         uint8_t tab[128];
         memset(tab, 0, sizeof(tab));
         build_hdr_tables(tab, tab + 64);
-        dHdrTables = (uint8_t*)rt_malloc(128);
+        dHdrTables.alloc(128);
         rt_h2d(dHdrTables, tab, 128);
-        dOpStats = (long long*)rt_malloc(64 * 8);
-        rt_memset(dOpStats, 0, 64 * 8);
+        dOpStats.alloc_zero(64);
         {
             std::vector<uint32_t> t(1024 + 32);
             for (uint32_t i = 0; i < 256; i++) {
@@ -495,7 +492,7 @@ struct Engine {  // per-process device objects shared by all batches
             uint32_t p = 1u << 30;  // x^1
             t[1024] = p;
             for (int k = 1; k < 32; k++) t[1024 + k] = p = mul(p, p);
-            dCrcTab = (uint32_t*)rt_malloc(t.size() * 4);
+            dCrcTab.alloc(t.size());
             rt_h2d(dCrcTab, t.data(), t.size() * 4);
         }
         rt_sync();
@@ -553,26 +550,26 @@ struct Batch {
     std::vector<HStream> streams;
     d4g_stats stats;
     // device
-    uint8_t* dIn = nullptr;
-    uint2* dTok = nullptr;
-    uint4* dRefs = nullptr;       // back-reference records
-    uint32_t* dTokRef = nullptr;  // token -> record index
-    uint32_t* dBinStat = nullptr; // per block: static bin statistics (d4g_types.h)
-    uint64_t* dBinMask = nullptr; // per block: bin record masks
-    D4GHsMemo* dHsMemo = nullptr; // per block: header-search memo
-    D4GRecodeMemo* dRcMemo = nullptr;  // per block: Huffman-rebuild memo
-    uint64_t* dPassMemo = nullptr;     // per block: token-pass memo entries
-    uint8_t* dU = nullptr;
-    D4GBlock* dBlocks = nullptr;
-    D4GState* dStates = nullptr;
-    uint64_t* dMasks = nullptr;
-    long long* dKeys = nullptr;
-    int32_t* dErr = nullptr;       // device consistency counter of THIS batch (kernels add to it; checked after each phase)
-    int32_t* dActive = nullptr;
-    D4GRoundResult* dResults = nullptr;
-    uint32_t* dOut = nullptr;
-    int32_t* dReady = nullptr;   // per (block, slot): epoch of the round that produced it (persistent executor)
-    unsigned* dHeads = nullptr;
+    RtBuf<uint8_t> dIn;
+    RtBuf<uint2> dTok;
+    RtBuf<uint4> dRefs;          // back-reference records
+    RtBuf<uint32_t> dTokRef;     // token -> record index
+    RtBuf<uint32_t> dBinStat;    // per block: static bin statistics (d4g_types.h)
+    RtBuf<uint64_t> dBinMask;    // per block: bin record masks
+    RtBuf<D4GHsMemo> dHsMemo;    // per block: header-search memo
+    RtBuf<D4GRecodeMemo> dRcMemo;   // per block: Huffman-rebuild memo
+    RtBuf<uint64_t> dPassMemo;      // per block: token-pass memo entries
+    RtBuf<uint8_t> dU;
+    RtBuf<D4GBlock> dBlocks;
+    RtBuf<D4GState> dStates;
+    RtBuf<uint64_t> dMasks;
+    RtBuf<long long> dKeys;
+    RtBuf<int32_t> dErr;         // device consistency counter of THIS batch (kernels add to it; checked after each phase)
+    RtBuf<int32_t> dActive;
+    RtBuf<D4GRoundResult> dResults;
+    RtBuf<uint32_t> dOut;
+    RtBuf<int32_t> dReady;       // per (block, slot): epoch of the round that produced it (persistent executor)
+    RtBuf<unsigned> dHeads;
     int epoch = 0;
     std::vector<D4GBlock> hBlocks;  // device block descriptors (host copy)
     std::vector<int> gpuType;       // current state type per device block
@@ -580,14 +577,11 @@ struct Batch {
     bool ran = false;
 
     ~Batch() {
-        try { rt_sync_all(); } catch (...) {}   // nothing may still be running on a block that goes back to the pool
-        rt_free(dIn); rt_free(dTok); rt_free(dRefs); rt_free(dTokRef); rt_free(dBinStat); rt_free(dBinMask); rt_free(dHsMemo); rt_free(dRcMemo); rt_free(dPassMemo); rt_free(chunkPool.batches); rt_free(chunkPool.next); rt_free(dU); rt_free(dBlocks); rt_free(dStates);
-        rt_free(dErr);
-        rt_free(dMasks); rt_free(dKeys); rt_free(dActive); rt_free(dResults); rt_free(dOut); rt_free(dStreams); rt_free(dSrc); rt_free(dReady); rt_free(dHeads); rt_free(dClArena);
+        try { rt_sync_all(); } catch (...) {}   // nothing may still be running on a block that goes back to the pool (the members follow)
     }
 
     int32_t* errors() {
-        if (!dErr) { dErr = (int32_t*)rt_malloc(16); rt_memset(dErr, 0, 16); }
+        if (!dErr) dErr.alloc_zero(4);
         return dErr;
     }
     // What only the level / persistent executors use (candidate keys, slot epochs, queue heads, the three memo tables): made
@@ -598,16 +592,12 @@ struct Batch {
         if (dKeys || !legacyBlocks) return;
         Engine& E = engine();
         const size_t nb = legacyBlocks;
-        dKeys = (long long*)rt_malloc(nb * (size_t)E.maxOps * sizeof(long long));
-        dReady = (int32_t*)rt_malloc(nb * (size_t)slotsAlloc * sizeof(int32_t));
-        rt_memset(dReady, 0, nb * (size_t)slotsAlloc * sizeof(int32_t));
-        dHeads = (unsigned*)rt_malloc(64);
-        dHsMemo = (D4GHsMemo*)rt_malloc(nb * (size_t)D4G_HSMEMO_SLOTS * sizeof(D4GHsMemo));
-        rt_memset(dHsMemo, 0, nb * (size_t)D4G_HSMEMO_SLOTS * sizeof(D4GHsMemo));
-        dPassMemo = (uint64_t*)rt_malloc((size_t)legacyPassMemoWords * 8 + 64);
-        rt_memset(dPassMemo, 0, (size_t)legacyPassMemoWords * 8 + 64);
-        dRcMemo = (D4GRecodeMemo*)rt_malloc(nb * (size_t)D4G_RCMEMO_SLOTS * sizeof(D4GRecodeMemo));
-        rt_memset(dRcMemo, 0, nb * (size_t)D4G_RCMEMO_SLOTS * sizeof(D4GRecodeMemo));
+        dKeys.alloc(nb * (size_t)E.maxOps);
+        dReady.alloc_zero(nb * (size_t)slotsAlloc);
+        dHeads.alloc(16);
+        dHsMemo.alloc_zero(nb * (size_t)D4G_HSMEMO_SLOTS);
+        dPassMemo.alloc_zero((size_t)legacyPassMemoWords, 64);
+        dRcMemo.alloc_zero(nb * (size_t)D4G_RCMEMO_SLOTS);
     }
     D4GCtx make_ctx(const Program& P, int nActive) {
         Engine& E = engine();
@@ -637,8 +627,7 @@ struct Batch {
             stats.bytes_in += (i64)len[i];
         }
         i64 total = off + D4G_INCH + 64;
-        dIn = (uint8_t*)rt_malloc((size_t)total);
-        rt_memset(dIn, 0, (size_t)total);
+        dIn.alloc_zero((size_t)total);
         for (size_t i = 0; i < n; i++) {
             if (fromDevice) rt_d2d(dIn + streams[i].inOff, in[i], len[i]);
             else rt_h2d(dIn + streams[i].inOff, in[i], len[i]);
@@ -652,9 +641,11 @@ struct Batch {
     struct PBlock { int type, bfinal; i64 bitPos, endBit, nTok, uLen, sizeBits, nRef; int firstBatch; i64 refSpan = -1; i64 hdrBits = 0; };   // refSpan: records the block occupies in refs even when it is STORED (LZ77 front end)
     struct PStream { int status = 0; std::vector<PBlock> blocks; i64 nTok = 0, nU = 0, consumed = 0, sizeBits = 0; i64 uBaseFixed = -1; };   // uBaseFixed: the decoded bytes already sit in U (LZ77 front end: the raw input)
     std::vector<PStream> ps;
-    D4GStreamDesc* dStreams = nullptr;
-    D4GChunkPool chunkPool = {nullptr, nullptr, 0};   // the probe's verified chunk starts, replayed by the emit pass
-    uint32_t* dSrc = nullptr;
+    RtBuf<D4GStreamDesc> dStreams;
+    RtBuf<D4GChunkBatch> dChunkBatches;   // the probe's verified chunk starts, replayed by the emit pass: what chunkPool points to
+    RtBuf<unsigned> dChunkNext;
+    D4GChunkPool chunkPool = {nullptr, nullptr, 0};
+    RtBuf<uint32_t> dSrc;
     int slotsAlloc = 0;
     double msParseKernels = 0;
 
@@ -673,7 +664,7 @@ struct Batch {
             for (i64 b = 0; b < streams[i].inLen; b += D4G_SCAN_TILE) tiles.push_back({(int32_t)i, 0, b});
             totalBytes += streams[i].inLen;
         }
-        dStreams = (D4GStreamDesc*)rt_malloc(n * sizeof(D4GStreamDesc));
+        dStreams.alloc(n);
         rt_h2d(dStreams, sd.data(), n * sizeof(D4GStreamDesc));
         RtEvent e0, e1;
         e0.record();
@@ -681,15 +672,17 @@ struct Batch {
         std::vector<D4GProbeIn> cands;
         std::vector<D4GProbeOut> pout;
         if (!tiles.empty()) {
-            D4GScanTile* dTiles = (D4GScanTile*)rt_malloc(tiles.size() * sizeof(D4GScanTile));
+            // (every step below ends in a blocking read: a buffer that goes back here is no longer in use)
+            RtBuf<D4GScanTile> dTiles;
+            dTiles.alloc(tiles.size());
             rt_h2d(dTiles, tiles.data(), tiles.size() * sizeof(D4GScanTile));
             unsigned cap = (unsigned)std::max<i64>(65536, totalBytes / 4);
-            unsigned* dN = (unsigned*)rt_malloc(4);
-            D4GProbeIn* dCands = nullptr;
+            RtBuf<unsigned> dN;
+            dN.alloc(1);
+            RtBuf<D4GProbeIn> dCands;
             unsigned nc = 0;
             for (int attempt = 0; attempt < 2; attempt++) {
-                rt_free(dCands);
-                dCands = (D4GProbeIn*)rt_malloc((size_t)cap * sizeof(D4GProbeIn));
+                dCands.alloc((size_t)cap);
                 rt_memset(dN, 0, 4);
                 RT_LAUNCH(k_scan_headers, tiles.size(), 256, dStreams, dTiles, dCands, dN, cap);
                 stats.kernel_launches++;
@@ -701,33 +694,32 @@ struct Batch {
             // that parse come back
             stats.scan_candidates = (i64)nc;
             if (nc) {
-                D4GProbeIn* dKept = (D4GProbeIn*)rt_malloc((size_t)nc * sizeof(D4GProbeIn));
+                RtBuf<D4GProbeIn> dKept;
+                dKept.alloc((size_t)nc);
                 rt_memset(dN, 0, 4);
                 RT_LAUNCH(k_prefilter_headers, (nc + 63) / 64, 64, dStreams, dCands, nc, dKept, dN);
                 stats.kernel_launches++;
                 rt_d2h(&nc, dN, 4);
-                rt_free(dCands);
-                dCands = dKept;
+                dCands = std::move(dKept);
             }
             if (nc) {
-                D4GProbeHit* dHits = (D4GProbeHit*)rt_malloc((size_t)nc * sizeof(D4GProbeHit));
+                RtBuf<D4GProbeHit> dHits;
+                dHits.alloc((size_t)nc);
                 rt_memset(dN, 0, 4);
                 chunkPool.cap = (unsigned)std::min<i64>(1 << 30, totalBytes * 8 / (64 * D4G_CHUNK_BITS) + 2 * (i64)nc * (parse_threads() / 64) + 64);   // one record per wave and batch
-                chunkPool.batches = (D4GChunkBatch*)rt_malloc((size_t)chunkPool.cap * sizeof(D4GChunkBatch));
-                chunkPool.next = (unsigned*)rt_malloc(16);
-                rt_memset(chunkPool.next, 0, 16);
+                chunkPool.batches = dChunkBatches.alloc((size_t)chunkPool.cap);
+                chunkPool.next = dChunkNext.alloc_zero(4);
                 RT_LAUNCH(k_probe_blocks, nc, parse_threads(), dStreams, dCands, (D4GProbeOut*)nullptr, nc, dHits, dN, chunkPool);
                 stats.kernel_launches++;
                 unsigned nh = 0;
                 rt_d2h(&nh, dN, 4);
                 std::vector<D4GProbeHit> hits(nh);
                 rt_d2h(hits.data(), dHits, (size_t)nh * sizeof(D4GProbeHit));
-                rt_free(dHits);
+                dHits.reset();
                 cands.resize(nh);
                 pout.resize(nh);
                 for (unsigned k = 0; k < nh; k++) { cands[k] = hits[k].in; pout[k] = hits[k].out; }
             }
-            rt_free(dCands); rt_free(dN); rt_free(dTiles);
         }
         // candidate maps: bit position -> probe result
         std::vector<std::vector<std::pair<i64, int>>> byStream(n);
@@ -737,8 +729,10 @@ struct Batch {
         // chain walk; positions the scan cannot see (fixed / stored / unusual dynamic blocks) are probed exactly
         std::vector<i64> cur(n, 0), upos(n, 0), spos(n, 0);
         std::vector<char> done(n, 0);
-        D4GProbeIn* dEx = (D4GProbeIn*)rt_malloc(n * sizeof(D4GProbeIn) + 16);
-        D4GProbeOut* dExOut = (D4GProbeOut*)rt_malloc(n * sizeof(D4GProbeOut) + 16);
+        RtBuf<D4GProbeIn> dEx;
+        RtBuf<D4GProbeOut> dExOut;
+        dEx.alloc(n, 16);
+        dExOut.alloc(n, 16);
         auto accept = [&](size_t i, i64 bitPos, const D4GProbeOut& o, bool fromScan) {
             PStream& P = ps[i];
             if (o.status != 0 || o.needHist > upos[i]) { P.status = -1; done[i] = 1; return; }
@@ -778,7 +772,7 @@ struct Batch {
             rt_d2h(eo.data(), dExOut, ex.size() * sizeof(D4GProbeOut));
             for (size_t k = 0; k < ex.size(); k++) accept(exStream[k], ex[k].bitPos, eo[k], false);
         }
-        rt_free(dEx); rt_free(dExOut);
+        dEx.reset(); dExOut.reset();
         e1.record();
         msParseKernels += rt_elapsed_ms(e0, e1);
         for (size_t i = 0; i < n; i++) {
@@ -910,32 +904,30 @@ struct Batch {
             }
         }
         size_t nb = hBlocks.size();
-        if (!dStreams) dStreams = (D4GStreamDesc*)rt_malloc(n * sizeof(D4GStreamDesc) + 16);
+        if (!dStreams) dStreams.alloc(n, 16);
         rt_h2d(dStreams, sd.data(), n * sizeof(D4GStreamDesc));
         if (refTot >= (1LL << 32)) throw std::runtime_error("batch holds 2^32 or more back-references: split it");
         uTotal = uTot;
         // (the LZ77 front end has filled tok / refs / tokRef / U already, with the same numbering)
-        if (!dTok) dTok = (uint2*)rt_malloc((size_t)tokTot * 8 + 64);
-        if (!dRefs) dRefs = (uint4*)rt_malloc((size_t)refTot * 16 + 64);
-        if (!dTokRef) dTokRef = (uint32_t*)rt_malloc((size_t)tokTot * 4 + 64);
-        if (!dU) dU = (uint8_t*)rt_malloc((size_t)uTot + 64);
+        if (!dTok) dTok.alloc((size_t)tokTot, 64);
+        if (!dRefs) dRefs.alloc((size_t)refTot, 64);
+        if (!dTokRef) dTokRef.alloc((size_t)tokTot, 64);
+        if (!dU) dU.alloc((size_t)uTot, 64);
         if (nb) {
-            dBlocks = (D4GBlock*)rt_malloc(nb * sizeof(D4GBlock));
+            dBlocks.alloc(nb);
             rt_h2d(dBlocks, hBlocks.data(), nb * sizeof(D4GBlock));
-            dStates = (D4GState*)rt_malloc(nb * (size_t)slotsAlloc * sizeof(D4GState));
-            dMasks = (uint64_t*)rt_malloc((size_t)maskWordsTotal * 8 + 64);
+            dStates.alloc(nb * (size_t)slotsAlloc);
+            dMasks.alloc((size_t)maskWordsTotal, 64);
             legacyBlocks = needSlots ? nb : 0;
             legacyPassMemoWords = passMemoWords;
             if (needSlots && !exec_fused()) ensure_legacy_tables();   // (the fused executor's batches make them when a block first falls back)
-            dActive = (int32_t*)rt_malloc(nb * sizeof(int32_t));
-            dResults = (D4GRoundResult*)rt_malloc(nb * sizeof(D4GRoundResult));
+            dActive.alloc(nb);
+            dResults.alloc(nb);
             // mask 0 of every block starts empty (no back-reference expanded); the writer reads it even when no search runs
             rt_memset(dMasks, 0, (size_t)maskWordsTotal * 8 + 64);   // one fill instead of one per block
             if (needSlots) {
-                dBinStat = (uint32_t*)rt_malloc(nb * (size_t)D4G_NBINS * D4G_BINSTRIDE * 4);
-                dBinMask = (uint64_t*)rt_malloc((size_t)binMaskWords * 8 + 64);
-                rt_memset(dBinStat, 0, nb * (size_t)D4G_NBINS * D4G_BINSTRIDE * 4);
-                rt_memset(dBinMask, 0, (size_t)binMaskWords * 8 + 64);
+                dBinStat.alloc_zero(nb * (size_t)D4G_NBINS * D4G_BINSTRIDE);
+                dBinMask.alloc_zero((size_t)binMaskWords, 64);
             }
         }
     }
@@ -945,36 +937,32 @@ struct Batch {
     void build_blocks(bool merge, bool needSlots) {
         Engine& E = engine();
         size_t n = streams.size();
+        i64 maxU = 0;
+        for (size_t i = 0; i < n; i++) maxU = std::max(maxU, ps[i].nU);
+        if (maxU >= (1LL << 31)) throw std::runtime_error("a stream decodes to 2 GiB or more");   // (k_fill_src's positions would reach D4G_SRC_FINAL)
         Layout LY;
         layout_blocks(merge, needSlots, LY);
         std::vector<D4GEmitIn>& emits = LY.emits;
         std::vector<D4GTokRange>& ranges = LY.ranges;
-        dSrc = (uint32_t*)rt_malloc((size_t)uTotal * 4 + 64);
+        dSrc.alloc((size_t)uTotal, 64);
         RtEvent e0, e1;
         e0.record();
         int32_t* dBadFlags = nullptr;     // per stream: a back-reference reached before the start of the stream
-        std::vector<void*> later;         // device buffers the queued kernels still read: freed after the wait below
+        RtScratch tmp;                    // device buffers the queued kernels still read: released after the wait below
         if (!emits.empty()) {
             // 3. emit
-            D4GEmitIn* dEm = (D4GEmitIn*)rt_malloc(emits.size() * sizeof(D4GEmitIn));
-            rt_h2d(dEm, emits.data(), emits.size() * sizeof(D4GEmitIn));
+            D4GEmitIn* dEm = tmp.upload(emits);
             D4GParseOut po = {dTok, dU, dStates, dRefs, dTokRef};
             RT_LAUNCH(k_emit_blocks, emits.size(), parse_threads(), dStreams, dEm, po, errors(), chunkPool);
             stats.kernel_launches++;
             // 4. decoded bytes
-            D4GTokRange* dRanges = (D4GTokRange*)rt_malloc(ranges.size() * sizeof(D4GTokRange));
-            rt_h2d(dRanges, ranges.data(), ranges.size() * sizeof(D4GTokRange));
-            int32_t* dBad = (int32_t*)rt_malloc(n * 4 + 16);
-            rt_memset(dBad, 0, n * 4 + 16);
+            D4GTokRange* dRanges = tmp.upload(ranges);
+            int32_t* dBad = tmp.alloc_zero<int32_t>(n, 16);
             const int GF = 8;
             RT_LAUNCH(k_fill_src, ranges.size() * GF, 256, dStreams, dRanges, dTok, dU, dSrc, dBad, GF);
             stats.kernel_launches++;
-            i64 maxU = 0;
-            for (size_t i = 0; i < n; i++) maxU = std::max(maxU, ps[i].nU);
-            if (maxU >= (1LL << 31)) throw std::runtime_error("a stream decodes to 2 GiB or more");
             int G = (int)std::min<i64>(2048, std::max<i64>(1, (maxU + 4095) / 4096));
-            unsigned long long* dChanged = (unsigned long long*)rt_malloc(40 * 8);   // one counter per round, zeroed once
-            rt_memset(dChanged, 0, 40 * 8);
+            unsigned long long* dChanged = tmp.alloc_zero<unsigned long long>(40);   // one counter per round, zeroed once
             i64 totalU = 0;
             for (size_t i = 0; i < n; i++) totalU += ps[i].nU;
             static int stopPct = -1;   // D4G_JUMP_STOP_PCT: stop doubling once fewer than this share of the bytes still moves
@@ -982,7 +970,6 @@ struct Batch {
             const unsigned long long stopNum = std::max<unsigned long long>(1, (unsigned long long)((totalU * stopPct + 99) / 100));   // the resolve pass walks what is left of the chains
             // the first rounds tile by tile, out of the XCDs' L2 (k_jump_tiles); D4G_JUMP_TILE_REPS=0: plain rounds only
             static const int tileReps = env_int("D4G_JUMP_TILE_REPS", 6);
-            void* jumpTmp[2] = {nullptr, nullptr};
             if (tileReps > 0) {
                 std::vector<D4GJumpTile> tl;
                 for (size_t i = 0; i < n; i++)
@@ -997,10 +984,8 @@ struct Batch {
                             const size_t t = x * per + j;
                             if (t < nt) ord[w++] = tl[t];
                         }
-                    D4GJumpTile* dTl = (D4GJumpTile*)rt_malloc(nt * sizeof(D4GJumpTile));
-                    rt_h2d(dTl, ord.data(), nt * sizeof(D4GJumpTile));
-                    unsigned long long* dCh0 = (unsigned long long*)rt_malloc(16);
-                    rt_memset(dCh0, 0, 16);
+                    D4GJumpTile* dTl = tmp.upload(ord);   // (released with the other parse buffers, after the next wait)
+                    unsigned long long* dCh0 = tmp.alloc_zero<unsigned long long>(2);
 #ifdef D4G_HOSTSIM
                     RT_LAUNCH(k_jump_tiles, nt, 256, dStreams, dTl, dSrc, tileReps, dCh0);
 #else
@@ -1025,7 +1010,6 @@ struct Batch {
                     }
 #endif
                     stats.kernel_launches++;
-                    jumpTmp[0] = dTl; jumpTmp[1] = dCh0;   // (freed with the other parse buffers, after the next synchronisation)
                 }
             }
             const int JB = tileReps > 0 ? 4 : 10;   // rounds per batch: launched back to back, counters read once (after the tile rounds one or two are left)
@@ -1053,39 +1037,34 @@ struct Batch {
             stats.kernel_launches++;
             // (no wait here: the bin statistics follow on the same stream; the flags come back behind them, one wait for both)
             dBadFlags = dBad;
-            later = {dEm, dRanges, dChanged, jumpTmp[0], jumpTmp[1]};
         }
-        later.push_back(block_bins(LY.realBlocks, needSlots));
+        block_bins(LY.realBlocks, needSlots, tmp);
         e1.record();
         if (dBadFlags) {
             std::vector<int32_t> bad(n);
             rt_d2h(bad.data(), dBadFlags, n * 4);
-            rt_free(dBadFlags);
-            for (void* q : later) rt_free(q);
+            tmp.release();
             for (size_t i = 0; i < n; i++)
                 if (bad[i]) throw std::runtime_error("parse: back-reference before the start of stream (host check missed it)");
         } else {
             rt_sync();
-            for (void* q : later) rt_free(q);
+            tmp.release();
         }
         msParseKernels += rt_elapsed_ms(e0, e1);
-        rt_free(dSrc);
-        dSrc = nullptr;
-        rt_free(chunkPool.batches); rt_free(chunkPool.next);
+        dSrc.reset();
+        dChunkBatches.reset(); dChunkNext.reset();
         chunkPool = {nullptr, nullptr, 0};
         check_device_errors();
     }
     // 5. static bin statistics of every block's back-reference records (the least-expensive pass works from them);
     //    also fills in the records' first decoded bytes
-    // (queued, not waited for: the caller frees the returned list after its next wait on the stream)
-    void* block_bins(const std::vector<int32_t>& realBlocks, bool needSlots) {
-        if (!needSlots || realBlocks.empty()) return nullptr;
-        int32_t* dReal = (int32_t*)rt_malloc(realBlocks.size() * 4);
-        rt_h2d(dReal, realBlocks.data(), realBlocks.size() * 4);
+    // (queued, not waited for: the block list comes from the caller's scratch, released after its next wait on the stream)
+    void block_bins(const std::vector<int32_t>& realBlocks, bool needSlots, RtScratch& tmp) {
+        if (!needSlots || realBlocks.empty()) return;
+        int32_t* dReal = tmp.upload(realBlocks);
         D4GCtx c = make_ctx(engine().progDyn, 0);
         RT_LAUNCH(k_block_bins, realBlocks.size() * D4G_BINS_SPLIT, 256, c, dReal);
         stats.kernel_launches++;
-        return dReal;
     }
 
     // One optimiseBlock call on every block of `act` (device block indices): runs the program
@@ -1132,16 +1111,17 @@ struct Batch {
     }
     // One optimiseBlock round of one long block with every workgroup of the device (k_search_cluster).  false: the round did
     // not fit the kernel's tables — the block is untouched and the caller uses another executor.
-    D4FClArena* dClArena = nullptr;
+    RtBuf<D4FClArena> dClArena;
     bool run_cluster(int blk, D4GRoundResult* out) {
         Engine& E = engine();
         rt().cur = 0;
-        if (!dClArena) dClArena = (D4FClArena*)rt_malloc(sizeof(D4FClArena));
+        if (!dClArena) dClArena.alloc(1);
         rt_memset(dClArena, 0, 128);   // the epoch counter; every command slot is cleared by the control workgroup before use
         int32_t one = blk;
         rt_h2d(dActive, &one, sizeof(one));
-        D4GRoundResult* dRes = (D4GRoundResult*)rt_malloc(D4F_MAXROUNDS * sizeof(D4GRoundResult));
-        int32_t* dInfo = (int32_t*)rt_malloc(16);
+        RtScratch tmp;
+        D4GRoundResult* dRes = tmp.alloc<D4GRoundResult>(D4F_MAXROUNDS);
+        int32_t* dInfo = tmp.alloc<int32_t>(4);
         D4GCtx c = make_ctx(E.progDyn, 1);
         D4FParams P;
         memset(&P, 0, sizeof(P));
@@ -1151,7 +1131,7 @@ struct Batch {
         P.regWords = env_int("D4G_FUSED_REG_WORDS", 64 * D4F_NWR);
         P.results = dRes;
         P.roundInfo = dInfo;
-        P.stats = getenv("D4G_FUSED_STATS") ? E.dOpStats : nullptr;
+        P.stats = getenv("D4G_FUSED_STATS") ? E.dOpStats.get() : nullptr;
 #ifdef D4G_HOSTSIM
         const int wgs = 3, threads = std::max(128, state_block());
 #else
@@ -1173,7 +1153,7 @@ struct Batch {
         stats.ms_state_kernels += ms;
         stats.state_tokens_per_round += hBlocks[blk].tokCount;
         stats.state_bytes_per_round += hBlocks[blk].uLen;
-        rt_free(dRes); rt_free(dInfo);
+        tmp.release();
         if (getenv("D4G_DEBUG_ROUNDS")) fprintf(stderr, "cluster search: block of %lld back-references, %.3f ms%s\n", (long long)hBlocks[blk].refCount, ms, (info & D4F_INFO_FALLBACK) ? " (did not fit)" : "");
         if ((info & D4F_INFO_FALLBACK) || (info & 0xffff) < 1) return false;
         gpuType[blk] = r.newType;
@@ -1190,6 +1170,7 @@ struct Batch {
         std::vector<std::vector<D4GRoundResult>> chains(act.size());
         std::vector<int> todo(act.size());
         for (size_t i = 0; i < act.size(); i++) todo[i] = (int)i;
+        RtScratch tmp;   // (run_round_legacy below waits before it returns or throws its own errors)
         D4GRoundResult* dRes = nullptr;
         int32_t* dInfo = nullptr;
         while (!todo.empty()) {
@@ -1199,8 +1180,8 @@ struct Batch {
             rt().cur = 0;
             rt_h2d(dActive, sub.data(), sub.size() * sizeof(int32_t));
             if (!dRes) {
-                dRes = (D4GRoundResult*)rt_malloc(act.size() * (size_t)D4F_MAXROUNDS * sizeof(D4GRoundResult));
-                dInfo = (int32_t*)rt_malloc(act.size() * sizeof(int32_t) + 16);
+                dRes = tmp.alloc<D4GRoundResult>(act.size() * (size_t)D4F_MAXROUNDS);
+                dInfo = tmp.alloc<int32_t>(act.size(), 16);
             }
             D4GCtx c = make_ctx(E.progDyn, nA);
             D4FParams P;
@@ -1210,7 +1191,7 @@ struct Batch {
             P.regWords = env_int("D4G_FUSED_REG_WORDS", 64 * D4F_NWR);
             P.results = dRes;
             P.roundInfo = dInfo;
-            P.stats = getenv("D4G_FUSED_STATS") ? E.dOpStats : nullptr;
+            P.stats = getenv("D4G_FUSED_STATS") ? E.dOpStats.get() : nullptr;
             std::vector<int> left(nA);
             int cap = 0;
             for (int i = 0; i < nA; i++) { left[i] = maxRounds - (int)chains[todo[i]].size(); cap = std::max(cap, left[i]); }
@@ -1258,7 +1239,7 @@ struct Batch {
             std::sort(next.begin(), next.end());
             todo.swap(next);
         }
-        rt_free(dRes); rt_free(dInfo);
+        tmp.release();
         return chains;
     }
     bool forceLevels = false;   // the round in hand fell back from the persistent executor
@@ -1660,14 +1641,15 @@ struct Batch {
         std::vector<D4GBlock> src;
         for (auto& kv : blockPatches) { idx.push_back(kv.first); src.push_back(kv.second); }
         blockPatches.clear();
-        int32_t* dIdx = (int32_t*)rt_malloc(idx.size() * 4);
-        D4GBlock* dSrcB = (D4GBlock*)rt_malloc(src.size() * sizeof(D4GBlock));
+        RtScratch tmp;
+        int32_t* dIdx = tmp.alloc<int32_t>(idx.size());
+        D4GBlock* dSrcB = tmp.alloc<D4GBlock>(src.size());
         rt_h2d(dIdx, idx.data(), idx.size() * 4);
         rt_h2d(dSrcB, src.data(), src.size() * sizeof(D4GBlock));
         RT_LAUNCH(k_patch_blocks, idx.size(), 64, dBlocks, dIdx, dSrcB, (int)idx.size());
         stats.kernel_launches++;
         rt_sync();   // (the staging buffers go back to the pool)
-        rt_free(dIdx); rt_free(dSrcB);
+        tmp.release();
     }
     void flush_commits(D4GMergeJob* dJobs) {
         flush_block_patches();
@@ -1681,7 +1663,8 @@ struct Batch {
     }
     void phase_merge() {
         Engine& E = engine();
-        D4GMergeJob* dJobs = (D4GMergeJob*)rt_malloc(2 * streams.size() * sizeof(D4GMergeJob) + 64);
+        RtScratch tmp;
+        D4GMergeJob* dJobs = tmp.alloc<D4GMergeJob>(2 * streams.size(), 64);
         while (true) {
             std::vector<MergeReq> reqs;
             std::vector<D4GMergeJob> jobs;
@@ -1711,7 +1694,7 @@ struct Batch {
             std::vector<D4GRoundResult> res = run_round(act);
             for (size_t i = 0; i < reqs.size(); i++) merge_apply(reqs[i].stream, reqs[i].arena, res[i]);
         }
-        rt_free(dJobs);
+        tmp.release();   // (every round above ended in a wait)
         flush_block_patches();
         check_device_errors();
         for (HStream& s : streams)
@@ -1744,11 +1727,10 @@ struct Batch {
             words += (pos + 31) / 32 + 2;
         }
         outWords = words;
-        dOut = (uint32_t*)rt_malloc((size_t)words * 4 + 64);
-        rt_memset(dOut, 0, (size_t)words * 4 + 64);
+        dOut.alloc_zero((size_t)words, 64);
         if (!jobs.empty()) {
-            D4GWriteJob* dJobs = (D4GWriteJob*)rt_malloc(jobs.size() * sizeof(D4GWriteJob));
-            rt_h2d(dJobs, jobs.data(), jobs.size() * sizeof(D4GWriteJob));
+            RtScratch tmp;
+            D4GWriteJob* dJobs = tmp.upload(jobs);
             D4GCtx c = make_ctx(engine().progDyn, 0);
 #ifdef D4G_HOSTSIM
             const int writeBlock = state_block();
@@ -1758,7 +1740,7 @@ struct Batch {
             RT_LAUNCH(k_write, jobs.size(), writeBlock, c, dJobs, dOut);
             stats.kernel_launches++;
             rt_sync();
-            rt_free(dJobs);
+            tmp.release();
         }
         check_device_errors();
         for (HStream& s : streams)
@@ -1774,10 +1756,10 @@ struct Batch {
         std::vector<long long> base(n + 1, 0);
         for (size_t i = 0; i < n; i++) base[i + 1] = base[i] + (streams[i].status == 0 ? (streams[i].nU + D4G_CSUM_TILE - 1) / D4G_CSUM_TILE : 0);
         long long nTiles = base[n];
-        long long* dBase = (long long*)rt_malloc((n + 1) * 8);
-        rt_h2d(dBase, base.data(), (n + 1) * 8);
-        D4GCsumRec* dCh = (D4GCsumRec*)rt_malloc((size_t)nTiles * sizeof(D4GCsumRec) + 16);
-        D4GCsumOut* dOutC = (D4GCsumOut*)rt_malloc(n * sizeof(D4GCsumOut));
+        RtScratch tmp;
+        long long* dBase = tmp.upload(base);
+        D4GCsumRec* dCh = tmp.alloc<D4GCsumRec>((size_t)nTiles, 16);
+        D4GCsumOut* dOutC = tmp.alloc<D4GCsumOut>(n);
         RtEvent e0, e1;
         e0.record();
         if (nTiles) {
@@ -1790,7 +1772,7 @@ struct Batch {
         csums.resize(n);
         rt_d2h(csums.data(), dOutC, n * sizeof(D4GCsumOut));
         stats.ms_checksum_kernels = rt_elapsed_ms(e0, e1);
-        rt_free(dBase); rt_free(dCh); rt_free(dOutC);
+        tmp.release();
     }
 
     void run(bool merge) {
@@ -1830,22 +1812,12 @@ struct Batch {
     // working set goes back to the memory pool, where the next batch finds it.
     void release_scratch() {
         rt_sync_all();
-        rt_free(dTok); dTok = nullptr;
-        rt_free(dRefs); dRefs = nullptr;
-        rt_free(dTokRef); dTokRef = nullptr;
-        rt_free(dBinStat); dBinStat = nullptr;
-        rt_free(dBinMask); dBinMask = nullptr;
-        rt_free(dHsMemo); dHsMemo = nullptr;
-        rt_free(dRcMemo); dRcMemo = nullptr;
-        rt_free(dPassMemo); dPassMemo = nullptr;
-        rt_free(dBlocks); dBlocks = nullptr;
-        rt_free(dStates); dStates = nullptr;
-        rt_free(dMasks); dMasks = nullptr;
-        rt_free(dKeys); dKeys = nullptr;
-        rt_free(dActive); dActive = nullptr;
-        rt_free(dResults); dResults = nullptr;
-        rt_free(dReady); dReady = nullptr;
-        rt_free(dHeads); dHeads = nullptr;
+        dTok.reset(); dRefs.reset(); dTokRef.reset();
+        dBinStat.reset(); dBinMask.reset();
+        dHsMemo.reset(); dRcMemo.reset(); dPassMemo.reset();
+        dBlocks.reset(); dStates.reset(); dMasks.reset();
+        dKeys.reset(); dActive.reset(); dResults.reset();
+        dReady.reset(); dHeads.reset();
     }
 };
 
@@ -1901,11 +1873,10 @@ inline void verify_items(std::vector<VerifyItem>& items, bool bytesOnHost, Verif
     std::vector<unsigned long long> first(pairs.size(), D4G_VERIFY_NONE);
     if (!pairs.empty()) {
         const size_t np = pairs.size();
-        D4GVerifyPair* dPairs = (D4GVerifyPair*)rt_malloc(np * sizeof(D4GVerifyPair));
-        long long* dBase = (long long*)rt_malloc((np + 1) * 8);
-        unsigned long long* dFirst = (unsigned long long*)rt_malloc(np * 8);
-        rt_h2d(dPairs, pairs.data(), np * sizeof(D4GVerifyPair));
-        rt_h2d(dBase, base.data(), (np + 1) * 8);
+        RtScratch tmp;
+        D4GVerifyPair* dPairs = tmp.upload(pairs);
+        long long* dBase = tmp.upload(base);
+        unsigned long long* dFirst = tmp.alloc<unsigned long long>(np);
         rt_memset(dFirst, 0xff, np * 8);
         RtEvent e0, e1;
         e0.record();
@@ -1913,7 +1884,7 @@ inline void verify_items(std::vector<VerifyItem>& items, bool bytesOnHost, Verif
         e1.record();
         rt_d2h(first.data(), dFirst, np * 8);
         T.msKernels += rt_elapsed_ms(e0, e1);
-        rt_free(dPairs); rt_free(dBase); rt_free(dFirst);
+        tmp.release();
     }
     for (size_t k = 0; k < pairs.size(); k++)
         if (first[k] != D4G_VERIFY_NONE) { items[owner[k]].verdict = VERIFY_BYTES; items[owner[k]].first = (i64)first[k]; }

@@ -51,15 +51,6 @@ inline std::string lz_spec_refusal(const LzSpecL& s, size_t nIn) {
     return "";
 }
 
-// device buffers of the front end that must not outlive it: released before the batch's own phases start, and by the
-// destructor when an exception unwinds the front end
-struct LzScratch {
-    std::vector<void*> v;
-    template <typename T> T* own(T* p) { v.push_back((void*)p); return p; }
-    void release() { for (void* p : v) rt_free(p); v.clear(); }
-    ~LzScratch() { release(); }
-};
-
 struct LzFront {
     Batch& B;
     std::vector<LzSpecL> specs;   // levels resolved (-1 -> 6)
@@ -93,8 +84,7 @@ struct LzFront {
             off += (((i64)len[i] + 15) & ~15LL) + 512;   // zero padding: the kernels read (never use) a few words past the end
             B.stats.bytes_decoded += (i64)len[i];
         }
-        B.dU = (uint8_t*)rt_malloc((size_t)off + 1024);
-        rt_memset(B.dU, 0, (size_t)off + 1024);
+        B.dU.alloc_zero((size_t)off, 1024);
         for (size_t i = 0; i < nIn; i++) {
             if (fromDevice) rt_d2d(B.dU + rawU[i], raw[i], len[i]);
             else rt_h2d(B.dU + rawU[i], raw[i], len[i]);
@@ -145,8 +135,9 @@ struct LzFront {
         for (size_t i = 0; i < nIn; i++)
             if (needSort[i])
                 for (i64 b = 0; b * LZ_SORT_BLOCK < rawLen[i]; b++) sortJobs.push_back({(int32_t)i, (int32_t)b});
-        LzScratch tmp;
-        LzStream* dStreamsLz = tmp.own((LzStream*)rt_malloc(nIn * sizeof(LzStream) + 16));
+        // device buffers of the front end that must not outlive it: released before the batch's own phases start
+        RtScratch tmp;
+        LzStream* dStreamsLz = tmp.alloc<LzStream>(nIn, 16);
         rt_h2d(dStreamsLz, hs.data(), nIn * sizeof(LzStream));
         uint16_t *dS16 = nullptr, *dRank = nullptr, *dBstart = nullptr;
         LzChunkMeta* dMeta = nullptr;
@@ -155,15 +146,15 @@ struct LzFront {
         RtEvent e0, e1, e2;
         e0.record();
         if (!sortJobs.empty()) {
-            dS16 = tmp.own((uint16_t*)rt_malloc((size_t)posTot * 2 + 64));
-            dRank = tmp.own((uint16_t*)rt_malloc((size_t)posTot * 2 + 64));
-            dBstart = tmp.own((uint16_t*)rt_malloc((size_t)posTot * 2 + 64));   // 32768 entries per sort block
-            LzSortJob* dJobs = (LzSortJob*)rt_malloc(sortJobs.size() * sizeof(LzSortJob));
-            rt_h2d(dJobs, sortJobs.data(), sortJobs.size() * sizeof(LzSortJob));
+            dS16 = tmp.alloc<uint16_t>((size_t)posTot, 64);
+            dRank = tmp.alloc<uint16_t>((size_t)posTot, 64);
+            dBstart = tmp.alloc<uint16_t>((size_t)posTot, 64);   // 32768 entries per sort block
+            RtScratch st;
+            LzSortJob* dJobs = st.upload(sortJobs);
             RT_LAUNCH(k_lz_sort, sortJobs.size(), LZ_SORT_THREADS, dStreamsLz, dJobs, dS16, dRank, dBstart);
             B.stats.kernel_launches++;
             rt_sync();
-            rt_free(dJobs);
+            st.release();
         }
         e1.record();
         // ---- 2. parse: speculative pass over every chunk, then exact re-runs until entry == predecessor's exit ----
@@ -171,17 +162,17 @@ struct LzFront {
         c.streams = dStreamsLz; c.S16 = dS16; c.rank16 = dRank; c.bstart = dBstart; c.errors = B.errors();
         c.meta = nullptr; c.chunkTok = nullptr; c.insLive = nullptr; c.insFrozen = nullptr; c.insChg = nullptr;
         if (metaTot > 0) {
-            dMeta = tmp.own((LzChunkMeta*)rt_malloc((size_t)metaTot * sizeof(LzChunkMeta)));
-            dChunkTok = tmp.own((uint32_t*)rt_malloc((size_t)metaTot * (LZ_CHUNK + 2) * 4 + 64));
+            dMeta = tmp.alloc<LzChunkMeta>((size_t)metaTot);
+            dChunkTok = tmp.alloc<uint32_t>((size_t)metaTot * (LZ_CHUNK + 2), 64);
             c.meta = dMeta; c.chunkTok = dChunkTok;
             uint8_t* dFast = nullptr;
             if (insTot > 0) {
-                c.insLive = tmp.own((uint32_t*)rt_malloc((size_t)insTot * 4 + 64));
-                c.insFrozen = tmp.own((uint32_t*)rt_malloc((size_t)insTot * 4 + 64));
-                c.insChg = tmp.own((int32_t*)rt_malloc((size_t)metaTot * 4 + 16));
+                c.insLive = tmp.alloc<uint32_t>((size_t)insTot, 64);
+                c.insFrozen = tmp.alloc<uint32_t>((size_t)insTot, 64);
+                c.insChg = tmp.alloc<int32_t>((size_t)metaTot, 16);
                 rt_memset(c.insLive, 0xff, (size_t)insTot * 4);   // a chunk that has not run yet: "every position inserted"
                 rt_memset(c.insChg, 0xff, (size_t)metaTot * 4);   // -1: never changed
-                dFast = tmp.own((uint8_t*)rt_malloc((size_t)metaTot + 16));
+                dFast = tmp.alloc<uint8_t>((size_t)metaTot, 16);
             }
             auto makeJob = [&](const Parse& P, int firstChunk) {
                 const LzLevelCfg g = lz_level_cfg(P.kind == LZ_KIND_RLE ? 9 : P.level);
@@ -217,13 +208,14 @@ struct LzFront {
                 }
             }
             if (dFast) rt_h2d(dFast, chunkFast.data(), (size_t)metaTot);
-            LzParseJob* dJobs = (LzParseJob*)rt_malloc(std::max(jobs.size(), (size_t)metaTot) * sizeof(LzParseJob) + 16);
+            RtScratch st;
+            LzParseJob* dJobs = st.alloc<LzParseJob>(std::max(jobs.size(), (size_t)metaTot), 16);
             launch(jobs, jobKind, 0, nullptr, 0, dJobs);
             B.stats.lz_parse_passes = 1;
-            int32_t* dIdx = tmp.own((int32_t*)rt_malloc((size_t)metaTot * 4 + 16));
-            int32_t* dRedo = tmp.own((int32_t*)rt_malloc((size_t)metaTot * 4 + 16));
-            uint8_t* dHeads = tmp.own((uint8_t*)rt_malloc((size_t)metaTot + 16));
-            unsigned* dN = tmp.own((unsigned*)rt_malloc(16));
+            int32_t* dIdx = tmp.alloc<int32_t>((size_t)metaTot, 16);
+            int32_t* dRedo = tmp.alloc<int32_t>((size_t)metaTot, 16);
+            uint8_t* dHeads = tmp.alloc<uint8_t>((size_t)metaTot, 16);
+            unsigned* dN = tmp.alloc<unsigned>(4);
             rt_h2d(dIdx, chunkIndex.data(), (size_t)metaTot * 4);
             std::vector<uint8_t> heads((size_t)metaTot);
             for (int pass = 1;; pass++) {
@@ -263,7 +255,7 @@ struct LzFront {
                 B.stats.lz_chunks_rerun += nr;
             }
             rt_d2h(meta.data(), dMeta, (size_t)metaTot * sizeof(LzChunkMeta));
-            rt_free(dJobs);
+            st.release();
         }
         e2.record();
         B.check_device_errors();
@@ -329,11 +321,11 @@ struct LzFront {
         std::vector<LzSplitOut> splitRes((size_t)splitSlots);
         std::vector<int32_t> splitCnt(splitJobs.size());
         if (!splitJobs.empty()) {
-            LzSplitJob* dJ = (LzSplitJob*)rt_malloc(splitJobs.size() * sizeof(LzSplitJob));
-            long long *dA = (long long*)rt_malloc(preSym.size() * 8 + 16), *dBp = (long long*)rt_malloc(preSym.size() * 8 + 16),
-                      *dC = (long long*)rt_malloc(preSym.size() * 8 + 16);
-            LzSplitOut* dO = (LzSplitOut*)rt_malloc((size_t)splitSlots * sizeof(LzSplitOut) + 16);
-            int32_t* dCnt = (int32_t*)rt_malloc(splitJobs.size() * 4 + 16);
+            RtScratch st;
+            LzSplitJob* dJ = st.alloc<LzSplitJob>(splitJobs.size());
+            long long *dA = st.alloc<long long>(preSym.size(), 16), *dBp = st.alloc<long long>(preSym.size(), 16), *dC = st.alloc<long long>(preSym.size(), 16);
+            LzSplitOut* dO = st.alloc<LzSplitOut>((size_t)splitSlots, 16);
+            int32_t* dCnt = st.alloc<int32_t>(splitJobs.size(), 16);
             rt_h2d(dJ, splitJobs.data(), splitJobs.size() * sizeof(LzSplitJob));
             rt_h2d(dA, preSym.data(), preSym.size() * 8);
             rt_h2d(dBp, preRef.data(), preRef.size() * 8);
@@ -342,7 +334,7 @@ struct LzFront {
             B.stats.kernel_launches++;
             rt_d2h(splitRes.data(), dO, (size_t)splitSlots * sizeof(LzSplitOut));
             rt_d2h(splitCnt.data(), dCnt, splitJobs.size() * 4);
-            rt_free(dJ); rt_free(dA); rt_free(dBp); rt_free(dC); rt_free(dO); rt_free(dCnt);
+            st.release();
         }
         size_t splitIdx = 0;
         for (size_t oi = 0; oi < nOut; oi++) {
@@ -392,13 +384,13 @@ struct LzFront {
         // ---- 4. tokens / records in the optimiser's layout ----
         RtEvent e3, e4;
         e3.record();
-        B.dTok = (uint2*)rt_malloc((size_t)tokTot * 8 + 64);
-        B.dRefs = (uint4*)rt_malloc((size_t)refTot * 16 + 64);
-        B.dTokRef = (uint32_t*)rt_malloc((size_t)tokTot * 4 + 64);
+        B.dTok.alloc((size_t)tokTot, 64);
+        B.dRefs.alloc((size_t)refTot, 64);
+        B.dTokRef.alloc((size_t)tokTot, 64);
         const size_t nBlk = blocks.size();
-        LzOutStream* dOuts = tmp.own((LzOutStream*)rt_malloc(nOut * sizeof(LzOutStream) + 16));
-        LzBlockDesc* dBlk = tmp.own((LzBlockDesc*)rt_malloc(nBlk * sizeof(LzBlockDesc) + 16));
-        LzFillJob* dFill = tmp.own((LzFillJob*)rt_malloc(fillJobs.size() * sizeof(LzFillJob) + 16));
+        LzOutStream* dOuts = tmp.alloc<LzOutStream>(nOut, 16);
+        LzBlockDesc* dBlk = tmp.alloc<LzBlockDesc>(nBlk, 16);
+        LzFillJob* dFill = tmp.alloc<LzFillJob>(fillJobs.size(), 16);
         rt_h2d(dOuts, outs.data(), nOut * sizeof(LzOutStream));
         rt_h2d(dBlk, blocks.data(), nBlk * sizeof(LzBlockDesc));
         rt_h2d(dFill, fillJobs.data(), fillJobs.size() * sizeof(LzFillJob));
@@ -412,8 +404,8 @@ struct LzFront {
             else { d.uLen = 0; d.refCount = 0; }
         rt_h2d(dBlk, blocks.data(), nBlk * sizeof(LzBlockDesc));
         // ---- 5. per block: zlib's trees and block type, and the block's state ----
-        D4GState* dTmpStates = tmp.own((D4GState*)rt_malloc(nBlk * sizeof(D4GState) + 16));
-        LzBlockOut* dBo = tmp.own((LzBlockOut*)rt_malloc(nBlk * sizeof(LzBlockOut) + 16));
+        D4GState* dTmpStates = tmp.alloc<D4GState>(nBlk, 16);
+        LzBlockOut* dBo = tmp.alloc<LzBlockOut>(nBlk, 16);
         std::vector<LzBlockOut> bo(nBlk);
         if (nBlk) {
             RT_LAUNCH(k_lz_blocks, nBlk, 64, dStreamsLz, dOuts, dBlk, (int)nBlk, B.dTok, dTmpStates, dBo);
@@ -458,16 +450,18 @@ struct LzFront {
                     const HBlock& hb = B.streams[oi].blocks[b];
                     if (hb.gpu >= 0) dst[outs[oi].blkBase + b] = B.hBlocks[hb.gpu].stateIdx;
                 }
-            long long* dDst = (long long*)rt_malloc(nBlk * 8 + 16);
+            RtScratch st;
+            long long* dDst = st.alloc<long long>(nBlk, 16);
             rt_h2d(dDst, dst.data(), nBlk * 8);
             RT_LAUNCH(k_lz_place_states, nBlk, 256, dTmpStates, dDst, (int)nBlk, B.dStates);
             B.stats.kernel_launches++;
             rt_sync();
-            rt_free(dDst);
+            st.release();
         }
-        void* binList = B.block_bins(LY.realBlocks, optimise);
+        RtScratch bins;
+        B.block_bins(LY.realBlocks, optimise, bins);
         rt_sync();
-        rt_free(binList);
+        bins.release();
         B.stats.ms_lz_sort = rt_elapsed_ms(e0, e1);
         B.stats.ms_lz_parse = rt_elapsed_ms(e1, e2);
         B.stats.ms_lz_emit = rt_elapsed_ms(e3, e4);

@@ -8,6 +8,9 @@
 #include <map>
 #include <string>
 #include <unordered_map>
+#include <atomic>
+#include <utility>
+#include <vector>
 
 #ifndef D4G_HOSTSIM
 #include <hip/hip_runtime.h>
@@ -179,6 +182,11 @@ inline void rt_free(void* p) {
     P.freeBlocks.emplace(c, p);
     P.heldBytes += c;
 }
+inline long long rt_live_blocks() {   // blocks handed out and not yet returned (debug / tests: d4g_debug_device_blocks)
+    std::lock_guard<std::mutex> lk(rtp().mu);
+    RtPool& P = rt_pool();
+    return (long long)P.capacity.size() - (long long)P.freeBlocks.size();
+}
 inline void rt_pool_release() {   // d4g_shutdown
     std::lock_guard<std::mutex> lk(rtp().mu);
     RtPool& P = rt_pool();
@@ -232,3 +240,72 @@ inline float rt_elapsed_ms(RtEvent& a, RtEvent& b) {
     return ms;
 }
 #endif
+
+// ---- device-memory ownership (both builds; the emulator's hipsim.h provides rt_malloc / rt_free / rt_sync_all) ----
+// Blocks handed out and not yet returned (debug / tests: d4g_debug_device_blocks).  The GPU build asks its pool (above);
+// the emulator's rt_malloc / rt_free are calloc / free, so there the two owners count what passes through them.
+#ifdef D4G_HOSTSIM
+inline std::atomic<long long>& rt_live_count() { static std::atomic<long long> n{0}; return n; }
+inline long long rt_live_blocks() { return rt_live_count(); }
+#endif
+inline void* rt_take(size_t n) {
+    void* p = rt_malloc(n);
+#ifdef D4G_HOSTSIM
+    rt_live_count()++;
+#endif
+    return p;
+}
+inline void rt_give(void* p) {
+#ifdef D4G_HOSTSIM
+    if (p) rt_live_count()--;
+#endif
+    rt_free(p);
+}
+// Nothing but rt_take / rt_give calls rt_malloc / rt_free, and nothing but the two owners calls those.  The pool's rule stands: a block goes back only after the work
+// that used it has completed, so the ordinary paths reset() / release() where they have waited for the stream.
+// RtBuf: move-only owner of one pool block, for what lives as long as a Batch, an Engine, a Program or a front end (their
+// destructors wait before the members go).  The conversion to T* keeps kernel argument lists and pointer arithmetic as
+// they were.
+template <typename T>
+struct RtBuf {
+    T* p = nullptr;
+    RtBuf() = default;
+    RtBuf(RtBuf&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    RtBuf& operator=(RtBuf&& o) noexcept { if (this != &o) { reset(); p = std::exchange(o.p, nullptr); } return *this; }
+    ~RtBuf() { reset(); }
+    T* alloc(size_t count, size_t extraBytes = 0) { reset(); return p = (T*)rt_take(count * sizeof(T) + extraBytes); }
+    T* alloc_zero(size_t count, size_t extraBytes = 0) { alloc(count, extraBytes); rt_memset(p, 0, count * sizeof(T) + extraBytes); return p; }
+    void reset() { rt_give(p); p = nullptr; }
+    T* get() const { return p; }
+    operator T*() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+};
+// RtScratch: the temporaries of one phase.  release() is the ordinary path (the caller has waited); the destructor finds
+// blocks only when an exception unwinds the phase, and then waits for the streams first (best effort, as ~Batch does).
+struct RtScratch {
+    std::vector<void*> v;
+    RtScratch() = default;
+    RtScratch(const RtScratch&) = delete;
+    RtScratch& operator=(const RtScratch&) = delete;
+    ~RtScratch() {
+        if (v.empty()) return;
+        try { rt_sync_all(); } catch (...) {}
+        release();
+    }
+    template <typename T> T* alloc(size_t count, size_t extraBytes = 0) {
+        if (v.size() == v.capacity()) v.reserve(2 * v.size() + 8);   // (grow first: a failed push_back must not lose the block)
+        v.push_back(rt_take(count * sizeof(T) + extraBytes));
+        return (T*)v.back();
+    }
+    template <typename T> T* alloc_zero(size_t count, size_t extraBytes = 0) {
+        T* p = alloc<T>(count, extraBytes);
+        rt_memset(p, 0, count * sizeof(T) + extraBytes);
+        return p;
+    }
+    template <typename T> T* upload(const std::vector<T>& h) {
+        T* p = alloc<T>(h.size());
+        rt_h2d(p, h.data(), h.size() * sizeof(T));
+        return p;
+    }
+    void release() { for (void* q : v) rt_give(q); v.clear(); }
+};

@@ -21,7 +21,9 @@ namespace d4g {
 struct ZfSpec { int32_t input, iterations, splitting, maxblocks; long long master; };
 
 struct ZfFront {
-    LzScratch own;
+    // (poolWords before own: members go in reverse order, and own's destructor is the one that waits when an exception unwinds)
+    RtBuf<uint32_t> poolWords;      // the change-point pool's words (pool.words), replaced when the pool grows
+    RtScratch own;                  // everything else the front end makes lives as long as it does
     std::vector<ZfInput> hIn;
     ZfInput* dIn = nullptr;
     ZfPool pool{};
@@ -30,16 +32,7 @@ struct ZfFront {
     double msTable = 0, msSplit = 0, msSqueeze = 0, msEmit = 0;
     i64 squeezeBlocks = 0, squeezePositions = 0;
 
-    template <typename T> T* dalloc(size_t n, bool zero = false) {
-        T* p = own.own((T*)rt_malloc((n ? n : 1) * sizeof(T)));
-        if (zero) rt_memset(p, 0, (n ? n : 1) * sizeof(T));
-        return p;
-    }
-    template <typename T> T* upload(const std::vector<T>& v) {
-        T* p = dalloc<T>(v.size());
-        rt_h2d(p, v.data(), v.size() * sizeof(T));
-        return p;
-    }
+    void release() { own.release(); poolWords.reset(); }   // the ordinary end: the caller has read its results (and so waited)
 
     // inputs: device pointers, 16-byte aligned, with >= 320 readable zero bytes after the end
     void create(size_t n, const uint8_t* const* dData, const i64* len) {
@@ -53,29 +46,29 @@ struct ZfFront {
             in.data = dData[i];
             in.n = len[i];
             const i64 tiles = (len[i] + ZF_KEY_TILE - 1) / ZF_KEY_TILE;
-            in.val = dalloc<uint16_t>((size_t)len[i] + 8);
-            in.same = dalloc<uint16_t>((size_t)len[i] + 8);
-            in.lead = dalloc<uint16_t>((size_t)tiles + 1);
-            in.val2 = dalloc<uint16_t>((size_t)len[i] + 8);
+            in.val = own.alloc<uint16_t>((size_t)len[i] + 8);
+            in.same = own.alloc<uint16_t>((size_t)len[i] + 8);
+            in.lead = own.alloc<uint16_t>((size_t)tiles + 1);
+            in.val2 = own.alloc<uint16_t>((size_t)len[i] + 8);
             const i64 sblocks = (len[i] + ZF_SORT_BLOCK - 1) / ZF_SORT_BLOCK;
             for (int kind = 0; kind < 2; kind++) {
-                in.sorted[kind] = dalloc<uint16_t>((size_t)sblocks * ZF_SORT_BLOCK + 8);
-                in.rank[kind] = dalloc<uint16_t>((size_t)sblocks * ZF_SORT_BLOCK + 8);
-                in.bstart[kind] = dalloc<uint16_t>((size_t)sblocks * ZF_SORT_BLOCK + 8);
+                in.sorted[kind] = own.alloc<uint16_t>((size_t)sblocks * ZF_SORT_BLOCK + 8);
+                in.rank[kind] = own.alloc<uint16_t>((size_t)sblocks * ZF_SORT_BLOCK + 8);
+                in.bstart[kind] = own.alloc<uint16_t>((size_t)sblocks * ZF_SORT_BLOCK + 8);
             }
-            in.table = dalloc<uint32_t>((size_t)len[i] * 8 + 8);
-            in.best = dalloc<uint32_t>((size_t)len[i] + 8);
+            in.table = own.alloc<uint32_t>((size_t)len[i] * 8 + 8);
+            in.best = own.alloc<uint32_t>((size_t)len[i] + 8);
             for (i64 t = 0; t < tiles; t++) kj.push_back({(int32_t)i, (int32_t)t});
             total += len[i];
         }
-        dIn = upload(hIn);
+        dIn = own.upload(hIn);
         pool.cap = (uint32_t)std::min<i64>(total / 2 + (1 << 16), 0x7fff0000LL);
         if (const char* pw = getenv("D4G_ZF_POOL_WORDS")) pool.cap = (uint32_t)std::max(64, atoi(pw));   // tests: start small, exercise the growth
-        pool.words = dalloc<uint32_t>(pool.cap);
-        pool.used = dalloc<uint32_t>(4, true);
+        pool.words = poolWords.alloc(pool.cap);
+        pool.used = own.alloc_zero<uint32_t>(4);
         pool.error = (int32_t*)(pool.used + 1);
         if (!kj.empty()) {
-            ZfKeyJob* dK = upload(kj);
+            ZfKeyJob* dK = own.upload(kj);
             RT_LAUNCH(k_zf_keys_a, kj.size(), 256, dIn, dK);
             RT_LAUNCH(k_zf_keys_b, kj.size(), 256, dIn, dK);
         }
@@ -93,7 +86,7 @@ struct ZfFront {
                 for (i64 b = 0; b * ZF_SORT_BLOCK < len[i]; b++)
                     for (int kind = 0; kind < 2; kind++) sj.push_back({(int32_t)i, (int32_t)b, kind, 0});
             if (!sj.empty()) {
-                ZfSortJob* dS = upload(sj);
+                ZfSortJob* dS = own.upload(sj);
                 RT_LAUNCH(k_zf_sort, sj.size(), ZF_SORT_THREADS, dIn, dS);
             }
             const i64 per = 1024;
@@ -101,7 +94,7 @@ struct ZfFront {
                 for (i64 p = 0; p < len[i]; p += per)
                     mj.push_back({(int32_t)i, (int32_t)std::min<i64>(per, len[i] - p), p, len[i], hIn[i].table + p * 8, hIn[i].best + p});
             if (!mj.empty()) {
-                ZfMatchJob* dM = upload(mj);
+                ZfMatchJob* dM = own.upload(mj);
                 with_pool_retry([&]() { RT_LAUNCH(k_zf_match_sorted, mj.size(), ZF_MS_THREADS, dIn, dM, pool); });
             }
         }
@@ -109,7 +102,7 @@ struct ZfFront {
     }
     void run_match(const std::vector<ZfMatchJob>& mj) {
         if (mj.empty()) return;
-        ZfMatchJob* dM = upload(mj);
+        ZfMatchJob* dM = own.upload(mj);
         with_pool_retry([&]() { RT_LAUNCH(k_zf_match, mj.size(), ZF_MATCH_THREADS, dIn, dM, pool); });
     }
     // The change-point pool is sized for ordinary data (half a word per input byte); inputs whose positions have many
@@ -126,13 +119,15 @@ struct ZfFront {
             if (!st[1]) { poolUsedHost = st[0]; return; }
             if (attempt >= 16 || pool.cap >= 0x7fff0000u) throw std::runtime_error("zopfli match table: change-point pool exhausted");
             const uint32_t newCap = (uint32_t)std::min<i64>((i64)pool.cap * 2, 0x7fff0000LL);
-            uint32_t* nw = dalloc<uint32_t>(newCap);
+            RtBuf<uint32_t> nw;
+            nw.alloc(newCap);
             if (poolUsedHost) rt_d2d(nw, pool.words, (size_t)poolUsedHost * 4);
-            pool.words = nw;
             pool.cap = newCap;
             const uint32_t z[2] = {poolUsedHost, 0};
             rt_h2d(pool.used, z, 8);
             rt_sync();
+            poolWords = std::move(nw);   // (the old words go back after the copy has completed)
+            pool.words = poolWords;
             poolGrowths++;
         }
     }
@@ -147,8 +142,8 @@ struct ZfFront {
         for (auto& e : ends)
             if (!tails.count(e) && e.second > 0) { tails[e] = Tail{0, nullptr, nullptr}; qs.push_back({e.first, 0, e.second}); keys.push_back(e); }
         if (qs.empty()) return;
-        ZfTailQuery* dQ = upload(qs);
-        uint32_t* dT = dalloc<uint32_t>(qs.size());
+        ZfTailQuery* dQ = own.upload(qs);
+        uint32_t* dT = own.alloc<uint32_t>(qs.size());
         RT_LAUNCH(k_zf_tail_len, qs.size(), 64, dIn, dQ, dT);
         std::vector<uint32_t> T(qs.size());
         rt_d2h(T.data(), dT, qs.size() * 4);
@@ -162,8 +157,8 @@ struct ZfFront {
                 t.best = hIn[qs[k].input].best + start;
                 continue;
             }
-            t.table = dalloc<uint32_t>((size_t)(end - start) * 8);
-            t.best = dalloc<uint32_t>((size_t)(end - start));
+            t.table = own.alloc<uint32_t>((size_t)(end - start) * 8);
+            t.best = own.alloc<uint32_t>((size_t)(end - start));
             for (i64 p = start; p < end; p += ZF_TILE)
                 mj.push_back({qs[k].input, (int32_t)std::min<i64>(ZF_TILE, end - p), p, end, t.table + (p - start) * 8, t.best + (p - start)});
         }
@@ -185,7 +180,7 @@ struct ZfFront {
     struct Store { uint16_t* lit = nullptr; uint16_t* dist = nullptr; uint32_t* pos = nullptr; uint32_t size = 0; };
     Store alloc_store(size_t cap) {
         Store s;
-        s.lit = dalloc<uint16_t>(cap + 8); s.dist = dalloc<uint16_t>(cap + 8); s.pos = dalloc<uint32_t>(cap + 8);
+        s.lit = own.alloc<uint16_t>(cap + 8); s.dist = own.alloc<uint16_t>(cap + 8); s.pos = own.alloc<uint32_t>(cap + 8);
         return s;
     }
     static ZfStore dev(const Store& s) { return ZfStore{s.lit, s.dist, s.pos, s.size}; }
@@ -198,16 +193,16 @@ struct ZfFront {
         if (!n) return res;
         std::vector<ZfSplitJob> jobs(n);
         std::vector<uint32_t*> dPts(n), dBp(n);
-        uint32_t* dNp = dalloc<uint32_t>(n + 1, true);
-        int32_t* dErr = (int32_t*)dalloc<uint32_t>(1, true);
+        uint32_t* dNp = own.alloc_zero<uint32_t>(n + 1);
+        int32_t* dErr = (int32_t*)own.alloc_zero<uint32_t>(1);
         for (size_t k = 0; k < n; k++) {
             // unlimited splitting (blocksplittingmax 0): split points are at least ten symbols apart
             const uint32_t cap = maxblocks[k] ? maxblocks[k] : (uint32_t)(stores[k].size / 10 + 2);
-            dPts[k] = dalloc<uint32_t>(cap + 1);
-            dBp[k] = dalloc<uint32_t>(cap + 1);
-            jobs[k] = {dev(stores[k]), maxblocks[k], cap, dalloc<uint8_t>(stores[k].size + 8, true), dPts[k], dBp[k], dNp + k, dErr};
+            dPts[k] = own.alloc<uint32_t>(cap + 1);
+            dBp[k] = own.alloc<uint32_t>(cap + 1);
+            jobs[k] = {dev(stores[k]), maxblocks[k], cap, own.alloc_zero<uint8_t>(stores[k].size + 8), dPts[k], dBp[k], dNp + k, dErr};
         }
-        ZfSplitJob* dJ = upload(jobs);
+        ZfSplitJob* dJ = own.upload(jobs);
         RT_LAUNCH(k_zf_split, n, ZF_SPLIT_WAVES * 64, dJ);
         std::vector<uint32_t> np(n);
         rt_d2h(np.data(), dNp, n * 4);
@@ -224,8 +219,8 @@ struct ZfFront {
     std::vector<ZfRangeOut> run_ranges(const std::vector<ZfRangeJob>& jobs) {
         std::vector<ZfRangeOut> out(jobs.size());
         if (jobs.empty()) return out;
-        ZfRangeJob* dJ = upload(jobs);
-        ZfRangeOut* dO = dalloc<ZfRangeOut>(jobs.size());
+        ZfRangeJob* dJ = own.upload(jobs);
+        ZfRangeOut* dO = own.alloc<ZfRangeOut>(jobs.size());
         RT_LAUNCH(k_zf_range_cost, jobs.size(), 64, dJ, dO);
         rt_d2h(out.data(), dO, jobs.size() * sizeof(ZfRangeOut));
         return out;
@@ -276,12 +271,12 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
             maxb.push_back((uint32_t)specs[m.spec].maxblocks);
         }
         if (!who.empty()) {
-            uint32_t* dCnt = dalloc<uint32_t>(who.size());
+            uint32_t* dCnt = own.alloc<uint32_t>(who.size());
             for (size_t q = 0; q < who.size(); q++) {
                 MB& m = mbs[who[q]];
                 gj.push_back({view(specs[m.spec].input, m.start, m.end), gs[q].lit, gs[q].dist, gs[q].pos, dCnt + q});
             }
-            ZfGreedyJob* dG = upload(gj);
+            ZfGreedyJob* dG = own.upload(gj);
             RT_LAUNCH(k_zf_greedy, gj.size(), 64, dG);
             std::vector<uint32_t> cnt(who.size());
             rt_d2h(cnt.data(), dCnt, who.size() * 4);
@@ -324,7 +319,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
             rep[q] = q;
             const size_t cap = (size_t)(b.end - b.start);
             b.buf[0] = alloc_store(cap); b.buf[1] = alloc_store(cap);
-            b.la = dalloc<uint16_t>(cap + 8); b.path = dalloc<uint32_t>(cap + 8);
+            b.la = own.alloc<uint16_t>(cap + 8); b.path = own.alloc<uint32_t>(cap + 8);
             ZfSqJob j{};
             j.v = view(input, b.start, b.end);
             for (int x = 0; x < 2; x++) { j.lit[x] = b.buf[x].lit; j.dist[x] = b.buf[x].dist; j.pos[x] = b.buf[x].pos; }
@@ -335,8 +330,8 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
             squeezePositions += (b.end - b.start) * j.iterations;
         }
         if (!jobs.empty()) {
-            ZfSqJob* dJ = upload(jobs);
-            ZfSqOut* dO = dalloc<ZfSqOut>(jobs.size());
+            ZfSqJob* dJ = own.upload(jobs);
+            ZfSqOut* dO = own.alloc<ZfSqOut>(jobs.size());
             RT_LAUNCH(k_zf_squeeze, jobs.size(), 64, dJ, dO);
             std::vector<ZfSqOut> outs(jobs.size());
             rt_d2h(outs.data(), dO, jobs.size() * sizeof(ZfSqOut));
@@ -452,7 +447,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
                 Block b{f.mb, (i64)firstPos[q], (i64)firstPos[q] + blen[q], {}, nullptr, nullptr, {}};
                 const size_t cap = (size_t)blen[q];
                 b.buf[0] = alloc_store(cap);
-                b.la = dalloc<uint16_t>(cap + 8); b.path = dalloc<uint32_t>(cap + 8);
+                b.la = own.alloc<uint16_t>(cap + 8); b.path = own.alloc<uint32_t>(cap + 8);
                 ZfSqJob j{};
                 j.v = view(specs[mbs[f.mb].spec].input, b.start, b.end);
                 j.lit[0] = b.buf[0].lit; j.dist[0] = b.buf[0].dist; j.pos[0] = b.buf[0].pos;
@@ -463,8 +458,8 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
                 jobs.push_back(j);
             }
             if (!jobs.empty()) {
-                ZfSqJob* dJ = upload(jobs);
-                ZfSqOut* dO = dalloc<ZfSqOut>(jobs.size());
+                ZfSqJob* dJ = own.upload(jobs);
+                ZfSqOut* dO = own.alloc<ZfSqOut>(jobs.size());
                 RT_LAUNCH(k_zf_squeeze, jobs.size(), 64, dJ, dO);
                 std::vector<ZfSqOut> outs(jobs.size());
                 rt_d2h(outs.data(), dO, jobs.size() * sizeof(ZfSqOut));
@@ -481,7 +476,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
         for (size_t s = 0; s < nS; s++) {
             const i64 n = hIn[specs[s].input].n;
             capWords[s] = (size_t)((n + n / 8 + 1024) / 4 + 64);
-            outWords[s] = dalloc<uint32_t>(capWords[s], true);
+            outWords[s] = own.alloc_zero<uint32_t>(capWords[s]);
         }
         size_t q = 0;
         for (size_t s = 0; s < nS; s++) {
@@ -538,7 +533,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
             outBits[s] = bp;
         }
         if (!ej.empty()) {
-            ZfEmitJob* dE = upload(ej);
+            ZfEmitJob* dE = own.upload(ej);
             RT_LAUNCH(k_zf_emit, ej.size(), 256, dE);
         }
         rt_sync();

@@ -634,15 +634,14 @@ int d4g_inflate(const uint8_t* in, size_t len, uint8_t** out, size_t* out_len, s
 namespace {
 // host inputs -> one padded device buffer (16-byte aligned starts, 512 zero bytes after each end)
 struct ZfUpload {
-    LzScratch own;
+    RtBuf<uint8_t> buf;
     std::vector<const uint8_t*> ptr;
     std::vector<i64> len;
     ZfUpload(size_t n, const uint8_t* const* raw, const size_t* raw_len) {
         i64 off = 0;
         std::vector<i64> at(n);
         for (size_t i = 0; i < n; i++) { at[i] = off; off += (((i64)raw_len[i] + 15) & ~15LL) + 512; }
-        uint8_t* d = own.own((uint8_t*)rt_malloc((size_t)off + 1024));
-        rt_memset(d, 0, (size_t)off + 1024);
+        uint8_t* d = buf.alloc_zero((size_t)off, 1024);
         for (size_t i = 0; i < n; i++) { rt_h2d(d + at[i], raw[i], raw_len[i]); ptr.push_back(d + at[i]); len.push_back((i64)raw_len[i]); }
         rt_sync();
     }
@@ -674,6 +673,7 @@ int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_le
             out_len[i] = (size_t)((zf.outBits[i] + 7) / 8);
             out[i] = host_copy(zf.outWords[i], out_len[i]);
         }
+        zf.release();
         return D4G_OK;
     }));
 }
@@ -710,6 +710,7 @@ int d4g_debug_zopfli_table(const uint8_t* raw, size_t n, size_t end, uint16_t* l
                 fill(w);
             }
         }
+        zf.release();
         return D4G_OK;
     });
 }
@@ -732,12 +733,13 @@ __global__ void __launch_bounds__(64) k_zf_debug_code_lengths(const uint32_t* fr
 int d4g_debug_zopfli_code_lengths(const uint32_t* freq, int n, int maxbits, uint32_t* lengths) {
     if (!freq || !lengths || n < 1 || n > ZF_NUM_LL || maxbits < 1 || maxbits > 15) return fail(D4G_ERR_ARG, "bad argument");
     return api(nullptr, [&] {
-        LzScratch own;
-        uint32_t* dF = own.own((uint32_t*)rt_malloc(n * 4));
-        uint32_t* dO = own.own((uint32_t*)rt_malloc(n * 4));
+        RtScratch tmp;
+        uint32_t* dF = tmp.alloc<uint32_t>(n);
+        uint32_t* dO = tmp.alloc<uint32_t>(n);
         rt_h2d(dF, freq, n * 4);
         RT_LAUNCH(k_zf_debug_code_lengths, 1, 64, dF, n, maxbits, dO);
         rt_d2h(lengths, dO, n * 4);
+        tmp.release();
         return D4G_OK;
     });
 }
@@ -762,14 +764,15 @@ __global__ void __launch_bounds__(64) k_debug_cl_tree(const uint32_t* freq, int 
 int d4g_debug_cl_tree_lengths(const uint32_t* freq, int n, uint32_t* lengths, int32_t* limited) {
     if (!freq || !lengths || !limited || n < 1) return fail(D4G_ERR_ARG, "bad argument");
     return api(nullptr, [&] {
-        LzScratch own;
-        uint32_t* dF = own.own((uint32_t*)rt_malloc((size_t)n * 19 * 4));
-        uint32_t* dO = own.own((uint32_t*)rt_malloc((size_t)n * 19 * 4));
-        int32_t* dL = own.own((int32_t*)rt_malloc((size_t)n * 4));
+        RtScratch tmp;
+        uint32_t* dF = tmp.alloc<uint32_t>((size_t)n * 19);
+        uint32_t* dO = tmp.alloc<uint32_t>((size_t)n * 19);
+        int32_t* dL = tmp.alloc<int32_t>((size_t)n);
         rt_h2d(dF, freq, (size_t)n * 19 * 4);
         RT_LAUNCH(k_debug_cl_tree, (n + 63) / 64, 64, dF, n, dO, dL);
         rt_d2h(lengths, dO, (size_t)n * 19 * 4);
         rt_d2h(limited, dL, (size_t)n * 4);
+        tmp.release();
         return D4G_OK;
     });
 }
@@ -819,7 +822,7 @@ struct CompressRun {
     std::vector<int> winner;             // index in list order, per input
     std::vector<long long> bits;         // its parsed bit size
     std::vector<size_t> off, len;        // its bytes in dWin
-    uint8_t* dWin = nullptr;
+    RtBuf<uint8_t> dWin;
     size_t used = 0;
     size_t perInput = 0;
     d4g_stats agg;
@@ -828,7 +831,6 @@ struct CompressRun {
     int64_t zfBlocks = 0, zfPosIter = 0;
     int64_t outputsOptimised = 0, outputsPruned = 0;
     CompressRun() { memset(&agg, 0, sizeof(agg)); }
-    ~CompressRun() { rt_free(dWin); }
 };
 void add_stats(d4g_stats& a, const d4g_stats& o) {
     a.ms_lz_sort += o.ms_lz_sort; a.ms_lz_parse += o.ms_lz_parse; a.ms_lz_emit += o.ms_lz_emit;
@@ -892,6 +894,7 @@ void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* 
             Z.e3->impl.create(zs.size(), sp.data(), sl.data(), true);
             Z.ms = now_ms() - tz;
             Z.e3->impl.run(merge);
+            zf.release();
         } catch (...) {
             Z.err = std::current_exception();
         }
@@ -932,13 +935,13 @@ void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* 
         }
         std::vector<double> lb(n, 0.0);
         if (!jobs.empty()) {
-            LzBoundJob* dJ = (LzBoundJob*)rt_malloc(jobs.size() * sizeof(LzBoundJob));
-            double* dLb = (double*)rt_malloc(n * 8 + 16);
-            rt_h2d(dJ, jobs.data(), jobs.size() * sizeof(LzBoundJob));
+            RtScratch tmp;
+            LzBoundJob* dJ = tmp.upload(jobs);
+            double* dLb = tmp.alloc<double>(n, 16);
             rt_memset(dLb, 0, n * 8);
             RT_LAUNCH(k_lz_entropy_bound, jobs.size(), 256, dJ, dLb);
             rt_d2h(lb.data(), dLb, n * 8);
-            rt_free(dJ); rt_free(dLb);
+            tmp.release();
         }
         std::vector<size_t> need;
         for (size_t i = 0; i < n; i++) {
@@ -1011,7 +1014,7 @@ void compress_run(CompressRun& R, size_t n, const uint8_t* const* raw, const siz
     R.winner.assign(n, -1); R.bits.assign(n, 0); R.off.assign(n, 0); R.len.assign(n, 0);
     size_t cap = 64;
     for (size_t i = 0; i < n; i++) cap += len[i] + len[i] / 512 + 96;   // a deflate stream never exceeds its input by more than this
-    R.dWin = (uint8_t*)rt_malloc(cap);
+    R.dWin.alloc(cap);
     // group size: the candidate search keeps ~1.6 MB of states per block; estimate >= 3 bytes per symbol and let an
     // out-of-memory failure halve the group
     const long long budget = env_int("D4G_GROUP_BLOCKS", 12000);
@@ -1226,22 +1229,23 @@ int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint
 int d4g_debug_verify_compare(const uint8_t* x, size_t x_skew, const uint8_t* y, size_t y_skew, size_t len, int64_t* first) {
     if ((len && (!x || !y)) || !first || x_skew > 15 || y_skew > 15) return fail(D4G_ERR_ARG, "bad argument");
     return api(nullptr, [&] {
-        LzScratch own;
-        uint8_t* dX = own.own((uint8_t*)rt_malloc(len + 64));
-        uint8_t* dY = own.own((uint8_t*)rt_malloc(len + 64));
+        RtScratch tmp;
+        uint8_t* dX = tmp.alloc<uint8_t>(len, 64);
+        uint8_t* dY = tmp.alloc<uint8_t>(len, 64);
         rt_h2d(dX + x_skew, x, len);
         rt_h2d(dY + y_skew, y, len);
         const D4GVerifyPair pr = {dX + x_skew, dY + y_skew, (long long)len};
         const long long base[2] = {0, ((long long)len + D4G_CSUM_TILE - 1) / D4G_CSUM_TILE};
-        D4GVerifyPair* dPair = own.own((D4GVerifyPair*)rt_malloc(sizeof(pr)));
-        long long* dBase = own.own((long long*)rt_malloc(16));
-        unsigned long long* dFirst = own.own((unsigned long long*)rt_malloc(8));
+        D4GVerifyPair* dPair = tmp.alloc<D4GVerifyPair>(1);
+        long long* dBase = tmp.alloc<long long>(2);
+        unsigned long long* dFirst = tmp.alloc<unsigned long long>(1);
         rt_h2d(dPair, &pr, sizeof(pr));
         rt_h2d(dBase, base, 16);
         rt_memset(dFirst, 0xff, 8);
         if (base[1]) RT_LAUNCH(k_verify_compare, base[1], 256, dPair, dBase, 1, dFirst);
         unsigned long long f = 0;
         rt_d2h(&f, dFirst, 8);
+        tmp.release();
         *first = f == D4G_VERIFY_NONE ? -1 : (int64_t)f;
         return D4G_OK;
     });
@@ -1290,6 +1294,15 @@ long long d4g_test_pack_kinds(void) {
     return bad;
 }
 #endif
+
+// debug and tests only: device-memory blocks the calling thread's context has handed out and not yet got back
+int d4g_debug_device_blocks(int64_t* live) {
+    if (!live) return fail(D4G_ERR_ARG, "null argument");
+    return api(nullptr, [&] {
+        *live = (int64_t)rt_live_blocks();
+        return D4G_OK;
+    });
+}
 
 // dev tool: the fused executor's accounting (collected while D4G_FUSED_STATS is set; see k_search_fused); read and cleared
 int d4g_debug_fused_stats(long long* out64) {

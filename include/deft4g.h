@@ -242,6 +242,10 @@ int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint
  * (Every decoded range the library itself compares starts on a 16-byte boundary; the kernel does not rely on it.) */
 int d4g_debug_verify_compare(const uint8_t* x, size_t x_skew, const uint8_t* y, size_t y_skew, size_t len, int64_t* first);
 
+/* Debug and tests only: *live = device-memory blocks the pool of the calling thread's context (d4g_set_device) has handed
+ * out and not yet got back.  Equal before and after any call — failed ones included — once the batches it made are closed. */
+int d4g_debug_device_blocks(int64_t* live);
+
 /* ---- per-block info: DeflateStream.printBlockInfo (B/deflate/DeflateStream.java:35-51) ----
  * which = 0: stream i as parsed (an encoder batch: as the encoder emitted it); 1: the final stream (the input's list
  * when the stream is unchanged; read off the written bytes otherwise, which verifies the batch if that has not happened).
