@@ -73,7 +73,8 @@ struct ZfFront {
             RT_LAUNCH(k_zf_keys_b, kj.size(), 256, dIn, dK);
         }
         // the shared table: chains enumerated from sorted buckets (D4G_ZF_TABLE=scan: the window-scan kernel the tails use)
-        static const bool scanTable = getenv("D4G_ZF_TABLE") && !strcmp(getenv("D4G_ZF_TABLE"), "scan");
+        const char* tb = getenv("D4G_ZF_TABLE");   // (read per call: the tests switch it inside one process)
+        const bool scanTable = tb && !strcmp(tb, "scan");
         std::vector<ZfMatchJob> mj;
         if (scanTable) {
             for (size_t i = 0; i < n; i++)

@@ -687,6 +687,7 @@ int d4g_debug_zopfli_table(const uint8_t* raw, size_t n, size_t end, uint16_t* l
         ZfFront zf;
         zf.create(1, up.ptr.data(), up.len.data());
         if (end == 0 || end > n) end = n;
+        if (end == 0) { zf.release(); return D4G_OK; }   // the empty input: no position, and no tail to look up
         zf.ensure_tails({{0, (i64)end}});
         const ZfFront::Tail& t = zf.tails.at({0, (i64)end});
         std::vector<uint32_t> table(n * 8 + 8), best(n + 8), pool(zf.pool.cap);

@@ -203,6 +203,9 @@ static void hash_prime(const unsigned char* in, size_t instart, size_t inend, Ha
     for (size_t i = ws; i < instart; i++) hash_update(in, i, inend, h);
 }
 
+/* Searches that ended because the chain walk used up MAX_CHAIN_HITS (tests: does an input reach the cap?); one thread. */
+static unsigned long long g_cap_breaks;
+
 /* Longest match at pos; sublen[l] = distance chosen for length l (may be NULL).  The match cache of the published
  * code only memoises this function's results, so it is not restated. */
 static void find_longest(const Hash* h, const unsigned char* a, size_t pos, size_t size, size_t limit,
@@ -242,7 +245,7 @@ static void find_longest(const Hash* h, const unsigned char* a, size_t pos, size
         if (p == pp) break;
         dist += p < pp ? pp - p : ((WSIZE - p) + pp);
         chain--;
-        if (chain <= 0) break;
+        if (chain <= 0) { g_cap_breaks++; break; }
     }
     (void)hhashval; (void)hval;
     *distance = bestdist;
@@ -1019,3 +1022,5 @@ void zopf_match_table(const unsigned char* in, size_t instart, size_t inend, u16
     }
     hash_free(&h);
 }
+unsigned long long zopf_cap_breaks(void) { return g_cap_breaks; }
+void zopf_cap_breaks_reset(void) { g_cap_breaks = 0; }

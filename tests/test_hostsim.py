@@ -252,15 +252,15 @@ def test_recompress_modes_in_the_emulator(sim):
         D.CompressionUtil(7, lib=L).compress(b"abc")                  # no such RecompressMode: loud failure
 
 
-def test_zopfli_encoder_in_the_emulator(sim):
+def test_zopfli_encoder_in_the_emulator(sim, monkeypatch):
     """The Zopfli kernels on the CPU emulation against the oracle (portable log flavour): code lengths, the match table
     with a block end inside the input, whole streams for the three splitting options, and the recompress modes that use
     them (list order JVM, [JZopfli], CafeUndZopfli, JZlib: C/CompressionUtil.java:44-78)."""
     import ctypes
     import random
-    import numpy as np
     import oracle_compose as OC
     import zopf_lib as ZF
+    import zopfli_table_cases as TC
     D, L = sim
     rng = random.Random(5)
     for n, mb in ((288, 15), (32, 15), (19, 7)):
@@ -272,13 +272,21 @@ def test_zopfli_encoder_in_the_emulator(sim):
             assert L.d4g_debug_zopfli_code_lengths((ctypes.c_uint32 * n)(*f), n, mb, out) == 0
             assert list(out) == ZF.length_limited(f, mb)
     runs = b"".join(bytes([rng.randrange(3)]) * rng.randrange(1, 300) for _ in range(8))
-    for data, end in ((synth.reptext(1000, 5), 600), (runs, len(runs) // 2)):
-        n, e = len(data), end or len(data)
-        l16, d16 = np.zeros(n, np.uint16), np.zeros(n, np.uint16)
-        assert L.d4g_debug_zopfli_table(data, n, end, l16.ctypes.data, d16.ctypes.data, None) == 0
-        ol, od = np.zeros(e, np.uint16), np.zeros(e, np.uint16)
-        ZF.lib().zopf_match_table(data, 0, e, ol.ctypes.data, od.ctypes.data, None)
-        assert np.array_equal(l16[:e], np.where(ol >= 3, ol, 0)) and np.array_equal(d16[:e], np.where(ol >= 3, od, 0))
+    # the table, change points included, under both builds (zopfli_table_cases.py; the GPU test has the inputs with the hard edges)
+    for build in TC.BUILDS:
+        monkeypatch.setenv("D4G_ZF_TABLE", build)
+        for data, end in ((synth.reptext(1000, 5), 600), (runs, len(runs) // 2)):
+            TC.check(L, data, end, what="%s build, end %d:" % (build, end))
+        for name, data in TC.SMALL.items():
+            TC.check(L, data, what="%s build, %s:" % (build, name))
+    monkeypatch.delenv("D4G_ZF_TABLE")
+    # change points beyond an entry's eight: the pool chain as the hook decodes it, in a pool that has to grow three times
+    # (the default build only: every growth runs the launch again, which the emulated window scan takes ten seconds over)
+    monkeypatch.setenv("D4G_ZF_POOL_WORDS", str(TC.EMU_LADDER_POOL))
+    TC.check(L, TC.ladder()[:1500], what="ladder:")
+    o = TC.check(L, TC.ladder_end(TC.EMU_LADDER), what="ladder_end:")
+    assert o.change_points().max() > 8 and TC.pool_words(o) > 4 * TC.EMU_LADDER_POOL
+    monkeypatch.delenv("D4G_ZF_POOL_WORDS")
     text = zlib.decompress(rd("asyoulik_asyoulik-gzip.s00.in.deflate"), -15)
     mix = text[:150] + bytes(rng.randrange(256) for _ in range(80)) + bytes(540) + text[3000:3070]
     for split in (ZF.SPLIT_FIRST, ZF.SPLIT_LAST, ZF.SPLIT_NONE):

@@ -59,3 +59,17 @@ def test_length_limited_codes_match_proxy():
         assert Z.length_limited(f, maxbits) == list(want[pos:pos + len(f)])
         pos += len(f)
     assert pos == len(want)
+
+
+def test_match_table_cases_reach_their_edges():
+    """tests/zopfli_table_cases.py: what each input is for (the hit cap reached, a match at distance 32767 and none at 32768,
+    change points beyond a table entry, a pool that has to grow, block ends inside a run and inside a match), asked of the
+    oracle alone — where the GPU tests ask again before they look at the device."""
+    import zopfli_table_cases as T
+    for c in T.CASES:
+        if c.ends:
+            c.check_ends()
+        if c.cond:
+            c.check_condition(T.Oracle(c.data))
+    o = T.Oracle(T.ladder_end(T.EMU_LADDER))
+    assert o.change_points().max() > 8 and T.pool_words(o) > 4 * T.EMU_LADDER_POOL

@@ -23,6 +23,10 @@ def lib():
         _lib.zopf_portable_log.argtypes = [C.c_double]
         _lib.zopf_portable_log.restype = C.c_double
         _lib.zopf_match_table.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.zopf_cap_breaks.argtypes = []
+        _lib.zopf_cap_breaks.restype = C.c_ulonglong
+        _lib.zopf_cap_breaks_reset.argtypes = []
+        _lib.zopf_cap_breaks_reset.restype = None
     return _lib
 
 
