@@ -54,6 +54,17 @@ class d4g_block_info(ctypes.Structure):
                [(n, ctypes.c_int64) for n in ("bit_pos", "size_bits", "header_bits", "tokens", "decoded_len")]
 
 
+class d4g_parse_error(ctypes.Structure):
+    _fields_ = [("reason", ctypes.c_int32), ("block", ctypes.c_int32)] + \
+               [(n, ctypes.c_int64) for n in ("block_bit_pos", "bit_pos", "decoded_offset", "value")]
+
+
+# D4G_PARSE_*: why a stream did not parse (d4g_batch_parse_error)
+PARSE_OK, PARSE_EOF, PARSE_BLOCK_TYPE, PARSE_STORED_LENGTHS, PARSE_CODE_LENGTHS, PARSE_LITLEN_SYMBOL, PARSE_DIST_SYMBOL, \
+    PARSE_DISTANCE_TOO_FAR = range(8)
+PARSE_REASON_NAMES = {0: "OK", 1: "EOF", 2: "BLOCK_TYPE", 3: "STORED_LENGTHS", 4: "CODE_LENGTHS", 5: "LITLEN_SYMBOL", 6: "DIST_SYMBOL",
+                      7: "DISTANCE_TOO_FAR"}
+
 VERIFY_OK, VERIFY_SKIPPED, VERIFY_PARSE, VERIFY_SIZE, VERIFY_LENGTH, VERIFY_BYTES = 0, 1, -1, -2, -3, -4     # D4G_VERIFY_*
 VERDICT_NAMES = {0: "OK", 1: "SKIPPED", -1: "PARSE", -2: "SIZE", -3: "LENGTH", -4: "BYTES"}
 BLOCK_TYPE_NAMES = ("STORED", "FIXED", "DYNAMIC")           # DeflateBlockType, as printBlockInfo prints it
@@ -69,7 +80,7 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
            "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
            "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
-           "d4g_debug_device_blocks"]
+           "d4g_debug_device_blocks", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name"]
 
 
 def load_library(path=None):
@@ -179,6 +190,12 @@ def load_library(path=None):
     L.d4g_batch_block_info.restype = ctypes.c_int
     L.d4g_batch_block_info.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(d4g_block_info), ctypes.c_size_t,
                                        ctypes.POINTER(ctypes.c_size_t)]
+    L.d4g_batch_parse_error.restype = ctypes.c_int
+    L.d4g_batch_parse_error.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(d4g_parse_error)]
+    L.d4g_diagnose_streams.restype = ctypes.c_int
+    L.d4g_diagnose_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_parse_error)]
+    L.d4g_parse_reason_name.restype = ctypes.c_char_p
+    L.d4g_parse_reason_name.argtypes = [ctypes.c_int]
     if path is None:
         _lib = L
     return L
@@ -240,6 +257,12 @@ def _need():
     if not _ready:
         init()
     return _lib
+
+
+def _parse_error_dict(e):
+    d = {k: getattr(e, k) for k, _ in d4g_parse_error._fields_}
+    d["reason_name"] = PARSE_REASON_NAMES.get(e.reason, "UNKNOWN")
+    return d
 
 
 class Batch:
@@ -356,6 +379,15 @@ class Batch:
             raise RuntimeError("d4g_batch_block_info: " + self.L.d4g_last_error().decode())
         return [{k: getattr(arr[j], k) for k, _ in d4g_block_info._fields_} for j in range(n.value)]
 
+    def parse_error(self, i):
+        """d4g_batch_parse_error: why stream i did not parse -> dict(reason, reason_name, block, block_bit_pos, bit_pos,
+        decoded_offset, value); reason PARSE_OK (and -1 everywhere else) for a stream that parsed."""
+        e = d4g_parse_error()
+        rc = self.L.d4g_batch_parse_error(self.h, i, ctypes.byref(e))
+        if rc != 0:
+            raise RuntimeError("d4g_batch_parse_error: " + self.L.d4g_last_error().decode())
+        return _parse_error_dict(e)
+
     def locate(self, i, offset, final=True):
         """Decoded byte `offset` of stream i -> (block index, byte within that block), by the stream's block list."""
         at = 0
@@ -462,6 +494,21 @@ def verify_streams(a, b, lib=None):
     if rc != 0:
         raise RuntimeError("d4g_verify_streams: " + L.d4g_last_error().decode())
     return [{"verdict": v[i], "first_mismatch": f[i]} for i in range(n)]
+
+
+def diagnose_streams(streams, lib=None):
+    """d4g_diagnose_streams: parse every raw DEFLATE stream and say where and why it fails -> list of the dicts of
+    Batch.parse_error (reason PARSE_OK for the streams that parse)."""
+    L = lib or _need()
+    n = len(streams)
+    keep = [bytes(s) for s in streams]
+    arr = (ctypes.c_char_p * max(1, n))(*keep)
+    lens = (ctypes.c_size_t * max(1, n))(*[len(s) for s in keep])
+    out = (d4g_parse_error * max(1, n))()
+    rc = L.d4g_diagnose_streams(n, arr, lens, out)
+    if rc != 0:
+        raise RuntimeError("d4g_diagnose_streams: " + L.d4g_last_error().decode())
+    return [_parse_error_dict(out[i]) for i in range(n)]
 
 
 ZOPFLI_SPLIT_FIRST, ZOPFLI_SPLIT_LAST, ZOPFLI_SPLIT_NONE = 0, 1, 2     # Options.BlockSplitting (CafeUndZopfli) / blocksplitting[last] (jzopfli)

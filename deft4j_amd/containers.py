@@ -365,14 +365,9 @@ def detect(data):
     return None
 
 
-def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, verify=False):
-    """files: list of bytes.  formats: optional list of container instances / None (auto-detect) / "raw".
-    mode: RecompressMode ordinal of `deft4j optimise --mode` (0 NONE, 1 CHEAP, 2 ZOPFLI, 3 ZOPFLI_EXTENSIVE, 4 ZOPFLI_VERY_EXTENSIVE; M/CMDUtil.java:44-50,76-105): above NONE every
-    stream is also recompressed and the recompression grafted in where it is smaller.
-    Returns [(output bytes or None when unreadable, transcript lines)] — the lines M/CMDUtil.java:64-74 and
-    K/DeflateFilesContainer.java:31-40 print.  Every deflate stream of every file goes to the GPU in one batch.
-    verify: before any file is assembled, every rewritten stream is parsed again on the device and its decoded bytes compared
-    with the original's (Batch.verify); a stream that fails raises RuntimeError naming file, stream, block and offset."""
+def _read_files(files, formats):
+    """-> (container per file or None when unreadable, the deflate payloads of all files in order, (file index, stream
+    name) per payload)"""
     conts = []
     for i, f in enumerate(files):
         c = formats[i] if formats and formats[i] is not None else None
@@ -390,6 +385,40 @@ def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, ver
         for name, pl in sp:
             payloads.append(pl)
             owner.append((i, name))
+    return conts, payloads, owner
+
+
+def explain_failures(files, formats=None, lib=None):
+    """Where the reference prints "Failed to parse deflate stream data": the containers are read as optimise_files reads
+    them, every stream of every file is parsed in one batch, and for each stream that does not parse the answer is
+    dict(file, stream, name, error) — file index, stream index within the file, stream name, and the dict of
+    Batch.parse_error (reason, reason_name, block, block_bit_pos, bit_pos, decoded_offset, value).  Files that cannot be
+    read as a container have no streams and are not listed."""
+    _, payloads, owner = _read_files(files, formats)
+    out = []
+    if not payloads:
+        return out
+    batch = Batch(payloads, lib=lib).parse()
+    try:
+        first = {}
+        for q, (i, name) in enumerate(owner):
+            first.setdefault(i, q)
+            if batch.result(q)["status"] < 0:
+                out.append(dict(file=i, stream=q - first[i], name=name, error=batch.parse_error(q)))
+    finally:
+        batch.close()
+    return out
+
+
+def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, verify=False):
+    """files: list of bytes.  formats: optional list of container instances / None (auto-detect) / "raw".
+    mode: RecompressMode ordinal of `deft4j optimise --mode` (0 NONE, 1 CHEAP, 2 ZOPFLI, 3 ZOPFLI_EXTENSIVE, 4 ZOPFLI_VERY_EXTENSIVE; M/CMDUtil.java:44-50,76-105): above NONE every
+    stream is also recompressed and the recompression grafted in where it is smaller.
+    Returns [(output bytes or None when unreadable, transcript lines)] — the lines M/CMDUtil.java:64-74 and
+    K/DeflateFilesContainer.java:31-40 print.  Every deflate stream of every file goes to the GPU in one batch.
+    verify: before any file is assembled, every rewritten stream is parsed again on the device and its decoded bytes compared
+    with the original's (Batch.verify); a stream that fails raises RuntimeError naming file, stream, block and offset."""
+    conts, payloads, owner = _read_files(files, formats)
     batch = None
     if payloads:
         batch = Batch(payloads, lib=lib)

@@ -639,7 +639,10 @@ struct Batch {
 
     // ---- parse: header scan -> block probes -> chain -> emit -> pointer jumping ----
     struct PBlock { int type, bfinal; i64 bitPos, endBit, nTok, uLen, sizeBits, nRef; int firstBatch; i64 refSpan = -1; i64 hdrBits = 0; };   // refSpan: records the block occupies in refs even when it is STORED (LZ77 front end)
-    struct PStream { int status = 0; std::vector<PBlock> blocks; i64 nTok = 0, nU = 0, consumed = 0, sizeBits = 0; i64 uBaseFixed = -1; };   // uBaseFixed: the decoded bytes already sit in U (LZ77 front end: the raw input)
+    struct PStream {
+        int status = 0; std::vector<PBlock> blocks; i64 nTok = 0, nU = 0, consumed = 0, sizeBits = 0; i64 uBaseFixed = -1;   // uBaseFixed: the decoded bytes already sit in U (LZ77 front end: the raw input)
+        i64 failBlock = -1, failBit = -1, failU = 0;   // status != 0: the block that did not parse (blocks accepted before it), its first bit, the bytes decoded before it
+    };
     std::vector<PStream> ps;
     RtBuf<D4GStreamDesc> dStreams;
     RtBuf<D4GChunkBatch> dChunkBatches;   // the probe's verified chunk starts, replayed by the emit pass: what chunkPool points to
@@ -653,6 +656,7 @@ struct Batch {
     void parse_probe() {
         size_t n = streams.size();
         ps.assign(n, PStream());
+        diagnosed = false; parseErrors.clear();   // (answers of an earlier parse go with it)
         std::vector<D4GStreamDesc> sd(n);
         std::vector<D4GScanTile> tiles;
         i64 totalBytes = 0;
@@ -735,7 +739,11 @@ struct Batch {
         dExOut.alloc(n, 16);
         auto accept = [&](size_t i, i64 bitPos, const D4GProbeOut& o, bool fromScan) {
             PStream& P = ps[i];
-            if (o.status != 0 || o.needHist > upos[i]) { P.status = -1; done[i] = 1; return; }
+            if (o.status != 0 || o.needHist > upos[i]) {
+                P.status = -1; done[i] = 1;
+                P.failBlock = (i64)P.blocks.size(); P.failBit = bitPos; P.failU = upos[i];
+                return;
+            }
             P.blocks.push_back({o.type, o.bfinal, bitPos, o.endBit, o.nTok, o.uLen, o.sizeBits, (i64)o.nRef, fromScan ? o.firstBatch : -1, -1, (i64)o.hdrBits});
             upos[i] += o.uLen;
             P.nTok += o.nTok;
@@ -749,7 +757,10 @@ struct Batch {
             }
             cur[i] = o.endBit;
             if (o.bfinal) { done[i] = 1; P.consumed = (o.endBit + 7) / 8; }
-            else if (o.eofHit) { P.status = -1; done[i] = 1; }  // the next 3-bit read hits EOF
+            else if (o.eofHit) {   // the next 3-bit read hits EOF
+                P.status = -1; done[i] = 1;
+                P.failBlock = (i64)P.blocks.size(); P.failBit = o.endBit; P.failU = upos[i];
+            }
         };
         while (true) {
             std::vector<D4GProbeIn> ex;
@@ -780,6 +791,47 @@ struct Batch {
             ps[i].sizeBits = spos[i];
             if (ps[i].status != 0) { ps[i].blocks.clear(); ps[i].nTok = 0; ps[i].nU = 0; }
         }
+    }
+
+    // ---- why a stream did not parse (d4g_batch_parse_error) ----
+    // One record per stream, made on the first question: a block whose 3 header bits the input no longer holds needs no
+    // kernel (that covers the empty input and a non-final block that ended it); every other failed stream gets one
+    // workgroup of a single k_diagnose_blocks launch.  A batch without failed streams launches and allocates nothing.
+    struct ParseError { int reason = 0; i64 block = -1, blockBit = -1, bitPos = -1, decoded = -1, value = -1; };
+    std::vector<ParseError> parseErrors;
+    bool diagnosed = false;
+    void diagnose() {
+        if (diagnosed) return;
+        const size_t n = std::min(ps.size(), streams.size());
+        std::vector<ParseError> res(streams.size());
+        std::vector<D4GDiagIn> in;
+        std::vector<size_t> owner;
+        for (size_t i = 0; i < n; i++) {
+            const PStream& P = ps[i];
+            if (P.status == 0) continue;
+            ParseError& e = res[i];
+            e.block = P.failBlock; e.blockBit = P.failBit;
+            if (P.failBit + 3 > streams[i].inLen * 8) { e.reason = D4G_DIAG_EOF; e.bitPos = P.failBit; e.decoded = P.failU; continue; }
+            in.push_back({(int32_t)i, 0, P.failBit, P.failU});
+            owner.push_back(i);
+        }
+        if (!in.empty()) {
+            RtScratch tmp;
+            D4GDiagIn* dIn2 = tmp.upload(in);
+            D4GDiagOut* dOut2 = tmp.alloc<D4GDiagOut>(in.size());
+            RT_LAUNCH(k_diagnose_blocks, in.size(), parse_threads(), dStreams, dIn2, dOut2);
+            stats.kernel_launches++;
+            std::vector<D4GDiagOut> o(in.size());
+            rt_d2h(o.data(), dOut2, in.size() * sizeof(D4GDiagOut));
+            tmp.release();
+            for (size_t k = 0; k < in.size(); k++) {
+                if (o[k].reason == D4G_DIAG_OK) throw std::runtime_error("diagnosis: the failing block of stream " + std::to_string(owner[k]) + " decodes");
+                ParseError& e = res[owner[k]];
+                e.reason = o[k].reason; e.bitPos = o[k].bitPos; e.decoded = o[k].decoded; e.value = o[k].value;
+            }
+        }
+        parseErrors.swap(res);
+        diagnosed = true;
     }
 
     // ---- device block table: host block lists, device descriptors and every per-block array, from `ps` ----

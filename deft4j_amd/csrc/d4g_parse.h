@@ -443,9 +443,63 @@ struct D4GParseOut {
     uint32_t* tokRef;   // per token: index of its back-reference record (written for back-references only)
 };
 
-template <bool EMIT>
+// Diagnosis of a block that does not parse (k_diagnose_blocks): the reasons are the D4G_PARSE_* codes of include/deft4g.h.
+enum { D4G_DIAG_OK = 0, D4G_DIAG_EOF, D4G_DIAG_BLOCK_TYPE, D4G_DIAG_STORED_LENGTHS, D4G_DIAG_CODE_LENGTHS, D4G_DIAG_LITLEN_SYMBOL,
+       D4G_DIAG_DIST_SYMBOL, D4G_DIAG_DISTANCE_TOO_FAR };
+struct D4GDiagIn { int32_t stream; int32_t pad; long long bitPos; long long hist; };   // the failing block; bytes decoded before it
+struct D4GDiagOut { int32_t reason; int32_t pad; long long bitPos, decoded, value; };
+struct D4GDiagRec { int reason, firstFar; long long bitPos, decoded, value; };          // the workgroup's record (LDS)
+
+// Why did no code match?  0: one did (sym | len << 16 in `packed`, as d4g_decode_sym_packed returns it); D4G_DIAG_EOF: the input
+// ended inside the code (fewer bits remain than the longest code has, and no code of the bits that remain matches); else -1:
+// the bits are no code of this table.
+__device__ inline int d4g_diag_code(const D4GDecTab* T, uint64_t bits, int avail, int& packed) {
+    // (the bit-serial walk of d4g_decode_sym_packed, kept apart from it: that function is on the parse's hot path and stays
+    // exactly as measured; its LUT path finds the same symbol, since a prefix code has one match)
+    int code = 0, maxLen = 0;
+    for (int l = 1; l <= 15; l++) if (T->count[l]) maxLen = l;
+    for (int l = 1; l <= 15 && l <= avail; l++) {
+        code = (code << 1) | (int)((bits >> (l - 1)) & 1);
+        if (T->count[l] && code >= T->first[l] && code < T->first[l] + T->count[l]) {
+            packed = (int)T->sorted[T->offs[l] + code - T->first[l]] | (l << 16);
+            return 0;
+        }
+    }
+    packed = -1;
+    return avail < maxLen ? D4G_DIAG_EOF : -1;
+}
+// The token that starts at `bits` and does not decode: reason, offset of the failing element from the token's first bit
+// (EOF: the code or extra-bit field that could not be read in full; a symbol error: the token itself), offending value.
+__device__ inline void d4g_diag_token(const D4GDecTab* lit, const D4GDecTab* dist, uint64_t bits, int avail, int& reason, int& off,
+                                      int& value) {
+    int pk;
+    off = 0; value = -1;
+    int c = d4g_diag_code(lit, bits, avail, pk);
+    if (c) { reason = c == D4G_DIAG_EOF ? D4G_DIAG_EOF : D4G_DIAG_LITLEN_SYMBOL; return; }
+    const int sym = pk & 0xffff;
+    int used = pk >> 16;
+    if (sym > 285) { reason = D4G_DIAG_LITLEN_SYMBOL; value = sym; return; }
+    if (sym <= 256) { reason = D4G_DIAG_OK; return; }   // (a token that decodes: not what the parser stopped at)
+    const int eb = d4g_lsym_ebits(sym);
+    if (used + eb > avail) { reason = D4G_DIAG_EOF; off = used; return; }
+    used += eb;
+    c = d4g_diag_code(dist, bits >> used, avail - used, pk);
+    if (c == D4G_DIAG_EOF) { reason = D4G_DIAG_EOF; off = used; return; }
+    if (c) { reason = D4G_DIAG_DIST_SYMBOL; return; }
+    const int ds = pk & 0xffff;
+    if (ds > 29) { reason = D4G_DIAG_DIST_SYMBOL; value = ds; return; }
+    used += pk >> 16;
+    if (used + d4g_dsym_ebits(ds) > avail) { reason = D4G_DIAG_EOF; off = used; return; }
+    reason = D4G_DIAG_OK;
+}
+
+// DIAG (k_diagnose_blocks): the block is known not to parse; the same decode, but every way out records why in `dg`, and the
+// token loop goes on past an invalid code to find the first failure in token order (`hist` = bytes decoded before the block).
+template <bool EMIT, bool DIAG = false>
 __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long long bitPos, int strict, D4GProbeOut& po,
-                                const D4GEmitIn* em, const D4GParseOut& out, const D4GChunkPool& pool) {
+                                const D4GEmitIn* em, const D4GParseOut& out, const D4GChunkPool& pool, D4GDiagRec* dg = nullptr,
+                                long long hist = 0) {
+    static_assert(!(EMIT && DIAG), "a diagnosis writes no tokens");
     __shared__ D4GParseLds L;
     const int tid = threadIdx.x, NL = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = NL >> 6;
     D4GBitReader br;   // thread 0's
@@ -453,6 +507,10 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
     br.nbits = sd.len * 8;
     br.rel = 0; br.posRel = 0; br.limitRel = 0; br.buf = 0; br.cnt = 0;
     D4GState* S = &L.st;
+    // DIAG: one thread records the failure (element position, decoded bytes before it, offending value)
+    [[maybe_unused]] auto diag = [&](int reason, long long bit, long long decoded, long long value) D4G_LAMBDA_INLINE {
+        if constexpr (DIAG) { dg->reason = reason; dg->bitPos = bit; dg->decoded = decoded; dg->value = value; }
+    };
     // workgroup-wide exchange of small values (all threads call; the value of thread 0 / a reduction comes back to all)
     auto bcast = [&](long long v) D4G_LAMBDA_INLINE {
         __syncthreads();
@@ -474,15 +532,20 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
     stage(bitPos);
     long long pk = 0;
     if (tid == 0) {
-        if (!br.have(3)) pk = -1;
-        else { pk = (long long)(br.buf & 7); br.skip(3); }
+        if (!br.have(3)) {
+            pk = -1;
+            if constexpr (DIAG) diag(D4G_DIAG_EOF, bitPos, hist, -1);
+        } else { pk = (long long)(br.buf & 7); br.skip(3); }
     }
     pk = bcast(pk);
     if (pk < 0) return;
     po.bfinal = (int)(pk & 1);
     int btype = (int)(pk >> 1);
     po.type = btype;
-    if (btype == 3) return;
+    if (btype == 3) {
+        if constexpr (DIAG) { if (tid == 0) diag(D4G_DIAG_BLOCK_TYPE, bitPos, hist, 3); }
+        return;
+    }
     if (strict && btype != 2) return;
     if (btype == 0) {
         // DeflateBlockUncompressed.parse — B/deflate/DeflateBlockUncompressed.java:23-36
@@ -492,11 +555,17 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
         long long r = 0, p = 0;
         if (tid == 0) {
             p = (br.pos() + 7) & ~7LL;
-            if (p + 16 > br.nbits) r = -1;
-            else {
+            if (p + 16 > br.nbits) {
+                r = -1;
+                if constexpr (DIAG) diag(D4G_DIAG_EOF, p, hist, -1);
+            } else {
                 br.reset_to(L.inbuf, p);
                 int len = (int)(br.buf & 0xffff), nlen = p + 32 > br.nbits ? 0xffff : (int)((br.buf >> 16) & 0xffff);
                 r = nlen != ((~len) & 0xffff) ? -1 : len;
+                if constexpr (DIAG) {   // a NLEN the input no longer holds is the end of input, not a mismatch
+                    if (r < 0 && p + 32 > br.nbits) diag(D4G_DIAG_EOF, p + 16, hist, -1);
+                    else if (r < 0) diag(D4G_DIAG_STORED_LENGTHS, p, hist, len);
+                }
             }
         }
         r = bcast(r);
@@ -524,15 +593,18 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
         // The fixed code (HuffmanTable.LIT, B/huffman/HuffmanTable.java:166-209) is the RFC 1951 code over
         // 288 symbols; 286/287 take code space but are not decodable symbols (decodeStream rejects > 285).
         for (int i = tid; i < D4G_NLIT; i += NL) S->litLen[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
-        for (int i = tid; i < D4G_NDIST; i += NL) S->distLen[i] = i < 30 ? 5 : 0;
+        // (a diagnosis gives the codes of distance symbols 30 / 31 their lengths too, so that it can name the symbol it refuses)
+        for (int i = tid; i < D4G_NDIST; i += NL) S->distLen[i] = (i < 30 || DIAG) ? 5 : 0;
         if (tid == 0) S->type = D4G_FIXED;
         __syncthreads();
     } else {
         // initDynamicDecoder — DeflateBlockHuffman.java:892-1010
         long long r = 0;
         if (tid == 0) {
-            if (!br.have(14)) r = -1;
-            else {
+            if (!br.have(14)) {
+                r = -1;
+                if constexpr (DIAG) diag(D4G_DIAG_EOF, br.pos(), hist, -1);
+            } else {
                 br.fill(L.inbuf);
                 S->nLit = (int)(br.buf & 31) + 257;
                 S->nDist = (int)((br.buf >> 5) & 31) + 1;
@@ -540,7 +612,10 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
                 br.skip(14);
                 if (S->nLit > 288) r = -1;
                 if (strict && (S->nLit > 286 || S->nDist > 30)) r = -1;
-                if (r == 0 && !br.have(3 * S->nCl)) r = -1;
+                if (r == 0 && !br.have(3 * S->nCl)) {
+                    r = -1;
+                    if constexpr (DIAG) diag(D4G_DIAG_EOF, br.pos() + 3 * (br.avail() / 3), hist, -1);   // the first entry cut short
+                }
                 if (r == 0) {
                     for (int i = 0; i < S->nCl; i++) {
                         br.fill(L.inbuf);
@@ -561,29 +636,56 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
             while (i < combined && r == 0) {
                 br.fill(L.inbuf);
                 int cl = 0, sym;
+                [[maybe_unused]] const long long symPos = DIAG ? br.pos() : 0;
                 D4G_DECODE(&L.cl, br.buf, br.avail(), sym, cl);
-                if (sym < 0 || sym > 18) { r = -1; break; }
+                if (sym < 0 || sym > 18) {
+                    r = -1;
+                    if constexpr (DIAG) {
+                        int pk2;
+                        diag(d4g_diag_code(&L.cl, br.buf, br.avail(), pk2) == D4G_DIAG_EOF ? D4G_DIAG_EOF : D4G_DIAG_CODE_LENGTHS, symPos, hist, -1);
+                    }
+                    break;
+                }
                 br.skip(cl);
                 S->hdrBits += cl;
                 int run = 0, value = sym;
                 if (sym == 16) {
-                    if (i < 1 || !br.have(2)) { r = -1; break; }
+                    if (i < 1 || !br.have(2)) {
+                        r = -1;
+                        if constexpr (DIAG) {
+                            if (i < 1) diag(D4G_DIAG_CODE_LENGTHS, symPos, hist, 16);
+                            else diag(D4G_DIAG_EOF, br.pos(), hist, -1);
+                        }
+                        break;
+                    }
                     run = (int)(br.buf & 3) + 3;
                     br.skip(2); S->hdrBits += 2;
                     value = (i - 1 < S->nLit) ? S->litLen[i - 1] : S->distLen[i - 1 - S->nLit];
                 } else if (sym == 17) {
-                    if (!br.have(3)) { r = -1; break; }
+                    if (!br.have(3)) {
+                        r = -1;
+                        if constexpr (DIAG) diag(D4G_DIAG_EOF, br.pos(), hist, -1);
+                        break;
+                    }
                     run = (int)(br.buf & 7) + 3;
                     br.skip(3); S->hdrBits += 3;
                     value = 0;
                 } else if (sym == 18) {
-                    if (!br.have(7)) { r = -1; break; }
+                    if (!br.have(7)) {
+                        r = -1;
+                        if constexpr (DIAG) diag(D4G_DIAG_EOF, br.pos(), hist, -1);
+                        break;
+                    }
                     run = (int)(br.buf & 127) + 11;
                     br.skip(7); S->hdrBits += 7;
                     value = 0;
                 }
                 int cnt = run ? run : 1;
-                if (i + cnt > combined) { r = -1; break; }
+                if (i + cnt > combined) {
+                    r = -1;
+                    if constexpr (DIAG) diag(D4G_DIAG_CODE_LENGTHS, symPos, hist, sym);
+                    break;
+                }
                 for (int k = 0; k < cnt; k++, i++) {
                     if (i < S->nLit) S->litLen[i] = (uint8_t)value;
                     else S->distLen[i - S->nLit] = (uint8_t)value;
@@ -596,7 +698,10 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
         if (r < 0) return;
     }
     d4g_build_decoder(&L.lit, S->litLen, btype == 1 ? 288 : S->nLit);
-    d4g_build_decoder(&L.dist, S->distLen, btype == 1 ? 30 : S->nDist);
+    // (DIAG: the fixed distance table then has 32 codes and is complete, where the probe's has 30 and is not.  Whether a token
+    // decodes is the same — 30 / 31 are refused as `ds > 29` instead of as "no code" — and nothing below reads L.dist.complete
+    // or L.dist.nCodes unless `strict` is set, which a diagnosis never does.)
+    d4g_build_decoder(&L.dist, S->distLen, btype == 1 ? (DIAG ? 32 : 30) : S->nDist);
     if (btype == 1 && tid == 0) { S->litLen[286] = 0; S->litLen[287] = 0; }
     __syncthreads();
     if (strict) {
@@ -626,10 +731,13 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
     const unsigned uStart32 = EMIT ? (unsigned)em->uStart : 0u;
     long long endBit = 0;
     constexpr int C = D4G_CHUNK_BITS;
-    // one chunk: WRITE = false counts, WRITE = true also stores the tokens (the thread's output offsets are known then)
+    // one chunk: mode 0 counts, mode 1 also stores the tokens (the thread's output offsets are known then), mode 2 (the
+    // diagnosis) stops at the first back-reference that reaches further back than the `uAt` bytes decoded before the chunk
+    [[maybe_unused]] int farPos = 0x7fffffff, farDist = 0;
+    [[maybe_unused]] unsigned farU = 0;
     auto decode_chunk = [&](auto writeTag, int start, int endc, int limRel, unsigned tokAt, unsigned uAt, unsigned refAt, int& exitp,
                             unsigned& n, unsigned& u, unsigned& r, unsigned& lb, int& need, int& fl) D4G_LAMBDA_INLINE {
-        constexpr bool WRITE = decltype(writeTag)::value;
+        constexpr bool WRITE = decltype(writeTag)::value == 1, FAR = decltype(writeTag)::value == 2;
         int pos = start;
         n = 0; u = 0; r = 0; lb = 0; need = -0x40000000; fl = 0;
         while (pos < endc) {
@@ -661,6 +769,9 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
                 int dist = d4g_dsym_base(ds) + (int)((bits >> (used + dcl)) & ((1u << deb) - 1));
                 used += dcl + deb;
                 if (used > avail) { fl = 2; break; }
+                if constexpr (FAR) {
+                    if (dist > (int)uAt + (int)u) { farPos = pos; farDist = dist; farU = u; break; }
+                }
                 if (dist - (int)u > need) need = dist - (int)u;
                 if (WRITE) {
                     atomicAdd(&S->hist[sym], 1u);
@@ -711,7 +822,7 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
             need = -0x40000000;   // (the host checked the distances at probe time)
         } else {
             for (int pass = 0; pass < NL + 2; pass++) {
-                if (dirty) decode_chunk(std::false_type{}, start, endc, limRel, 0u, 0u, 0u, exitp, n, u, r, lb, need, fl);
+                if (dirty) decode_chunk(std::integral_constant<int, 0>{}, start, endc, limRel, 0u, 0u, 0u, exitp, n, u, r, lb, need, fl);
                 // every thread takes its left neighbour's exit (and stop flag)
                 __syncthreads();
                 L.xExit[tid] = exitp;
@@ -735,7 +846,9 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
         __syncthreads();
         const int f = L.firstStop;
         const bool valid = tid <= f;
-        if (f < NL && L.xFlag[f] == 2) return;   // invalid code or out of input: the block does not parse
+        if constexpr (!DIAG) {
+            if (f < NL && L.xFlag[f] == 2) return;   // invalid code or out of input: the block does not parse
+        }
         unsigned pn = valid ? n : 0u, pu = valid ? u : 0u, pr = valid ? r : 0u, plb = valid ? lb : 0u;
         unsigned sn = pn, su = pu, sr = pr;   // inclusive scans: inside the wave, then across waves
         for (int d = 1; d < 64; d <<= 1) {
@@ -760,10 +873,40 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
             __syncthreads();
             for (int w = 0; w < nw; w++) if (L.wsM[w] > needHist) needHist = L.wsM[w];
         }
+        if constexpr (DIAG) {
+            // The first failure in token order.  Threads up to f hold true tokens (thread f: those before its invalid code) and
+            // now know the bytes decoded before their chunk: a second pass finds each chunk's first back-reference that reaches
+            // before the start of the stream.  The first such thread wins; without one, thread f's invalid code is the failure.
+            const long long before = hist + (long long)nU + (long long)(su - pu);
+            if (valid) {
+                int e2, need2, fl2;
+                unsigned n2, u2, r2, lb2;
+                decode_chunk(std::integral_constant<int, 2>{}, start, endc, limRel, 0u, (unsigned)(before > 0x3fffffff ? 0x3fffffff : before), 0u,
+                             e2, n2, u2, r2, lb2, need2, fl2);
+            }
+            __syncthreads();
+            if (tid == 0) dg->firstFar = NL;
+            __syncthreads();
+            if (valid && farPos != 0x7fffffff) atomicMin(&dg->firstFar, tid);
+            __syncthreads();
+            const int ff = dg->firstFar;
+            if (ff < NL) {
+                if (tid == ff) diag(D4G_DIAG_DISTANCE_TOO_FAR, baseBits + farPos, before + farU, farDist);
+                return;
+            }
+            if (f < NL && L.xFlag[f] == 2) {
+                if (tid == f) {
+                    int reason, off, value;
+                    d4g_diag_token(&L.lit, &L.dist, d4g_peek64(L.inbuf, exitp), limRel - exitp, reason, off, value);
+                    diag(reason, baseBits + exitp + off, before + u, value);
+                }
+                return;
+            }
+        }
         if (EMIT && valid) {
             int e2, need2, fl2;
             unsigned n2, u2, r2, lb2;
-            decode_chunk(std::true_type{}, start, endc, limRel, nTok + (sn - pn), nU + (su - pu), nRef + (sr - pr), e2, n2, u2, r2, lb2, need2,
+            decode_chunk(std::integral_constant<int, 1>{}, start, endc, limRel, nTok + (sn - pn), nU + (su - pu), nRef + (sr - pr), e2, n2, u2, r2, lb2, need2,
                          fl2);
             if (replay) exitp = e2;
         }
@@ -843,6 +986,24 @@ __global__ void __launch_bounds__(D4G_PARSE_MAXTHREADS) k_probe_blocks(const D4G
         } else {
             outp[blockIdx.x] = po;
         }
+    }
+}
+
+// Diagnosis: one workgroup per stream whose parse failed decodes the failing block once more and reports the first failure
+// in token order.  Launched only when a caller asks why (d4g_batch_parse_error); nothing on the parse path runs it.
+__global__ void __launch_bounds__(D4G_PARSE_MAXTHREADS) k_diagnose_blocks(const D4GStreamDesc* streams, const D4GDiagIn* in, D4GDiagOut* outp) {
+    __shared__ D4GDiagRec rec;
+    const D4GDiagIn di = in[blockIdx.x];
+    if (threadIdx.x == 0) { rec.reason = D4G_DIAG_OK; rec.firstFar = 0; rec.bitPos = -1; rec.decoded = -1; rec.value = -1; }
+    __syncthreads();
+    D4GProbeOut po;
+    D4GParseOut none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    d4g_parse_block<false, true>(streams[di.stream], di.bitPos, 0, po, nullptr, none, D4GChunkPool{nullptr, nullptr, 0u}, &rec, di.hist);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        D4GDiagOut o;
+        o.reason = rec.reason; o.pad = 0; o.bitPos = rec.bitPos; o.decoded = rec.decoded; o.value = rec.value;
+        outp[blockIdx.x] = o;
     }
 }
 

@@ -216,6 +216,19 @@ int verdicts_to_code(const std::vector<VerifyItem>& items, const std::vector<siz
                                              std::to_string((long long)items[k].first));
     return D4G_OK;
 }
+// ---- why a stream did not parse (Batch::diagnose, d4g_host.h) ----
+static_assert(D4G_DIAG_OK == D4G_PARSE_OK && D4G_DIAG_EOF == D4G_PARSE_EOF && D4G_DIAG_BLOCK_TYPE == D4G_PARSE_BLOCK_TYPE &&
+              D4G_DIAG_STORED_LENGTHS == D4G_PARSE_STORED_LENGTHS && D4G_DIAG_CODE_LENGTHS == D4G_PARSE_CODE_LENGTHS &&
+              D4G_DIAG_LITLEN_SYMBOL == D4G_PARSE_LITLEN_SYMBOL && D4G_DIAG_DIST_SYMBOL == D4G_PARSE_DIST_SYMBOL &&
+              D4G_DIAG_DISTANCE_TOO_FAR == D4G_PARSE_DISTANCE_TOO_FAR, "reason values");
+const d4g_parse_error PARSE_ERROR_NONE = {D4G_PARSE_OK, -1, -1, -1, -1, -1};
+// stream i of a parsed batch (the guard held by the caller; an encoder batch parses nothing: every stream is OK)
+d4g_parse_error batch_parse_error(d4g_batch& b, size_t i) {
+    if (b.lz || b.impl.ps[i].status == 0) return PARSE_ERROR_NONE;
+    b.impl.diagnose();
+    const Batch::ParseError& e = b.impl.parseErrors[i];
+    return d4g_parse_error{e.reason, (int32_t)e.block, e.blockBit, e.bitPos, e.decoded, e.value};
+}
 // has the library written stream i's final bytes?  (an encoder batch writes every output; an optimiser batch only what changed)
 bool stream_written(const d4g_batch& b, size_t i) {
     return b.lz ? b.impl.streams[i].status == 0 : stream_status(b, i) == D4G_STREAM_CHANGED;
@@ -1208,6 +1221,38 @@ int d4g_verify_streams(size_t n, const uint8_t* const* a, const size_t* a_len, c
         }
         return D4G_OK;
     });
+}
+
+int d4g_batch_parse_error(d4g_batch* b, size_t i, d4g_parse_error* out) {
+    return api(b, [&] {
+        if (!b || !out) return fail(D4G_ERR_ARG, "null argument");
+        if (i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
+        if (!b->lz && i >= b->impl.ps.size()) return fail(D4G_ERR_ARG, "the batch has not been parsed");
+        *out = batch_parse_error(*b, i);
+        return D4G_OK;
+    });
+}
+
+int d4g_diagnose_streams(size_t n, const uint8_t* const* in, const size_t* in_len, d4g_parse_error* out) {
+    if (n && (!in || !in_len || !out)) return fail(D4G_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) out[i] = PARSE_ERROR_NONE;
+    return api(nullptr, [&] {
+        std::unique_ptr<d4g_batch> b = make_batch(n, in, in_len);
+        engine().init();
+        b->impl.parse_probe();
+        for (size_t i = 0; i < n; i++) out[i] = batch_parse_error(*b, i);
+        return D4G_OK;
+    });
+}
+
+const char* d4g_parse_reason_name(int reason) {   // (NULL, like the batch creators, when the guard refuses the call)
+    static const char* const names[] = {"OK", "EOF", "BLOCK_TYPE", "STORED_LENGTHS", "CODE_LENGTHS", "LITLEN_SYMBOL", "DIST_SYMBOL", "DISTANCE_TOO_FAR"};
+    const char* name = nullptr;
+    api(nullptr, [&] {
+        name = reason >= 0 && reason < (int)(sizeof(names) / sizeof(names[0])) ? names[reason] : "UNKNOWN";
+        return D4G_OK;
+    });
+    return name;
 }
 
 int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint8_t xor_mask) {

@@ -257,6 +257,43 @@ typedef struct d4g_block_info { int32_t type, bfinal; int64_t bit_pos, size_bits
 int d4g_batch_block_info(d4g_batch* b, size_t i, int which /* 0 = input as parsed, 1 = final stream */, d4g_block_info* out, size_t cap,
                          size_t* n_blocks);
 
+/* ---- why a stream does not parse ----
+ * The reference says "Failed to parse deflate stream data" and no more; here a stream that came back D4G_STREAM_PARSE_ERROR
+ * can be asked where and why.  The answer is the first failure in token order, the one a sequential decoder stops at.
+ * reason / bit_pos (first bit of the element that failed) / value (the offending value, -1 where there is none):
+ *   OK                the stream parsed                                                       -1          -1
+ *   EOF               the input ends inside an element: the 3 header bits (the empty input and a non-final last block
+ *                     included), a stored block's LEN or NLEN, the 14 count bits, a code-length entry, any code or extra-bit
+ *                     field                                  first bit of the field that could not be read in full   -1
+ *   BLOCK_TYPE        BTYPE 3                                 the block's first header bit                 3
+ *   STORED_LENGTHS    NLEN is not the complement of LEN       the byte-aligned position of LEN             LEN
+ *   CODE_LENGTHS      no code-length code matches, a 16 with nothing before it, a run past HLIT + HDIST
+ *                                                             first bit of the code-length symbol          the symbol, -1: no code
+ *   LITLEN_SYMBOL     no literal/length code matches, or symbol 286 / 287      first bit of the token      the symbol, -1: no code
+ *   DIST_SYMBOL       no distance code matches, or symbol 30 / 31              first bit of the token      the symbol, -1: no code
+ *   DISTANCE_TOO_FAR  a back-reference reaches before the first decoded byte   first bit of the token      the distance
+ * block = blocks parsed before the failing one, block_bit_pos = its first header bit, decoded_offset = bytes of the whole
+ * stream decoded before the failing element.  Whether a stream parses is decided by the parser alone; the diagnosis runs
+ * only when asked (the first question about a batch diagnoses all its failed streams in one kernel launch and keeps the
+ * answers), so a batch whose streams all parse never pays for it.  An encoder batch answers OK for every stream. */
+#define D4G_PARSE_OK 0
+#define D4G_PARSE_EOF 1
+#define D4G_PARSE_BLOCK_TYPE 2
+#define D4G_PARSE_STORED_LENGTHS 3
+#define D4G_PARSE_CODE_LENGTHS 4
+#define D4G_PARSE_LITLEN_SYMBOL 5
+#define D4G_PARSE_DIST_SYMBOL 6
+#define D4G_PARSE_DISTANCE_TOO_FAR 7
+typedef struct d4g_parse_error {
+    int32_t reason, block;          /* D4G_PARSE_*; index of the block that failed (-1 when OK) */
+    int64_t block_bit_pos, bit_pos; /* the failing block's first header bit; the failing element's first bit */
+    int64_t decoded_offset;         /* bytes decoded before the failing element */
+    int64_t value;
+} d4g_parse_error;
+int d4g_batch_parse_error(d4g_batch* b, size_t i, d4g_parse_error* out);  /* after parse / run / run_recompress */
+int d4g_diagnose_streams(size_t n, const uint8_t* const* in, const size_t* in_len, d4g_parse_error* out);
+const char* d4g_parse_reason_name(int reason);  /* "OK", "EOF", "BLOCK_TYPE", ...; "UNKNOWN" for any other value; NULL before d4g_init */
+
 /* ---- one-shot wrappers ----
  * Deft.optimiseDeflateStream for n streams: out[i]/out_len[i] are set only when status[i] ==
  * D4G_STREAM_CHANGED (else out[i] = NULL and the caller returns its original array). */

@@ -81,6 +81,11 @@ public final class NativeDeft {
      *  -4 bytes differ.  Parsed and compared on the device; the reference has no counterpart. */
     public static native int[] verifyStreams(byte[][] a, byte[][] b) throws java.io.IOException;
 
+    /** Why stream i of a native batch (a d4g_batch pointer) did not parse: {reason, block, block_bit_pos, bit_pos, decoded_offset, value};
+     *  reason 0: it parsed, 1 EOF, 2 BLOCK_TYPE, 3 STORED_LENGTHS, 4 CODE_LENGTHS, 5 LITLEN_SYMBOL, 6 DIST_SYMBOL, 7 DISTANCE_TOO_FAR
+     *  (include/deft4g.h).  The reference prints "Failed to parse deflate stream data" and nothing more. */
+    public static native long[] parseError(long batch, int i) throws java.io.IOException;
+
     /** Deft.optimiseDeflateStream(byte[], boolean): same contract, including "returns the SAME array when nothing was saved" */
     public static byte[] optimiseDeflateStream(byte[] original, boolean mergeBlocks) {
         final int[] status = new int[1];

@@ -272,3 +272,21 @@ JNIEXPORT jintArray JNICALL JFN(verifyStreams)(JNIEnv* e, jclass c, jobjectArray
     unpin(e, &B);
     return res;
 }
+
+/* long[6] parseError(long batch, int i): why stream i of a d4g_batch did not parse, as {reason (D4G_PARSE_*, 0: it parsed),
+ * block, block_bit_pos, bit_pos, decoded_offset, value}.  `batch` is a d4g_batch* a native caller holds.  The reference only
+ * prints "Failed to parse deflate stream data". */
+JNIEXPORT jlongArray JNICALL JFN(parseError)(JNIEnv* e, jclass c, jlong batch, jint i) {
+    (void)c;
+    d4g_parse_error pe;
+    jlong v[6];
+    jlongArray res = NULL;
+    if (i < 0 || d4g_batch_parse_error((d4g_batch*)(intptr_t)batch, (size_t)i, &pe) != D4G_OK) {
+        throw_io(e, "d4g_batch_parse_error");
+        return NULL;
+    }
+    v[0] = pe.reason; v[1] = pe.block; v[2] = pe.block_bit_pos; v[3] = pe.bit_pos; v[4] = pe.decoded_offset; v[5] = pe.value;
+    res = (*e)->NewLongArray(e, 6);
+    if (res) (*e)->SetLongArrayRegion(e, res, 0, 6, v);
+    return res;
+}
