@@ -116,6 +116,30 @@ static inline int parse_threads() {
     if (v != 64 && v != 128 && v != 256 && v != 512) v = 64;
     return v;
 }
+// How build_blocks resolves the decoded bytes (read per call: the tests switch it inside one process).  "blocks": block-local
+// copies with window markers (k_seg_symbols / k_seg_compose / k_seg_substitute); "doubling": pointer jumping over the whole
+// stream (k_fill_src / k_jump_* / k_resolve_streams); "auto" (the default): blocks, except for a stream that holds a block one
+// workgroup should not walk alone (more than D4G_SEG_MAX_BYTES decoded bytes or D4G_SEG_MAX_TOKENS tokens), which goes the
+// doubling way as a whole.
+enum { D4G_COPY_AUTO = 0, D4G_COPY_DOUBLING = 1, D4G_COPY_BLOCKS = 2 };
+static inline int copy_mode() {
+    const char* t = getenv("D4G_COPY");
+    if (!t || !strcmp(t, "auto")) return D4G_COPY_AUTO;
+    if (!strcmp(t, "doubling")) return D4G_COPY_DOUBLING;
+    if (!strcmp(t, "blocks")) return D4G_COPY_BLOCKS;
+    throw std::runtime_error("D4G_COPY must be doubling, blocks or auto");
+}
+#define D4G_SEG_TARGET_BYTES 8192        // consecutive blocks are gathered into one segment while they decode to no more than this
+#define D4G_SEG_MAX_BYTES (1LL << 20)    // auto: a block beyond either bound sends its stream the doubling way
+#define D4G_SEG_MAX_TOKENS (1LL << 16)
+// threads per workgroup of the block-local copy kernels (the emulator's fibers are slow: there, what the block decoders have)
+static inline int seg_threads() {
+#ifdef D4G_HOSTSIM
+    return parse_threads();
+#else
+    return 1024;
+#endif
+}
 static inline int env_int(const char* name, int def) {
     const char* t = getenv(name);
     return t ? atoi(t) : def;
@@ -995,8 +1019,48 @@ struct Batch {
         Layout LY;
         layout_blocks(merge, needSlots, LY);
         std::vector<D4GEmitIn>& emits = LY.emits;
-        std::vector<D4GTokRange>& ranges = LY.ranges;
-        dSrc.alloc((size_t)uTotal, 64);
+        const std::vector<D4GTokRange>& allRanges = LY.ranges;
+        // route every stream: segments for the block-local copy, or its ranges for the doubling passes
+        const int copyMode = copy_mode();
+        std::vector<D4GTokRange> ranges;          // the doubling way
+        std::vector<char> doubling(n, 0);
+        std::vector<D4GStreamDesc> sdOld;         // their stream table, when other streams go the other way
+        std::vector<D4GSegment> segs;
+        std::vector<D4GSubChunk> chunks;
+        std::vector<int32_t> slotOrd;             // per tail slot: its index among the slots of its stream
+        i64 maxSlots = 0;
+        for (size_t i = 0; i < allRanges.size();) {
+            size_t j = i;
+            const int32_t si = allRanges[i].stream;
+            bool old = copyMode == D4G_COPY_DOUBLING;
+            for (; j < allRanges.size() && allRanges[j].stream == si; j++)
+                if (copyMode == D4G_COPY_AUTO && (allRanges[j].uLen > D4G_SEG_MAX_BYTES || allRanges[j].tokCount > D4G_SEG_MAX_TOKENS)) old = true;
+            if (old) {
+                doubling[si] = 1;
+                ranges.insert(ranges.end(), allRanges.begin() + i, allRanges.begin() + j);
+            } else {
+                const size_t first = segs.size();
+                for (size_t k = i; k < j;) {
+                    size_t e = k + 1;
+                    i64 bytes = allRanges[k].uLen;
+                    while (e < j && bytes + allRanges[e].uLen <= D4G_SEG_TARGET_BYTES) bytes += allRanges[e++].uLen;
+                    segs.push_back({si, (int32_t)k, (int32_t)(e - k), -1, -1, 0, allRanges[k].uStart, bytes});
+                    k = e;
+                }
+                // the tail of every segment but the last is the window of the next one
+                for (size_t q = first; q + 1 < segs.size(); q++) {
+                    segs[q].tail = (int32_t)slotOrd.size();
+                    segs[q + 1].win = segs[q].tail;
+                    slotOrd.push_back((int32_t)(q - first));
+                }
+                maxSlots = std::max(maxSlots, (i64)(segs.size() - first) - 1);
+                for (size_t q = first; q < segs.size(); q++)
+                    for (i64 o = 0; o < segs[q].uLen; o += D4G_SUB_CHUNK)
+                        chunks.push_back({si, segs[q].win, segs[q].uStart + o, std::min<i64>(D4G_SUB_CHUNK, segs[q].uLen - o)});
+            }
+            i = j;
+        }
+        if (!ranges.empty()) dSrc.alloc((size_t)uTotal, 64);
         RtEvent e0, e1;
         e0.record();
         int32_t* dBadFlags = nullptr;     // per stream: a back-reference reached before the start of the stream
@@ -1008,87 +1072,124 @@ struct Batch {
             RT_LAUNCH(k_emit_blocks, emits.size(), parse_threads(), dStreams, dEm, po, errors(), chunkPool);
             stats.kernel_launches++;
             // 4. decoded bytes
-            D4GTokRange* dRanges = tmp.upload(ranges);
             int32_t* dBad = tmp.alloc_zero<int32_t>(n, 16);
-            const int GF = 8;
-            RT_LAUNCH(k_fill_src, ranges.size() * GF, 256, dStreams, dRanges, dTok, dU, dSrc, dBad, GF);
-            stats.kernel_launches++;
-            int G = (int)std::min<i64>(2048, std::max<i64>(1, (maxU + 4095) / 4096));
-            unsigned long long* dChanged = tmp.alloc_zero<unsigned long long>(40);   // one counter per round, zeroed once
-            i64 totalU = 0;
-            for (size_t i = 0; i < n; i++) totalU += ps[i].nU;
-            static int stopPct = -1;   // D4G_JUMP_STOP_PCT: stop doubling once fewer than this share of the bytes still moves
-            if (stopPct < 0) { const char* t = getenv("D4G_JUMP_STOP_PCT"); stopPct = t ? atoi(t) : 50; }
-            const unsigned long long stopNum = std::max<unsigned long long>(1, (unsigned long long)((totalU * stopPct + 99) / 100));   // the resolve pass walks what is left of the chains
-            // the first rounds tile by tile, out of the XCDs' L2 (k_jump_tiles); D4G_JUMP_TILE_REPS=0: plain rounds only
-            static const int tileReps = env_int("D4G_JUMP_TILE_REPS", 6);
-            if (tileReps > 0) {
-                std::vector<D4GJumpTile> tl;
-                for (size_t i = 0; i < n; i++)
-                    for (i64 q = 0; q < ps[i].nU; q += D4G_JUMP_TILE) tl.push_back({(int32_t)i, 0, q});
-                if (!tl.empty()) {
-                    // consecutive tiles -> workgroup ids equal mod 8 (one XCD, one L2): region x of the tile list goes to ids x, x + 8, ...
-                    const size_t nt = tl.size(), per = (nt + 7) / 8;
-                    std::vector<D4GJumpTile> ord(nt);
-                    size_t w = 0;
-                    for (size_t j = 0; j < per; j++)
-                        for (size_t x = 0; x < 8; x++) {
-                            const size_t t = x * per + j;
-                            if (t < nt) ord[w++] = tl[t];
-                        }
-                    D4GJumpTile* dTl = tmp.upload(ord);   // (released with the other parse buffers, after the next wait)
-                    unsigned long long* dCh0 = tmp.alloc_zero<unsigned long long>(2);
-#ifdef D4G_HOSTSIM
-                    RT_LAUNCH(k_jump_tiles, nt, 256, dStreams, dTl, dSrc, tileReps, dCh0);
-#else
-                    {
-                        // 1024 threads per tile and 70 KiB of LDS the kernel never touches: at most two tiles per CU (one beside a
-                        // resident search workgroup), so the tiles of an XCD's CUs and their neighbours stay in its L2 over the
-                        // rounds (2.89 -> 2.66 ms of parse kernels at one tile per CU, 100 KiB; 70 KiB is what several batches in
-                        // flight like best: 12.5-13.0 -> 13.3-13.4 GB/s on config 2)
-                        static const int jt = env_int("D4G_JUMP_THREADS", 1024), jl = env_int("D4G_JUMP_LDS_KB", 70);
-                        if (jl > 64) {   // (more than 64 KiB of dynamic LDS has to be allowed once per device)
-                            static std::atomic<unsigned long long> allowed{0};
-                            int dev = 0;
-                            RT_CHECK(hipGetDevice(&dev));
-                            const unsigned long long bit = 1ull << (dev & 63);
-                            if (!(allowed.load() & bit)) {
-                                RT_CHECK(hipFuncSetAttribute((const void*)k_jump_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, jl * 1024));
-                                allowed.fetch_or(bit);
-                            }
-                        }
-                        hipLaunchKernelGGL(k_jump_tiles, dim3((unsigned)nt), dim3((unsigned)jt), (size_t)jl * 1024, rt().sa(), dStreams, dTl, dSrc, tileReps, dCh0);
-                        RT_CHECK(hipGetLastError());
+            dBadFlags = dBad;   // (no wait in here: the bin statistics follow on the same stream; the flags come back behind them, one wait for both)
+            if (!segs.empty()) {
+                D4GTokRange* dAll = tmp.upload(allRanges);
+                D4GSegment* dSegs = tmp.upload(segs);
+                uint16_t* dSym = tmp.alloc<uint16_t>((size_t)uTotal, 64);
+                const size_t slots = slotOrd.size();
+                uint16_t* dTailA = slots ? tmp.alloc<uint16_t>(slots * D4G_WIN) : nullptr;
+                RT_LAUNCH(k_seg_symbols, segs.size(), seg_threads(), dStreams, dSegs, dAll, dTok, dU, dSym, dTailA, dBad);
+                stats.kernel_launches++;
+                stats.copy_segments += (i64)segs.size();
+                // windows: rounds of the scan are sized from the segment counts, nothing is read back
+                if (maxSlots > 1) {
+                    int32_t* dOrd = tmp.upload(slotOrd);
+                    uint16_t* dTailB = tmp.alloc<uint16_t>(slots * D4G_WIN);
+                    const int GC = 4;
+                    for (i64 d = 1; d < maxSlots; d <<= 1) {
+                        RT_LAUNCH(k_seg_compose, slots * GC, 256, dOrd, dTailA, dTailB, (int)d, GC);
+                        std::swap(dTailA, dTailB);
+                        stats.kernel_launches++;
+                        stats.copy_rounds++;
                     }
+                }
+                if (!chunks.empty()) {
+                    D4GSubChunk* dChunks = tmp.upload(chunks);
+                    RT_LAUNCH(k_seg_substitute, chunks.size(), seg_threads(), dStreams, dChunks, dSym, dTailA, dU);
+                    stats.kernel_launches++;
+                }
+            }
+            if (!ranges.empty()) {
+                // (the doubling passes go stream by stream: they get a stream table in which the other streams are empty)
+                D4GStreamDesc* dStreams = this->dStreams;
+                if (!segs.empty()) {
+                    sdOld.resize(n);
+                    for (size_t i = 0; i < n; i++) sdOld[i] = {dIn ? dIn + streams[i].inOff : nullptr, streams[i].inLen, streams[i].uBase, doubling[i] ? ps[i].nU : 0};
+                    dStreams = tmp.upload(sdOld);
+                }
+                maxU = 0;
+                for (size_t i = 0; i < n; i++) if (doubling[i]) maxU = std::max(maxU, ps[i].nU);
+                D4GTokRange* dRanges = tmp.upload(ranges);
+                const int GF = 8;
+                RT_LAUNCH(k_fill_src, ranges.size() * GF, 256, dStreams, dRanges, dTok, dU, dSrc, dBad, GF);
+                stats.kernel_launches++;
+                int G = (int)std::min<i64>(2048, std::max<i64>(1, (maxU + 4095) / 4096));
+                unsigned long long* dChanged = tmp.alloc_zero<unsigned long long>(40);   // one counter per round, zeroed once
+                i64 totalU = 0;
+                for (size_t i = 0; i < n; i++) if (doubling[i]) totalU += ps[i].nU;
+                static int stopPct = -1;   // D4G_JUMP_STOP_PCT: stop doubling once fewer than this share of the bytes still moves
+                if (stopPct < 0) { const char* t = getenv("D4G_JUMP_STOP_PCT"); stopPct = t ? atoi(t) : 50; }
+                const unsigned long long stopNum = std::max<unsigned long long>(1, (unsigned long long)((totalU * stopPct + 99) / 100));   // the resolve pass walks what is left of the chains
+                // the first rounds tile by tile, out of the XCDs' L2 (k_jump_tiles); D4G_JUMP_TILE_REPS=0: plain rounds only
+                static const int tileReps = env_int("D4G_JUMP_TILE_REPS", 6);
+                if (tileReps > 0) {
+                    std::vector<D4GJumpTile> tl;
+                    for (size_t i = 0; i < n; i++)
+                        for (i64 q = 0; doubling[i] && q < ps[i].nU; q += D4G_JUMP_TILE) tl.push_back({(int32_t)i, 0, q});
+                    if (!tl.empty()) {
+                        // consecutive tiles -> workgroup ids equal mod 8 (one XCD, one L2): region x of the tile list goes to ids x, x + 8, ...
+                        const size_t nt = tl.size(), per = (nt + 7) / 8;
+                        std::vector<D4GJumpTile> ord(nt);
+                        size_t w = 0;
+                        for (size_t j = 0; j < per; j++)
+                            for (size_t x = 0; x < 8; x++) {
+                                const size_t t = x * per + j;
+                                if (t < nt) ord[w++] = tl[t];
+                            }
+                        D4GJumpTile* dTl = tmp.upload(ord);   // (released with the other parse buffers, after the next wait)
+                        unsigned long long* dCh0 = tmp.alloc_zero<unsigned long long>(2);
+#ifdef D4G_HOSTSIM
+                        RT_LAUNCH(k_jump_tiles, nt, 256, dStreams, dTl, dSrc, tileReps, dCh0);
+#else
+                        {
+                            // 1024 threads per tile and 70 KiB of LDS the kernel never touches: at most two tiles per CU (one beside a
+                            // resident search workgroup), so the tiles of an XCD's CUs and their neighbours stay in its L2 over the
+                            // rounds (2.89 -> 2.66 ms of parse kernels at one tile per CU, 100 KiB; 70 KiB is what several batches in
+                            // flight like best: 12.5-13.0 -> 13.3-13.4 GB/s on config 2)
+                            static const int jt = env_int("D4G_JUMP_THREADS", 1024), jl = env_int("D4G_JUMP_LDS_KB", 70);
+                            if (jl > 64) {   // (more than 64 KiB of dynamic LDS has to be allowed once per device)
+                                static std::atomic<unsigned long long> allowed{0};
+                                int dev = 0;
+                                RT_CHECK(hipGetDevice(&dev));
+                                const unsigned long long bit = 1ull << (dev & 63);
+                                if (!(allowed.load() & bit)) {
+                                    RT_CHECK(hipFuncSetAttribute((const void*)k_jump_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, jl * 1024));
+                                    allowed.fetch_or(bit);
+                                }
+                            }
+                            hipLaunchKernelGGL(k_jump_tiles, dim3((unsigned)nt), dim3((unsigned)jt), (size_t)jl * 1024, rt().sa(), dStreams, dTl, dSrc, tileReps, dCh0);
+                            RT_CHECK(hipGetLastError());
+                        }
 #endif
-                    stats.kernel_launches++;
+                        stats.kernel_launches++;
+                    }
                 }
+                const int JB = tileReps > 0 ? 4 : 10;   // rounds per batch: launched back to back, counters read once (after the tile rounds one or two are left)
+                for (int base = 0; base < 40; base += JB) {
+                    for (int round = base; round < base + JB; round++) {
+                        RT_LAUNCH(k_jump_streams, n * (size_t)G, 256, dStreams, dSrc, dChanged + round, G,
+                                  round == 0 ? (const unsigned long long*)nullptr : dChanged + round - 1, stopNum);
+                        stats.kernel_launches++;
+                    }
+                    unsigned long long ch[10];
+                    rt_d2h(ch, dChanged + base, JB * 8);
+                    if (getenv("D4G_DEBUG_JUMP")) {
+                        fprintf(stderr, "jump rounds %d..%d of %lld bytes, moved:", base, base + JB - 1, (long long)totalU);
+                        for (int k = 0; k < JB; k++) fprintf(stderr, " %llu", ch[k]);
+                        fprintf(stderr, "\n");
+                    }
+                    bool done = false;
+                    for (int k = 0; k < JB; k++) {
+                        stats.jump_rounds++;                   // round base + k ran (its predecessor moved enough)
+                        if (ch[k] < stopNum) { done = true; break; }
+                    }
+                    if (done) break;
+                }
+                RT_LAUNCH(k_resolve_streams, n * (size_t)G, 256, dStreams, dSrc, dU, G);
+                stats.kernel_launches++;
             }
-            const int JB = tileReps > 0 ? 4 : 10;   // rounds per batch: launched back to back, counters read once (after the tile rounds one or two are left)
-            for (int base = 0; base < 40; base += JB) {
-                for (int round = base; round < base + JB; round++) {
-                    RT_LAUNCH(k_jump_streams, n * (size_t)G, 256, dStreams, dSrc, dChanged + round, G,
-                              round == 0 ? (const unsigned long long*)nullptr : dChanged + round - 1, stopNum);
-                    stats.kernel_launches++;
-                }
-                unsigned long long ch[10];
-                rt_d2h(ch, dChanged + base, JB * 8);
-                if (getenv("D4G_DEBUG_JUMP")) {
-                    fprintf(stderr, "jump rounds %d..%d of %lld bytes, moved:", base, base + JB - 1, (long long)totalU);
-                    for (int k = 0; k < JB; k++) fprintf(stderr, " %llu", ch[k]);
-                    fprintf(stderr, "\n");
-                }
-                bool done = false;
-                for (int k = 0; k < JB; k++) {
-                    stats.jump_rounds++;                   // round base + k ran (its predecessor moved enough)
-                    if (ch[k] < stopNum) { done = true; break; }
-                }
-                if (done) break;
-            }
-            RT_LAUNCH(k_resolve_streams, n * (size_t)G, 256, dStreams, dSrc, dU, G);
-            stats.kernel_launches++;
-            // (no wait here: the bin statistics follow on the same stream; the flags come back behind them, one wait for both)
-            dBadFlags = dBad;
         }
         block_bins(LY.realBlocks, needSlots, tmp);
         e1.record();

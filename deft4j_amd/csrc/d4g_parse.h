@@ -13,10 +13,11 @@
 //                         probes the few positions the scan cannot see (fixed / stored blocks);
 //   3. k_emit_blocks      one wave per confirmed block decodes again, now writing tokens at
 //                         their final offsets and the block's initial state;
-//   4. k_fill_src / k_jump_streams / k_resolve_streams   decoded bytes by pointer jumping: every
-//                         byte points at the byte it copies (src < position), doubling collapses
-//                         the chains onto literals, then one gather fills U.  No 32 KiB window is
-//                         ever walked serially.
+//   4. k_seg_symbols / k_seg_compose / k_seg_substitute   decoded bytes block by block: 16-bit symbols
+//                         with markers into the 32 KiB before a segment, windows resolved by a scan
+//                         over segments, one substitution pass that writes U (section 4b below);
+//      k_fill_src / k_jump_streams / k_resolve_streams   the same bytes by pointer jumping over the whole
+//                         stream, for streams with a block too long for one workgroup (D4G_COPY).
 // Decoding itself keeps the reference's semantics (LUT fast path; bit-serial canonical fallback
 // identical to Huffman.readSymbol, B/huffman/Huffman.java:170-197; reads past EOF fail).
 #pragma once
@@ -1151,4 +1152,225 @@ __global__ void __launch_bounds__(256) k_resolve_streams(const D4GStreamDesc* st
             u[q] = u[a & ~D4G_SRC_FINAL];
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// 4b. Decoded bytes block by block, with window markers (D4G_COPY=blocks; the two-pass scheme of pugz / rapidgzip).
+// A DEFLATE distance is at most 32 768, so a copy reads what its own segment produced or one of the 32 768 bytes
+// before the segment: a segment (one block, or a run of small blocks of one stream) decodes in one ordered pass
+// without knowing what precedes it.  What it cannot know becomes a marker into that window.
+//   k_seg_symbols      one workgroup per segment: 16-bit symbols (a byte, or D4G_SYM_MARK | i = byte i of the window)
+//                      for every decoded byte, and the segment's last 32 Ki symbols (its "tail": a map from the window
+//                      before the segment to the window after it);
+//   k_seg_compose      tails compose: a logarithmic scan over the segments of a stream resolves every window;
+//   k_seg_substitute   every byte reads its symbol, markers are looked up in the segment's resolved window, U is
+//                      written once.
+// No chain is followed across the stream and no count comes back to the host.
+// ---------------------------------------------------------------------------------------
+#define D4G_WIN 32768
+#define D4G_SEG_GROUP_BYTES 4096    // decoded bytes one group of tokens may produce (what the ring holds beyond the window)
+#define D4G_SEG_GROUP_TOKENS 511    // tokens per group (one more is staged for its position: the end of the group)
+#define D4G_SEG_RING (D4G_WIN + D4G_SEG_GROUP_BYTES)
+#define D4G_SYM_MARK 0x8000u        // | i: byte i of the 32 KiB before the segment
+#define D4G_SYM_PTR 0x4000u         // inside a group only: | offset of the byte of the same group this one copies
+static_assert(((D4G_SEG_GROUP_TOKENS + 1) & D4G_SEG_GROUP_TOKENS) == 0, "the token search takes power-of-two steps");
+static_assert(D4G_SEG_GROUP_BYTES <= 0x4000 && D4G_SEG_GROUP_BYTES >= 258, "a group offset fits a pointer symbol; any token fits a group");
+struct D4GSegment {
+    int32_t stream;
+    int32_t rangeFirst, rangeCount;   // its blocks (D4GTokRange records, consecutive)
+    int32_t tail;                     // slot its tail is written to (-1: nobody needs it)
+    int32_t win;                      // slot that holds its resolved window after the scan (-1: first segment of its stream)
+    int32_t pad;
+    long long uStart, uLen;           // stream-relative decoded range
+};
+#define D4G_SUB_CHUNK 65536         // decoded bytes one workgroup of the substitution pass writes
+struct D4GSubChunk { int32_t stream, win; long long first, count; };
+struct D4GSegLds {
+    uint16_t ring[D4G_SEG_RING];      // symbol of segment-relative position j (j >= -32768) at slot (j + 32768) % D4G_SEG_RING
+    uint32_t pos[D4G_SEG_GROUP_TOKENS + 1];
+    uint32_t a[D4G_SEG_GROUP_TOKENS + 1];
+    int n;
+    int anyPtr[3];
+};
+
+// One group at a time: up to 511 tokens that produce up to 4096 bytes.  Every byte of the group finds its token (binary
+// search over the staged positions) and becomes the literal, the finished symbol of its source (a source before the group
+// is final), or a pointer to its source inside the group; pointer doubling in LDS then resolves the group in at most
+// log2(4096) rounds whatever the tokens are — a run of tokens that each depend on the one before (PNG rows at distance
+// 3-4, long runs) costs rounds, not one round per token.
+__global__ void __launch_bounds__(1024) k_seg_symbols(const D4GStreamDesc* streams, const D4GSegment* segs, const D4GTokRange* ranges,
+                                                                      const uint2* tok, const uint8_t* U, uint16_t* sym, uint16_t* tails,
+                                                                      int32_t* badDist) {
+    __shared__ D4GSegLds L;
+    const int tid = threadIdx.x, NL = blockDim.x;
+    const D4GSegment sg = segs[blockIdx.x];
+    const D4GStreamDesc sd = streams[sg.stream];
+    uint16_t* out = sym + sd.uBase + sg.uStart;
+    const uint32_t segStart = (uint32_t)sg.uStart;
+    for (int i = tid; i < D4G_WIN; i += NL) L.ring[i] = (uint16_t)(D4G_SYM_MARK | (uint32_t)i);
+    if (tid == 0) { L.n = D4G_SEG_GROUP_TOKENS; L.anyPtr[0] = 0; L.anyPtr[1] = 0; L.anyPtr[2] = 0; }
+    __syncthreads();
+    int rr = 0;   // doubling rounds so far (workgroup-uniform): round r raises anyPtr[r % 3]
+    bool bad = false;
+    for (int r = 0; r < sg.rangeCount; r++) {
+        const D4GTokRange rg = ranges[sg.rangeFirst + r];
+        const uint32_t b0 = (uint32_t)(rg.uStart - sg.uStart), bLen = (uint32_t)rg.uLen;
+        if (rg.stored) {   // the emit pass has put the bytes into U
+            const uint8_t* u = U + sd.uBase + rg.uStart;
+            for (uint32_t k = tid; k < bLen; k += NL) {
+                const uint16_t v = u[k];
+                if (bLen - k <= D4G_WIN) L.ring[(b0 + k + D4G_WIN) % D4G_SEG_RING] = v;   // (what a later copy can reach)
+                out[b0 + k] = v;
+            }
+            __syncthreads();
+            continue;
+        }
+        const uint2* tk = tok + rg.tokStart;
+        long long t0 = 0;
+        uint32_t gs = b0;
+        uint2 pre = make_uint2(0u, 0u);
+        if (tid < rg.tokCount) pre = tk[tid];
+        while (t0 < rg.tokCount) {
+            const long long left = rg.tokCount - t0;
+            const int m = left < D4G_SEG_GROUP_TOKENS ? (int)left : D4G_SEG_GROUP_TOKENS, m1 = left < D4G_SEG_GROUP_TOKENS + 1 ? (int)left : D4G_SEG_GROUP_TOKENS + 1;
+            // stage the tokens; the group ends before the first one whose bytes would pass the group's byte bound
+            for (int i = tid; i <= D4G_SEG_GROUP_TOKENS; i += NL) {
+                if (i >= m1) { L.pos[i] = 0xffffffffu; continue; }   // (the search below may look at any staged slot)
+                const uint2 t = i == tid ? pre : tk[t0 + i];
+                const uint32_t p = t.y - segStart;
+                const int dist = tok_dist(t.x), val = tok_val(t.x);
+                const uint32_t len = dist ? (uint32_t)val : (val < 256 ? 1u : 0u);
+                L.pos[i] = p;
+                L.a[i] = t.x;
+                if (i < m && p + len - gs > D4G_SEG_GROUP_BYTES) atomicMin(&L.n, i);
+            }
+            __syncthreads();
+            const int n = L.n < m ? L.n : m;
+            const uint32_t ge = n < m1 ? L.pos[n] : b0 + bLen;
+            if (t0 + n + tid < rg.tokCount) pre = tk[t0 + n + tid];   // the next group's tokens, asked for now
+            // K bytes per thread side by side: the LDS reads of a step are independent of each other and overlap
+            constexpr int K = 4;
+            for (uint32_t base = gs + tid; base < ge; base += K * NL) {
+                uint32_t j[K], e[K];
+                int lo[K];
+#pragma unroll
+                for (int k = 0; k < K; k++) { j[k] = base + k * NL; lo[k] = 0; }
+                // the last token that starts at or before j (an end-of-block token has no bytes and is last): tokens from n on
+                // start at or after the group's end, the slots past the staged ones hold the largest position
+#pragma unroll
+                for (int st = (D4G_SEG_GROUP_TOKENS + 1) / 2; st > 0; st >>= 1) {
+#pragma unroll
+                    for (int k = 0; k < K; k++)
+                        if (L.pos[lo[k] + st] <= j[k]) lo[k] += st;
+                }
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const bool in = j[k] < ge;
+                    const uint32_t a = L.a[in ? lo[k] : 0];
+                    const uint32_t dist = in ? (uint32_t)tok_dist(a) : 0u;
+                    const uint32_t back = L.ring[(j[k] + D4G_WIN - dist) % D4G_SEG_RING];   // (final if it lies before the group, unused otherwise)
+                    if (!dist) e[k] = a & 0xffu;
+                    else if (dist > segStart + j[k]) { e[k] = 0; bad = true; }   // before the start of the stream
+                    else if (j[k] - gs >= dist) e[k] = D4G_SYM_PTR | (j[k] - dist - gs);
+                    else e[k] = back;
+                }
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    if (j[k] < ge) L.ring[(j[k] + D4G_WIN) % D4G_SEG_RING] = (uint16_t)e[k];
+            }
+            __syncthreads();
+            if (tid == 0) L.n = D4G_SEG_GROUP_TOKENS;
+            // in place and unsynchronised, like k_jump_streams: any value read is further up the same chain, or final
+            for (;;) {
+                bool mine = false;
+                for (uint32_t base = gs + tid; base < ge; base += K * NL) {
+                    uint32_t e[K], e2[K];
+#pragma unroll
+                    for (int k = 0; k < K; k++) e[k] = base + k * NL < ge ? L.ring[(base + k * NL + D4G_WIN) % D4G_SEG_RING] : 0u;
+#pragma unroll
+                    for (int k = 0; k < K; k++) e2[k] = L.ring[(gs + (e[k] & 0x3fffu) + D4G_WIN) % D4G_SEG_RING];
+#pragma unroll
+                    for (int k = 0; k < K; k++)
+                        if ((e[k] & 0xc000u) == D4G_SYM_PTR) {
+                            L.ring[(base + k * NL + D4G_WIN) % D4G_SEG_RING] = (uint16_t)e2[k];
+                            mine |= (e2[k] & 0xc000u) == D4G_SYM_PTR;
+                        }
+                }
+                if (mine) L.anyPtr[rr % 3] = 1;
+                if (tid == 0) L.anyPtr[(rr + 1) % 3] = 0;   // (last read two barriers ago)
+                __syncthreads();
+                const int any = L.anyPtr[rr % 3];
+                rr++;
+                if (!any) break;
+            }
+            for (uint32_t j = gs + tid; j < ge; j += NL) out[j] = L.ring[(j + D4G_WIN) % D4G_SEG_RING];
+            gs = ge;
+            t0 += n;
+        }
+        __syncthreads();   // (a stored block that follows rewrites most of the ring)
+    }
+    if (bad) badDist[sg.stream] = 1;  // reference: readSlice walks off the first block (NullPointerException)
+    if (sg.tail >= 0) {
+        __syncthreads();
+        uint16_t* t = tails + (long long)sg.tail * D4G_WIN;
+        const uint32_t q0 = (uint32_t)sg.uLen;
+        for (int i = tid; i < D4G_WIN; i += NL) t[i] = L.ring[(q0 + (uint32_t)i) % D4G_SEG_RING];
+    }
+}
+
+// One round of the scan over tail slots (the slots of a stream are consecutive; ord = index inside the stream): slot s
+// takes the markers of its map through the map of slot s - d.  Ping-pong, not in place: `out` is complete after the round.
+__global__ void __launch_bounds__(256) k_seg_compose(const int32_t* slotOrd, const uint16_t* in, uint16_t* out, int d, int G) {
+    const long long slot = blockIdx.x / G;
+    const bool look = slotOrd[slot] >= d;
+    const uint4* a = (const uint4*)(in + slot * D4G_WIN);
+    uint4* o = (uint4*)(out + slot * D4G_WIN);
+    const uint16_t* prev = in + (slot - (look ? d : 0)) * D4G_WIN;
+    auto via = [&](uint32_t w) D4G_LAMBDA_INLINE {   // two symbols
+        uint32_t lo = w & 0xffffu, hi = w >> 16;
+        if (lo & D4G_SYM_MARK) lo = prev[lo & 0x7fffu];
+        if (hi & D4G_SYM_MARK) hi = prev[hi & 0x7fffu];
+        return lo | (hi << 16);
+    };
+    for (int i = (blockIdx.x % G) * blockDim.x + threadIdx.x; i < D4G_WIN / 8; i += G * blockDim.x) {
+        uint4 v = a[i];
+        if (look && ((v.x | v.y | v.z | v.w) & 0x80008000u)) v = make_uint4(via(v.x), via(v.y), via(v.z), via(v.w));
+        o[i] = v;
+    }
+}
+
+__global__ void __launch_bounds__(1024) k_seg_substitute(const D4GStreamDesc* streams, const D4GSubChunk* chunks, const uint16_t* sym,
+                                                        const uint16_t* tails, uint8_t* U) {
+    alignas(16) __shared__ uint8_t W[D4G_WIN];
+    const D4GSubChunk c = chunks[blockIdx.x];
+    const D4GStreamDesc sd = streams[c.stream];
+    const int tid = threadIdx.x, NL = blockDim.x;
+    const bool hasWin = c.win >= 0;
+    auto low2 = [](uint32_t w) D4G_LAMBDA_INLINE { return (w & 0xffu) | ((w >> 8) & 0xff00u); };   // the low bytes of two symbols
+    if (hasWin) {
+        // (a marker left in a resolved window points before the start of the stream: only a stream with a bad distance has one)
+        const uint4* t = (const uint4*)(tails + (long long)c.win * D4G_WIN);
+        for (int i = tid; i < D4G_WIN / 8; i += NL) {
+            const uint4 v = t[i];
+            *(uint2*)(W + i * 8) = make_uint2(low2(v.x) | (low2(v.y) << 16), low2(v.z) | (low2(v.w) << 16));
+        }
+        __syncthreads();
+    }
+    const uint16_t* s = sym + sd.uBase;
+    uint8_t* u = U + sd.uBase;
+    auto res = [&](uint32_t h) D4G_LAMBDA_INLINE -> uint32_t { return (hasWin && (h & D4G_SYM_MARK)) ? W[h & 0x7fffu] : (h & 0xffu); };
+    auto res2 = [&](uint32_t w) D4G_LAMBDA_INLINE -> uint32_t { return res(w & 0xffffu) | (res(w >> 16) << 8); };
+    const long long a = c.first, b = c.first + c.count;
+    long long a8 = (a + 7) & ~7LL, b8 = b & ~7LL;
+    if (a8 > b) a8 = b;
+    if (b8 < a8) b8 = a8;
+    for (long long q = a + tid; q < a8; q += NL) u[q] = (uint8_t)res(s[q]);
+    for (long long q = a8 + (long long)tid * 8; q < b8; q += (long long)NL * 8) {   // uBase is a multiple of 16: aligned 16-byte loads, 8-byte stores
+        const uint4 v = *(const uint4*)(s + q);
+        uint2 w;
+        if ((v.x | v.y | v.z | v.w) & 0x80008000u) w = make_uint2(res2(v.x) | (res2(v.y) << 16), res2(v.z) | (res2(v.w) << 16));
+        else w = make_uint2(low2(v.x) | (low2(v.y) << 16), low2(v.z) | (low2(v.w) << 16));
+        *(uint2*)(u + q) = w;
+    }
+    for (long long q = b8 + tid; q < b; q += NL) u[q] = (uint8_t)res(s[q]);
 }

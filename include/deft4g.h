@@ -80,6 +80,9 @@ typedef struct d4g_stats {
      * streams plus the byte compare (HIP events); streams verified; decoded bytes compared */
     double ms_verify, ms_verify_kernels;
     int64_t verify_streams, verify_bytes;
+    /* decoded bytes by block-local copies (D4G_COPY, the default path): segments decoded (one workgroup each) and rounds of
+     * the window scan; jump_rounds counts the rounds of the doubling path and stays 0 where no stream takes it */
+    int64_t copy_segments, copy_rounds;
 } d4g_stats;
 
 /* Select the HIP device (one process per GPU) and create the library's stream.
