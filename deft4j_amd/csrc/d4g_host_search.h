@@ -1,0 +1,450 @@
+// d4g_host_search.h — Batch, candidate search: the executors' launchers and DeflateStream.optimise's per-block part.
+#pragma once
+
+namespace d4g {
+
+// What only the level / persistent executors use (candidate keys, slot epochs, queue heads, the three memo tables): made
+// on their first use — a batch the fused executor handles alone never allocates or clears them.
+inline void Batch::ensure_legacy_tables() {
+    if (dKeys || !legacyBlocks) return;
+    Engine& E = engine();
+    const size_t nb = legacyBlocks;
+    dKeys.alloc(nb * (size_t)E.maxOps);
+    dReady.alloc_zero(nb * (size_t)slotsAlloc);
+    dHeads.alloc(16);
+    dHsMemo.alloc_zero(nb * (size_t)D4G_HSMEMO_SLOTS);
+    dPassMemo.alloc_zero((size_t)legacyPassMemoWords, 64);
+    dRcMemo.alloc_zero(nb * (size_t)D4G_RCMEMO_SLOTS);
+}
+
+// what both fused launchers hand their kernel
+inline D4FParams Batch::fused_params(int maxRounds, D4GRoundResult* results, int32_t* info) {
+    Engine& E = engine();
+    D4FParams P;
+    memset(&P, 0, sizeof(P));
+    P.ops[0] = E.progDyn.dOps; P.ops[1] = E.progFixed.dOps;
+    P.nOps[0] = (int)E.progDyn.ops.size(); P.nOps[1] = (int)E.progFixed.ops.size();
+    P.maxRounds = maxRounds;
+    P.regWords = fused_reg_words();
+    P.results = results;
+    P.roundInfo = info;
+    P.stats = fused_stats() ? E.dOpStats.get() : nullptr;
+    return P;
+}
+// one launch of state ops over these blocks, for the roofline figures
+inline void Batch::count_state_launch(const int32_t* blk, size_t n) {
+    stats.state_launches++;
+    for (size_t i = 0; i < n; i++) { stats.state_tokens_per_round += hBlocks[blk[i]].tokCount; stats.state_bytes_per_round += hBlocks[blk[i]].uLen; }
+}
+
+// One optimiseBlock call per block of `act`: the fused executor takes the blocks it can hold, the level / persistent
+// executors the rest.
+inline std::vector<D4GRoundResult> Batch::run_round(const std::vector<int>& act) {
+    if (!exec_fused()) return run_round_legacy(act);
+    std::vector<D4GRoundResult> res(act.size());
+    std::vector<int> small, big;
+    std::vector<size_t> smallPos, bigPos;
+    // Blocks of up to 16384 back-references: one workgroup each (fused).  Longer ones: when there are many of them they
+    // still fill the device one workgroup each; a few long blocks get the whole device one after the other (cluster).
+    size_t nLong = 0;
+    for (int k : act) nLong += hBlocks[k].refCount > (1LL << 14);
+    for (size_t i = 0; i < act.size(); i++) {
+        if (hBlocks[act[i]].refCount <= fused_max_refs(nLong)) { small.push_back(act[i]); smallPos.push_back(i); }
+        else { big.push_back(act[i]); bigPos.push_back(i); }
+    }
+    if (!small.empty()) {
+        std::vector<std::vector<D4GRoundResult>> ch = run_fused(small, 1);
+        for (size_t i = 0; i < small.size(); i++) res[smallPos[i]] = ch[i].at(0);
+    }
+    if (!big.empty() && cluster_enabled()) {   // long merged blocks, one launch of the whole device each
+        std::vector<int> rest;
+        std::vector<size_t> restPos;
+        for (size_t i = 0; i < big.size(); i++) {
+            const D4GBlock& d = hBlocks[big[i]];
+            D4GRoundResult r;
+            if (d.refCount > cluster_min_refs() && (d.maskBase & 15) == 0 && (d.maskWords & 15) == 0 && (d.binMask & 15) == 0 && run_cluster(big[i], &r)) res[bigPos[i]] = r;
+            else { rest.push_back(big[i]); restPos.push_back(bigPos[i]); }
+        }
+        big.swap(rest);
+        bigPos.swap(restPos);
+    }
+    if (!big.empty()) {
+        std::vector<D4GRoundResult> r = run_round_legacy(big);
+        for (size_t i = 0; i < big.size(); i++) res[bigPos[i]] = r[i];
+    } else {
+        stats.rounds++;
+    }
+    return res;
+}
+// One optimiseBlock round of one long block with every workgroup of the device (k_search_cluster).  false: the round did
+// not fit the kernel's tables — the block is untouched and the caller uses another executor.
+inline bool Batch::run_cluster(int blk, D4GRoundResult* out) {
+    Engine& E = engine();
+    rt().cur = 0;
+    if (!dClArena) dClArena.alloc(1);
+    rt_memset(dClArena, 0, 128);   // the epoch counter; every command slot is cleared by the control workgroup before use
+    int32_t one = blk;
+    rt_h2d(dActive, &one, sizeof(one));
+    RtScratch tmp;
+    D4GRoundResult* dRes = tmp.alloc<D4GRoundResult>(D4F_MAXROUNDS);
+    int32_t* dInfo = tmp.alloc<int32_t>(4);
+    D4GCtx c = make_ctx(E.progDyn, 1);
+    const D4FParams P = fused_params(1, dRes, dInfo);
+#ifdef D4G_HOSTSIM
+    const int threads = fused_block();
+#else
+    const int threads = 512;
+#endif
+    RtEvent e0, e1;
+    e0.record();
+    RT_LAUNCH(k_search_cluster, cluster_wgs(), threads, c, P, dClArena, 0);
+    e1.record();
+    stats.kernel_launches++;
+    count_state_launch(&one, 1);
+    int32_t info = 0;
+    rt_d2h(&info, dInfo, sizeof(info));
+    D4GRoundResult r;
+    rt_d2h(&r, dRes, sizeof(r));
+    const float ms = rt_elapsed_ms(e0, e1);
+    msSearch += ms;
+    stats.ms_state_kernels += ms;
+    tmp.release();
+    if (debug_rounds()) fprintf(stderr, "cluster search: block of %lld back-references, %.3f ms%s\n", (long long)hBlocks[blk].refCount, ms, (info & D4F_INFO_FALLBACK) ? " (did not fit)" : "");
+    if ((info & D4F_INFO_FALLBACK) || (info & 0xffff) < 1) return false;
+    gpuType[blk] = r.newType;
+    stats.rounds_fused += 1;
+    stats.rounds_cluster += 1;
+    *out = r;
+    return true;
+}
+// Fused executor (k_search_fused): every block of `act` runs up to maxRounds optimiseBlock rounds, while it keeps
+// improving, inside one workgroup.  Returns each block's chain of round results.  A round that does not fit the
+// kernel's tables comes back untouched and is run by the level executor; the block then goes on here.
+inline std::vector<std::vector<D4GRoundResult>> Batch::run_fused(const std::vector<int>& act, int maxRounds) {
+    Engine& E = engine();
+    std::vector<std::vector<D4GRoundResult>> chains(act.size());
+    std::vector<int> todo(act.size());
+    for (size_t i = 0; i < act.size(); i++) todo[i] = (int)i;
+    RtScratch tmp;   // (run_round_legacy below waits before it returns or throws its own errors)
+    D4GRoundResult* dRes = nullptr;
+    int32_t* dInfo = nullptr;
+    while (!todo.empty()) {
+        const int nA = (int)todo.size();
+        std::vector<int32_t> sub(nA);
+        for (int i = 0; i < nA; i++) sub[i] = act[todo[i]];
+        rt().cur = 0;
+        rt_h2d(dActive, sub.data(), sub.size() * sizeof(int32_t));
+        if (!dRes) {
+            dRes = tmp.alloc<D4GRoundResult>(act.size() * (size_t)D4F_MAXROUNDS);
+            dInfo = tmp.alloc<int32_t>(act.size(), 16);
+        }
+        D4GCtx c = make_ctx(E.progDyn, nA);
+        int cap = 0;   // most rounds any of them may still run
+        for (int i = 0; i < nA; i++) cap = std::max(cap, maxRounds - (int)chains[todo[i]].size());
+        const D4FParams P = fused_params(std::min(cap, (int)D4F_MAXROUNDS), dRes, dInfo);
+        RtEvent e0, e1;
+        e0.record();
+        RT_LAUNCH(k_search_fused, nA, fused_block(), c, P);
+        e1.record();
+        stats.kernel_launches++;
+        count_state_launch(sub.data(), sub.size());
+        std::vector<int32_t> info(nA);
+        rt_d2h(info.data(), dInfo, (size_t)nA * sizeof(int32_t));
+        std::vector<D4GRoundResult> r((size_t)nA * D4F_MAXROUNDS);
+        rt_d2h(r.data(), dRes, r.size() * sizeof(D4GRoundResult));
+        const float ms = rt_elapsed_ms(e0, e1);
+        msSearch += ms;
+        stats.ms_state_kernels += ms;
+        if (debug_rounds()) fprintf(stderr, "fused search: %d blocks, up to %d rounds, %.3f ms\n", nA, P.maxRounds, ms);
+        std::vector<int> next, fb;
+        for (int i = 0; i < nA; i++) {
+            const int n = info[i] & 0xffff;
+            std::vector<D4GRoundResult>& ch = chains[todo[i]];
+            for (int k = 0; k < n; k++) ch.push_back(r[(size_t)i * D4F_MAXROUNDS + k]);
+            if (n) gpuType[sub[i]] = ch.back().newType;
+            stats.rounds_fused += n;
+            if (info[i] & D4F_INFO_FALLBACK) fb.push_back(todo[i]);
+            else if ((info[i] & D4F_INFO_MORE) && (int)ch.size() < maxRounds) next.push_back(todo[i]);
+        }
+        if (!fb.empty()) {   // one round with the level executor, then back here if it improved
+            std::vector<int> fbAct(fb.size());
+            for (size_t i = 0; i < fb.size(); i++) fbAct[i] = act[fb[i]];
+            std::vector<D4GRoundResult> rr = run_round_legacy(fbAct);
+            stats.fused_fallbacks += (int64_t)fb.size();
+            for (size_t i = 0; i < fb.size(); i++) {
+                chains[fb[i]].push_back(rr[i]);
+                if (rr[i].improved && (int)chains[fb[i]].size() < maxRounds) next.push_back(fb[i]);
+            }
+        }
+        std::sort(next.begin(), next.end());
+        todo.swap(next);
+    }
+    tmp.release();
+    return chains;
+}
+// Persistent executor: dependency-driven work queues over the blocks of `sub` (grouped by XCD, xoff[x] = start of queue x),
+// state ops on the lane's first stream and header searches on its second, then the selection.
+inline void Batch::launch_persistent(const Program& P, const std::vector<int32_t>& sub, const int* xoff, Events& evs) {
+    const int nA = (int)sub.size();
+    D4GCtx c = make_ctx(P, nA);
+    epoch++;
+    rt_memset(dHeads, 0, 64);
+    const long long spinLimit = spin_limit();
+    D4GQueue qs = {P.dStateFlat, P.nStateFlat, dHeads, dReady, epoch, {0}, spinLimit};
+    D4GQueue qh = {P.dHdrFlat, P.nHdrFlat, dHeads + 8, dReady, epoch, {0}, spinLimit};
+    for (int x = 0; x < 9; x++) { qs.xoff[x] = xoff[x]; qh.xoff[x] = xoff[x]; }
+    RtEvent ready;
+    ready.record();
+    rt_stream2_wait(ready);
+    static const int cus = device_cus();
+    const int sPerCu = state_wgs_per_cu(), hPerCu = hs_wgs_per_cu();
+    i64 ns = (i64)P.nStateFlat * nA, nh = (i64)P.nHdrFlat * nA;
+    i64 gs = std::min<i64>(ns, (i64)cus * sPerCu), gh = std::min<i64>(nh, (i64)cus * hPerCu);
+    evs.emplace_back(new RtEvent());
+    evs.back()->record();
+    RT_LAUNCH(k_persist_state_ops, gs, state_block(), c, qs);
+    evs.emplace_back(new RtEvent());
+    evs.back()->record();
+    stats.kernel_launches++;
+    count_state_launch(sub.data(), sub.size());
+    if (gh > 0) {
+        RT_LAUNCH2(k_persist_hdr_search, gh, 64, c, qh);
+        stats.kernel_launches++;
+    }
+    RtEvent hsDone;
+    hsDone.record2();
+    rt_stream_wait(hsDone);
+    RT_LAUNCH(k_select, nA, state_block(), c, dResults);
+    stats.kernel_launches++;
+    stats.search_lanes = std::max<int64_t>(stats.search_lanes, 1);
+}
+// Level executor: one launch per program level.  The active blocks are split into groups, one stream lane each: the launch
+// tail of one group's level (a few long recode/tree ops) overlaps the other groups' levels.
+inline void Batch::launch_levels(const Program& P, const std::vector<int32_t>& sub, RtEvent& uploaded, Events& evs, Events& keep) {
+    const int nA = (int)sub.size();
+    int G = std::min(lanes(), std::max(1, nA / 16));
+    Events laneDone;
+    for (int g = 0; g < G; g++) {
+        int lo = (int)((i64)nA * g / G), hi = (int)((i64)nA * (g + 1) / G);
+        if (hi <= lo) continue;
+        rt().cur = g;
+        D4GCtx c = make_ctx(P, hi - lo);
+        c.active = dActive + lo;
+        rt_stream_wait(uploaded);
+        i64 groups = (hi - lo + 7) / 8;
+        const int tg = tile_groups();   // launch tiles (d4g_map_wg): the whole group by default
+        c.tileGroups = tg > 0 && tg < groups ? tg : (int)groups;
+        groups = (groups + c.tileGroups - 1) / c.tileGroups * c.tileGroups;
+        // Level l's header searches read bases produced at level l-1, so they run on the lane's second
+        // stream beside level l's state ops (the searches are LDS-bound at low occupancy).
+        RtEvent* lvlPrev = nullptr;
+        rt_stream2_wait(uploaded);
+        for (int l = 0; l < P.nLevels; l++) {
+            if (P.hdrOff[l].second) {
+                if (lvlPrev) rt_stream2_wait(*lvlPrev);
+                i64 grid = 8 * groups * P.hdrOff[l].second;
+                RT_LAUNCH2(k_exec_hdr_search, grid, 64, c, P.dLists + P.hdrOff[l].first, P.hdrOff[l].second);
+                stats.kernel_launches++;
+            }
+            if (P.stateOff[l].second) {
+                i64 grid = 8 * groups * P.stateOff[l].second;
+                evs.emplace_back(new RtEvent());
+                evs.back()->record();
+                RT_LAUNCH(k_exec_state_ops, grid, state_block(), c, P.dLists + P.stateOff[l].first, P.stateOff[l].second);
+                evs.emplace_back(new RtEvent());
+                evs.back()->record();
+                stats.kernel_launches++;
+                count_state_launch(sub.data() + lo, (size_t)(hi - lo));
+            }
+            if (P.wideOff[l].second) {
+                i64 grid = 8 * groups * P.wideOff[l].second;
+                RT_LAUNCH(k_exec_state_ops_wide, grid, wide_block(), c, P.dLists + P.wideOff[l].first, P.wideOff[l].second);
+                stats.kernel_launches++;
+            }
+            keep.emplace_back(new RtEvent());
+            keep.back()->record();
+            lvlPrev = keep.back().get();
+        }
+        keep.emplace_back(new RtEvent());
+        keep.back()->record2();
+        rt_stream_wait(*keep.back());
+        RT_LAUNCH(k_select, hi - lo, state_block(), c, dResults + lo);
+        stats.kernel_launches++;
+        laneDone.emplace_back(new RtEvent());
+        laneDone.back()->record();
+        stats.search_lanes = std::max<int64_t>(stats.search_lanes, G);   // most lanes any round of the batch used
+    }
+    rt().cur = 0;
+    for (auto& ev : laneDone) rt_stream_wait(*ev);
+}
+// One pass (one program) of a round over `sub`, whose results go to res[subPos[k]].  false: a wait inside the persistent
+// kernels gave up (see wg_wait_slot): nothing was selected, the blocks are untouched, the error counter is reset.
+inline bool Batch::run_legacy_pass(const Program& P, std::vector<int32_t> sub, std::vector<size_t> subPos, bool persist, int pass, std::vector<D4GRoundResult>& res) {
+    rt().cur = 0;
+    int xoff[9] = {0};
+    if (persist) {
+        // group the active blocks by (position mod 8): one task queue per XCD
+        std::vector<int32_t> g;
+        std::vector<size_t> gp;
+        for (int x = 0; x < 8; x++) {
+            xoff[x] = (int)g.size();
+            for (size_t i = x; i < sub.size(); i += 8) { g.push_back(sub[i]); gp.push_back(subPos[i]); }
+        }
+        xoff[8] = (int)g.size();
+        sub.swap(g);
+        subPos.swap(gp);
+    }
+    rt_h2d(dActive, sub.data(), sub.size() * sizeof(int32_t));
+    RtEvent e0, e1, uploaded;
+    uploaded.record();
+    Events evs, keep;
+    e0.record();
+    if (persist) launch_persistent(P, sub, xoff, evs);
+    else launch_levels(P, sub, uploaded, evs, keep);
+    e1.record();
+    std::vector<D4GRoundResult> r(sub.size());
+    rt_d2h(r.data(), dResults, sub.size() * sizeof(D4GRoundResult));
+    const float roundMs = rt_elapsed_ms(e0, e1);
+    msSearch += roundMs;
+    if (persist && !r.empty() && r[0].improved < 0) {
+        int32_t zero[2] = {0, 0};
+        rt_h2d(errors() + 1, zero, 4);
+        rt_sync();
+        stats.persist_fallbacks++;
+        return false;
+    }
+    if (debug_rounds())
+        fprintf(stderr, "search round %lld (%s program, %s): %d active blocks, %.3f ms\n", (long long)stats.rounds, pass == 0 ? "dynamic" : "fixed",
+                persist ? "persistent" : "levels", (int)sub.size(), roundMs);
+    for (size_t k = 0; k + 1 < evs.size(); k += 2) stats.ms_state_kernels += rt_elapsed_ms(*evs[k], *evs[k + 1]);
+    for (size_t k = 0; k < sub.size(); k++) {
+        res[subPos[k]] = r[k];
+        gpuType[sub[k]] = r[k].newType;
+    }
+    return true;
+}
+// One optimiseBlock call on every block of `act` with the level / persistent executors: the dynamic program over the
+// blocks that are dynamic now, then the fixed one over the fixed ones.
+inline std::vector<D4GRoundResult> Batch::run_round_legacy(const std::vector<int>& act) {
+    Engine& E = engine();
+    ensure_legacy_tables();
+    std::vector<D4GRoundResult> res(act.size());
+    for (int pass = 0; pass < 2; pass++) {
+        const Program& P = pass == 0 ? E.progDyn : E.progFixed;
+        const int wantType = pass == 0 ? D4G_DYNAMIC : D4G_FIXED;
+        std::vector<int32_t> sub;
+        std::vector<size_t> subPos;
+        for (size_t i = 0; i < act.size(); i++)
+            if (gpuType[act[i]] == wantType) { sub.push_back(act[i]); subPos.push_back(i); }
+        if (sub.empty()) continue;
+        // the same pass again with the level executor, which has no cross-kernel waits, when the persistent one gave up
+        if (exec_persistent((int)sub.size()) == 0 || !run_legacy_pass(P, sub, subPos, true, pass, res)) run_legacy_pass(P, sub, subPos, false, pass, res);
+    }
+    stats.rounds++;
+    return res;
+}
+
+// Winner of optimiseBlock given the device result and the stream position (stored candidate
+// = DeflateStream.java:376-383, ranked right after op 0 "optimised").  Returns true when the
+// stored candidate wins.
+inline bool Batch::stored_wins(const D4GRoundResult& r, i64 uLen, i64 pos, i64* storedSize) {
+    if (uLen > 65535) return false;
+    i64 c = pos % 8;
+    c = c == 0 ? 0 : 8 - c;
+    i64 ss = (uLen + 4) * 8 + c;
+    *storedSize = ss;
+    if (ss < r.bestSize) return true;
+    if (ss == r.bestSize && r.improved && r.bestSeq > 0) return true;
+    return false;
+}
+
+// ---- DeflateStream.optimise, per-block part — DeflateStream.java:496-566 ----
+inline void Batch::phase1() {
+    // blocks the reference's loop reaches: it stops right after removing the first empty block
+    std::vector<int> act;
+    std::vector<std::pair<int, int>> owner;  // (stream, block index in stream)
+    for (size_t si = 0; si < streams.size(); si++) {
+        HStream& s = streams[si];
+        if (s.status != 0) continue;
+        for (size_t k = 0; k < s.blocks.size(); k++) {
+            HBlock& b = s.blocks[k];
+            bool sole = (k == 0 && s.blocks.size() == 1);
+            if (b.uLen == 0 && !sole) break;
+            if (b.type != D4G_STORED) { act.push_back(b.gpu); owner.push_back({(int)si, (int)k}); }
+        }
+    }
+    if (exec_fused()) {   // all rounds of a block inside one workgroup; blocks the fused executor does not take follow below
+        std::vector<int> fa, rest;
+        std::vector<std::pair<int, int>> fo, ro;
+        size_t nLong = 0;
+        for (int k : act) nLong += hBlocks[k].refCount > (1LL << 14);
+        for (size_t i = 0; i < act.size(); i++) {
+            if (hBlocks[act[i]].refCount <= fused_max_refs(nLong)) { fa.push_back(act[i]); fo.push_back(owner[i]); }
+            else { rest.push_back(act[i]); ro.push_back(owner[i]); }
+        }
+        if (!fa.empty()) {
+            std::vector<std::vector<D4GRoundResult>> ch = run_fused(fa, 1 << 20);
+            for (size_t i = 0; i < fa.size(); i++) streams[fo[i].first].blocks[fo[i].second].chain = ch[i];
+            stats.rounds++;
+        }
+        act.swap(rest);
+        owner.swap(ro);
+    }
+    // fixpoint rounds: every block follows its own chain of strictly improving Huffman states
+    while (!act.empty()) {
+        std::vector<D4GRoundResult> res = run_round_legacy(act);
+        std::vector<int> nact;
+        std::vector<std::pair<int, int>> nowner;
+        for (size_t i = 0; i < act.size(); i++) {
+            HBlock& b = streams[owner[i].first].blocks[owner[i].second];
+            b.chain.push_back(res[i]);
+            if (res[i].improved) { nact.push_back(act[i]); nowner.push_back(owner[i]); }
+        }
+        act.swap(nact);
+        owner.swap(nowner);
+    }
+    check_device_errors();
+    // sequential resolution with the stream bit position (pos drift included)
+    for (HStream& s : streams) {
+        if (s.status != 0) continue;
+        i64 pos = 0, saved = 0;
+        bool first = true;
+        size_t idx = 0;
+        while (idx < s.blocks.size()) {
+            bool finishPass = true;
+            HBlock& b = s.blocks[idx];
+            bool hasNext = idx + 1 < s.blocks.size();
+            if (b.uLen > 0 || (first && !hasNext)) {
+                pos += 3;
+                if (b.type != D4G_STORED) {
+                    size_t step = 0;
+                    // chain index = number of improvements already applied to this block
+                    while (step < b.chain.size() && b.chain[step].curSize != b.size) step++;
+                    if (step >= b.chain.size()) throw std::runtime_error("phase1: chain lookup failed");
+                    const D4GRoundResult& r = b.chain[step];
+                    i64 ss = 0;
+                    if (stored_wins(r, b.uLen, pos, &ss)) {
+                        i64 cs = b.size - ss;
+                        if (cs > 0) { saved += cs; b.type = D4G_STORED; finishPass = false; }
+                    } else if (r.improved) {
+                        saved += b.size - r.bestSize;
+                        b.size = r.bestSize;
+                        finishPass = false;
+                    }
+                }
+                pos += b.size_at(pos);
+            } else {
+                saved += b.size_at(pos + 3) + 3;
+                s.blocks.erase(s.blocks.begin() + idx);
+                break;
+            }
+            if (finishPass) { idx++; first = false; }
+        }
+        s.saved = saved;
+        // final Huffman type per block comes from the last round that ran on it
+        for (HBlock& b : s.blocks)
+            if (b.type != D4G_STORED) b.type = gpuType[b.gpu];
+    }
+}
+
+}  // namespace d4g

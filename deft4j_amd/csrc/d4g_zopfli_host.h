@@ -63,7 +63,7 @@ struct ZfFront {
         }
         dIn = own.upload(hIn);
         pool.cap = (uint32_t)std::min<i64>(total / 2 + (1 << 16), 0x7fff0000LL);
-        if (const char* pw = getenv("D4G_ZF_POOL_WORDS")) pool.cap = (uint32_t)std::max(64, atoi(pw));   // tests: start small, exercise the growth
+        if (const int pw = zf_pool_words()) pool.cap = (uint32_t)pw;   // tests: start small, exercise the growth
         pool.words = poolWords.alloc(pool.cap);
         pool.used = own.alloc_zero<uint32_t>(4);
         pool.error = (int32_t*)(pool.used + 1);
@@ -73,8 +73,7 @@ struct ZfFront {
             RT_LAUNCH(k_zf_keys_b, kj.size(), 256, dIn, dK);
         }
         // the shared table: chains enumerated from sorted buckets (D4G_ZF_TABLE=scan: the window-scan kernel the tails use)
-        const char* tb = getenv("D4G_ZF_TABLE");   // (read per call: the tests switch it inside one process)
-        const bool scanTable = tb && !strcmp(tb, "scan");
+        const bool scanTable = zf_table_scan();   // (read per call: the tests switch it inside one process)
         std::vector<ZfMatchJob> mj;
         if (scanTable) {
             for (size_t i = 0; i < n; i++)
@@ -344,7 +343,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
             }
             for (size_t q = 0; q < blocks.size(); q++)
                 if (rep[q] != q) { blocks[q].out = blocks[rep[q]].out; blocks[q].buf[0] = blocks[rep[q]].buf[0]; blocks[q].buf[1] = blocks[rep[q]].buf[1]; }
-            if (env_int("D4G_DEBUG_ZOPFLI", 0) > 1)
+            if (debug_zopfli() > 1)
                 for (size_t q = 0; q < jobs.size() && q < 8; q++)
                     fprintf(stderr, "[zopfli] squeeze job %zu (%lld bytes): ticks greedy %lld, DP %lld, trace+follow %lld, cost %lld, statistics %lld\n", q,
                             (long long)(jobs[q].v.end - jobs[q].v.start), outs[q].cyc[0], outs[q].cyc[1], outs[q].cyc[2], outs[q].cyc[3], outs[q].cyc[4]);

@@ -191,10 +191,6 @@ int32_t stream_status(const d4g_batch& b, size_t i) {
     return s.status != 0 ? D4G_STREAM_PARSE_ERROR : ((s.saved > 0 || grafted) ? D4G_STREAM_CHANGED : D4G_STREAM_UNCHANGED);
 }
 // ---- round-trip verification (verify_items, d4g_host.h) ----
-bool verify_switch() {   // D4G_VERIFY=1: every call that returns rewritten bytes verifies them first
-    const char* v = getenv("D4G_VERIFY");
-    return v && v[0] && !(v[0] == '0' && !v[1]);
-}
 const char* verdict_name(int v) {
     switch (v) {
         case VERIFY_OK: return "OK";
@@ -334,7 +330,7 @@ static int init_ctx(int ctx, int device_index) {
         return fail(D4G_ERR_ARG, "already initialised on device " + std::to_string(rt().device) + ": call d4g_shutdown() before selecting another device");
     RT_CHECK(hipSetDevice(device_index));
     rt().device = device_index;
-    if (const char* mb = getenv("D4G_POOL_MAX_MB")) rt_pool().maxHeldBytes = (size_t)atoll(mb) << 20;
+    pool_max_bytes(&rt_pool().maxHeldBytes);
 #endif
     rt().ready = true;
     (void)rt();           // this thread's streams
@@ -676,7 +672,7 @@ int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_le
             specs.push_back({(int32_t)i, iterations, splitting, max_blocks, (long long)master_block});
         }
         zf.encode(specs);
-        if (env_int("D4G_DEBUG_ZOPFLI", 0))
+        if (debug_zopfli())
             fprintf(stderr, "[zopfli] inputs %zu: table %.1f ms, split %.1f ms, squeeze %.1f ms (%lld blocks, %lld position-iterations), final+emit %.1f ms\n", n,
                     zf.msTable, zf.msSplit, zf.msSqueeze, (long long)zf.squeezeBlocks, (long long)zf.squeezePositions, zf.msEmit);
         if (verify_switch())
@@ -917,7 +913,7 @@ void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* 
 #ifndef D4G_HOSTSIM
     if (!zIdx.empty()) zthread.threads.emplace_back(zopfli_stage);
 #endif
-    const bool dbg = env_int("D4G_DEBUG_ZOPFLI", 0) > 0;
+    const bool dbg = debug_zopfli() > 0;
     const double tg0 = now_ms();
     if (afterStart) afterStart();      // the caller's own work that only had to wait for the Zopfli stage to be under way
     if (dbg) fprintf(stderr, "[group] +%.1f s: caller's work done\n", (now_ms() - tg0) / 1000);
@@ -1031,7 +1027,7 @@ void compress_run(CompressRun& R, size_t n, const uint8_t* const* raw, const siz
     R.dWin.alloc(cap);
     // group size: the candidate search keeps ~1.6 MB of states per block; estimate >= 3 bytes per symbol and let an
     // out-of-memory failure halve the group
-    const long long budget = env_int("D4G_GROUP_BLOCKS", 12000);
+    const long long budget = group_blocks();
     size_t i0 = 0;
     long long shrink = 1;
     while (i0 < n) {
