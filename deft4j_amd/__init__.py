@@ -55,6 +55,25 @@ class d4g_block_info(ctypes.Structure):
                [(n, ctypes.c_int64) for n in ("bit_pos", "size_bits", "header_bits", "tokens", "decoded_len")]
 
 
+class d4g_found_stream(ctypes.Structure):
+    _fields_ = [("file", ctypes.c_int32), ("kind", ctypes.c_int32)] + \
+               [(n, ctypes.c_int64) for n in ("offset", "payload_offset", "payload_len", "total_len", "decoded_len", "size_bits")] + \
+               [("crc32", ctypes.c_uint32), ("adler32", ctypes.c_uint32), ("n_blocks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class d4g_find_options(ctypes.Structure):
+    _fields_ = [("kinds", ctypes.c_int32), ("reserved", ctypes.c_int32), ("min_decoded", ctypes.c_int64)]
+
+
+class d4g_find_stats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("bytes_scanned", "header_candidates", "first_block_ok", "parsed", "confirmed", "reported",
+                                              "kernel_launches")] + [("ms_total", ctypes.c_double), ("ms_kernels", ctypes.c_double)]
+
+
+FOUND_ZLIB, FOUND_GZIP = 1, 2                               # D4G_FOUND_*
+FOUND_KIND_NAMES = {1: "zlib", 2: "gzip"}
+
+
 class d4g_parse_error(ctypes.Structure):
     _fields_ = [("reason", ctypes.c_int32), ("block", ctypes.c_int32)] + \
                [(n, ctypes.c_int64) for n in ("block_bit_pos", "bit_pos", "decoded_offset", "value")]
@@ -81,7 +100,8 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
            "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
            "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
-           "d4g_debug_device_blocks", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name"]
+           "d4g_debug_device_blocks", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name",
+           "d4g_find_streams"]
 
 
 def load_library(path=None):
@@ -197,6 +217,9 @@ def load_library(path=None):
     L.d4g_diagnose_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_parse_error)]
     L.d4g_parse_reason_name.restype = ctypes.c_char_p
     L.d4g_parse_reason_name.argtypes = [ctypes.c_int]
+    L.d4g_find_streams.restype = ctypes.c_int
+    L.d4g_find_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_find_options),
+                                   ctypes.POINTER(ctypes.POINTER(d4g_found_stream)), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_find_stats)]
     if path is None:
         _lib = L
     return L
@@ -510,6 +533,35 @@ def diagnose_streams(streams, lib=None):
     if rc != 0:
         raise RuntimeError("d4g_diagnose_streams: " + L.d4g_last_error().decode())
     return [_parse_error_dict(out[i]) for i in range(n)]
+
+
+def find_streams(files, kinds=0, min_decoded=0, lib=None, stats=False):
+    """d4g_find_streams: the zlib and gzip streams embedded in files whose layout is not known (include/deft4g.h states what
+    counts as one).  kinds: OR of 1 << FOUND_ZLIB / 1 << FOUND_GZIP, 0 = both.  -> one list per file, in offset order, of
+    dict(file, kind, kind_name, offset, payload_offset, payload_len, total_len, decoded_len, size_bits, crc32, adler32,
+    n_blocks); with stats=True also the dict of d4g_find_stats."""
+    L = lib or _need()
+    n = len(files)
+    keep = [bytes(f) for f in files]
+    arr = (ctypes.c_char_p * max(1, n))(*keep)
+    lens = (ctypes.c_size_t * max(1, n))(*[len(f) for f in keep])
+    opt = d4g_find_options(kinds, 0, min_decoded)
+    found = ctypes.POINTER(d4g_found_stream)()
+    nf = ctypes.c_size_t()
+    st = d4g_find_stats()
+    rc = L.d4g_find_streams(n, arr, lens, ctypes.byref(opt), ctypes.byref(found), ctypes.byref(nf), ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError("d4g_find_streams: " + L.d4g_last_error().decode())
+    res = [[] for _ in range(n)]
+    for k in range(nf.value):
+        d = {name: getattr(found[k], name) for name, _ in d4g_found_stream._fields_ if name != "reserved"}
+        d["kind_name"] = FOUND_KIND_NAMES.get(d["kind"], "unknown")
+        res[d["file"]].append(d)
+    if nf.value:
+        L.d4g_free(found)
+    if stats:
+        return res, {name: getattr(st, name) for name, _ in d4g_find_stats._fields_}
+    return res
 
 
 ZOPFLI_SPLIT_FIRST, ZOPFLI_SPLIT_LAST, ZOPFLI_SPLIT_NONE = 0, 1, 2     # Options.BlockSplitting (CafeUndZopfli) / blocksplitting[last] (jzopfli)

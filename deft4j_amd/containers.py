@@ -1,4 +1,5 @@
-"""Container wrappers around the device hot path: raw deflate, gzip, zlib, PNG, zip.
+"""Container wrappers around the device hot path: raw deflate, gzip, zlib, PNG, zip, and
+EmbeddedFile for zlib / gzip streams at unknown offsets of any other file.
 
 Host-side mirrors of K/RawDeflateFile.java, K/GZFile.java and K/ZLibFile.java (K/ = deft4j-container/
 src/main/java/com/github/NeRdTheNed/deft4j/container/): same fields, same read/write order, same quirks
@@ -351,6 +352,53 @@ class ZipFile:
         return bytes(out)
 
 
+class EmbeddedFile:
+    """Any file that carries zlib or gzip streams at offsets nobody told us (the reference's wish list, M/CMDUtil.java:120-125:
+    "General support for optimising embedded GZip / ZLib / deflate streams in other files").  The streams are found on the
+    device (deft4j_amd.find_streams; include/deft4g.h states what counts as one), those that decode to fewer than
+    `min_decoded` bytes are left alone.  Never chosen by `detect`: ask for it with formats=[EmbeddedFile()] or "embedded".
+
+    write() replaces each payload, keeps every header and trailer as it is (the decoded bytes, and so the checksums, do
+    not change) and shifts what follows.  The library does not pretend to fix a container it does not know: lengths,
+    offsets or checksums the outer format keeps about these streams are NOT updated.  `relocations` — one
+    (old_offset, old_total_len, new_offset, new_total_len) per stream, in offset order — is what a caller who knows the
+    outer format needs to fix them."""
+    file_type = "Embedded streams"
+    multi = True
+
+    def __init__(self, min_decoded=64):
+        self.min_decoded = min_decoded
+        self.relocations = []
+
+    def read(self, data, lib=None):
+        from . import find_streams
+        self.data = bytes(data)
+        self.found = find_streams([self.data], min_decoded=self.min_decoded, lib=lib)[0]
+        return bool(self.found)
+
+    def stream_payloads(self):
+        return [("%s stream at %d" % (f["kind_name"], f["offset"]), self.data[f["payload_offset"]:f["payload_offset"] + f["payload_len"]])
+                for f in self.found]
+
+    def write(self, deflate_outputs):
+        out = bytearray()
+        pos = 0
+        self.relocations = []
+        for f, new in zip(self.found, deflate_outputs):
+            end = f["offset"] + f["total_len"]
+            out += self.data[pos:f["payload_offset"]]
+            new_off = len(out) - (f["payload_offset"] - f["offset"])
+            out += new
+            out += self.data[f["payload_offset"] + f["payload_len"]:end]      # the trailer, as it is
+            self.relocations.append((f["offset"], f["total_len"], new_off, len(out) - new_off))
+            pos = end
+        out += self.data[pos:]
+        return bytes(out)
+
+
+_MULTI = (PNGFile, ZipFile, EmbeddedFile)     # containers with a list of streams (stream_payloads)
+
+
 def detect(data):
     """K/ContainerUtil.java:64-86 by magic bytes (PNG, zip, gzip, zlib); anything else must be given explicitly."""
     if bytes(data[:8]) == PNGFile.SIG:
@@ -365,7 +413,7 @@ def detect(data):
     return None
 
 
-def _read_files(files, formats):
+def _read_files(files, formats, lib=None):
     """-> (container per file or None when unreadable, the deflate payloads of all files in order, (file index, stream
     name) per payload)"""
     conts = []
@@ -373,15 +421,17 @@ def _read_files(files, formats):
         c = formats[i] if formats and formats[i] is not None else None
         if c == "raw":
             c = RawDeflateFile()
+        if c == "embedded":
+            c = EmbeddedFile()
         if c is None:
             c = detect(f)
-        ok = c is not None and c.read(f)
+        ok = c is not None and (c.read(f, lib=lib) if isinstance(c, EmbeddedFile) else c.read(f))
         conts.append(c if ok else None)
     payloads, owner = [], []
     for i, c in enumerate(conts):
         if c is None:
             continue
-        sp = c.stream_payloads() if isinstance(c, (PNGFile, ZipFile)) else [(c.name, c.payload)]
+        sp = c.stream_payloads() if isinstance(c, _MULTI) else [(c.name, c.payload)]
         for name, pl in sp:
             payloads.append(pl)
             owner.append((i, name))
@@ -394,7 +444,7 @@ def explain_failures(files, formats=None, lib=None):
     dict(file, stream, name, error) — file index, stream index within the file, stream name, and the dict of
     Batch.parse_error (reason, reason_name, block, block_bit_pos, bit_pos, decoded_offset, value).  Files that cannot be
     read as a container have no streams and are not listed."""
-    _, payloads, owner = _read_files(files, formats)
+    _, payloads, owner = _read_files(files, formats, lib)
     out = []
     if not payloads:
         return out
@@ -411,14 +461,15 @@ def explain_failures(files, formats=None, lib=None):
 
 
 def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, verify=False):
-    """files: list of bytes.  formats: optional list of container instances / None (auto-detect) / "raw".
+    """files: list of bytes.  formats: optional list of container instances / None (auto-detect) / "raw" /
+    "embedded" (EmbeddedFile: zlib and gzip streams wherever they lie in the file).
     mode: RecompressMode ordinal of `deft4j optimise --mode` (0 NONE, 1 CHEAP, 2 ZOPFLI, 3 ZOPFLI_EXTENSIVE, 4 ZOPFLI_VERY_EXTENSIVE; M/CMDUtil.java:44-50,76-105): above NONE every
     stream is also recompressed and the recompression grafted in where it is smaller.
     Returns [(output bytes or None when unreadable, transcript lines)] — the lines M/CMDUtil.java:64-74 and
     K/DeflateFilesContainer.java:31-40 print.  Every deflate stream of every file goes to the GPU in one batch.
     verify: before any file is assembled, every rewritten stream is parsed again on the device and its decoded bytes compared
     with the original's (Batch.verify); a stream that fails raises RuntimeError naming file, stream, block and offset."""
-    conts, payloads, owner = _read_files(files, formats)
+    conts, payloads, owner = _read_files(files, formats, lib)
     batch = None
     if payloads:
         batch = Batch(payloads, lib=lib)
@@ -439,7 +490,7 @@ def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, ver
     for i, c in enumerate(conts):
         if c is None:
             continue
-        n = len(c.stream_payloads()) if isinstance(c, (PNGFile, ZipFile)) else 1
+        n = len(c.stream_payloads()) if isinstance(c, _MULTI) else 1
         lines = ["File type recognised as " + c.file_type]
         total = 0
         ok = True
@@ -460,7 +511,7 @@ def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, ver
                     orig = r["size_bits_in"] - saved
                     rlines.append("Recompressed stream %d (%s) from %d bits to %d bits, saved %d bits" % (j, owner[k + j][1], orig, orig - rs, rs))
                     rtotal += rs
-            pieces.append((batch.output(k + j), None if isinstance(c, ZipFile) else batch.checksums(k + j)))
+            pieces.append((batch.output(k + j), None if isinstance(c, (ZipFile, EmbeddedFile)) else batch.checksums(k + j)))
         if ok:
             if total > 0:
                 lines.append("Total bits saved %d" % total)
@@ -468,7 +519,7 @@ def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, ver
             lines += rlines
             if rtotal > 0:
                 lines.append("Saved %d bits with recompression" % rtotal)
-            if isinstance(c, ZipFile):   # members keep their CRC-32 (the decoded bytes do not change)
+            if isinstance(c, (ZipFile, EmbeddedFile)):   # members keep their checksums (the decoded bytes do not change)
                 results[i] = (c.write([pc[0] for pc in pieces]), lines)
             elif isinstance(c, PNGFile):
                 zl = [c.streams[j][2].write(pieces[j][0], *pieces[j][1]) for j in range(n)]

@@ -97,6 +97,11 @@ struct Batch {
         i64 maxSlots = 0;
     };
     struct MergeReq { int stream; int arena; };
+    struct ChainStart { int32_t stream; i64 bit; };   // walk_chains: a block chain begins at this bit of this stream
+    struct BlockMap {   // scan_inputs: the dynamic headers the scan found and the probe confirmed
+        std::vector<std::vector<std::pair<i64, int>>> byStream;   // per stream, sorted: bit position -> index in pout
+        std::vector<D4GProbeOut> pout;
+    };
 
     // ---- whole batch: lives until the batch is closed ----
     std::vector<std::vector<uint8_t>> inputs;
@@ -157,6 +162,8 @@ struct Batch {
     // d4g_host_parse.h
     void create(size_t n, const uint8_t* const* in, const size_t* len, bool fromDevice = false);
     void parse_probe();
+    void scan_inputs(BlockMap& M);
+    void walk_chains(const std::vector<ChainStart>& starts, const BlockMap& M, std::vector<PStream>& out, int maxBlocks);
     void scan_candidates(const std::vector<D4GScanTile>& tiles, i64 totalBytes, std::vector<D4GProbeIn>& cands, std::vector<D4GProbeOut>& pout);
     void diagnose();
     void layout_blocks(bool merge, bool needSlots, Layout& LY);
@@ -194,6 +201,7 @@ struct Batch {
     // d4g_host_write.h
     void phase_write();
     void checksums();
+    D4GCsumOut* launch_checksums(RtScratch& tmp);
     void run(bool merge);
     void run_parse(bool merge);
     void run_rest(bool merge);

@@ -81,11 +81,10 @@ inline void Batch::scan_candidates(const std::vector<D4GScanTile>& tiles, i64 to
     }
 }
 
-// Steps 1-2 + host chain walk: fills `ps` (block list per stream, exact token/byte counts).
-inline void Batch::parse_probe() {
+// Steps 1-2 for the batch's inputs: stream table, header scan, and the map of the dynamic headers the probe confirmed
+// (per stream: bit position -> probe result), which every chain that crosses the stream shares.
+inline void Batch::scan_inputs(BlockMap& M) {
     size_t n = streams.size();
-    ps.assign(n, PStream());
-    diagnosed = false; parseErrors.clear();   // (answers of an earlier parse go with it)
     std::vector<D4GStreamDesc> sd(n);
     std::vector<D4GScanTile> tiles;
     i64 totalBytes = 0;
@@ -99,25 +98,32 @@ inline void Batch::parse_probe() {
     }
     dStreams.alloc(n);
     rt_h2d(dStreams, sd.data(), n * sizeof(D4GStreamDesc));
-    RtEvent e0, e1;
-    e0.record();
     std::vector<D4GProbeIn> cands;
-    std::vector<D4GProbeOut> pout;
-    if (!tiles.empty()) scan_candidates(tiles, totalBytes, cands, pout);
+    if (!tiles.empty()) scan_candidates(tiles, totalBytes, cands, M.pout);
     // candidate maps: bit position -> probe result
-    std::vector<std::vector<std::pair<i64, int>>> byStream(n);
+    M.byStream.assign(n, {});
     for (size_t k = 0; k < cands.size(); k++)
-        if (pout[k].status == 0) { byStream[cands[k].stream].push_back({cands[k].bitPos, (int)k}); stats.scan_confirmed++; }
-    for (auto& v : byStream) std::sort(v.begin(), v.end());
-    // chain walk; positions the scan cannot see (fixed / stored / unusual dynamic blocks) are probed exactly
-    std::vector<i64> cur(n, 0), upos(n, 0), spos(n, 0);
+        if (M.pout[k].status == 0) { M.byStream[cands[k].stream].push_back({cands[k].bitPos, (int)k}); stats.scan_confirmed++; }
+    for (auto& v : M.byStream) std::sort(v.begin(), v.end());
+}
+
+// Host chain walk over chain starts: chain k begins at bit starts[k].bit of stream starts[k].stream and fills out[k] (block
+// list, exact token / byte counts; decoded positions and size bits count from the chain's start).  Confirmed headers come
+// from the stream's shared map; positions the scan cannot see (fixed / stored / unusual dynamic blocks) are probed
+// exactly, the live chains of all streams in one launch per step.  maxBlocks > 0 stops every chain after that many blocks
+// (status 0: no block failed so far).
+inline void Batch::walk_chains(const std::vector<ChainStart>& starts, const BlockMap& M, std::vector<PStream>& out, int maxBlocks) {
+    const size_t n = starts.size();
+    out.assign(n, PStream());
+    std::vector<i64> cur(n), upos(n, 0), spos(n, 0);
+    for (size_t i = 0; i < n; i++) cur[i] = starts[i].bit;
     std::vector<char> done(n, 0);
     RtBuf<D4GProbeIn> dEx;
     RtBuf<D4GProbeOut> dExOut;
     dEx.alloc(n, 16);
     dExOut.alloc(n, 16);
     auto accept = [&](size_t i, i64 bitPos, const D4GProbeOut& o, bool fromScan) {
-        PStream& P = ps[i];
+        PStream& P = out[i];
         if (o.status != 0 || o.needHist > upos[i]) {
             P.status = -1; done[i] = 1;
             P.failBlock = (i64)P.blocks.size(); P.failBit = bitPos; P.failU = upos[i];
@@ -140,16 +146,17 @@ inline void Batch::parse_probe() {
             P.status = -1; done[i] = 1;
             P.failBlock = (i64)P.blocks.size(); P.failBit = o.endBit; P.failU = upos[i];
         }
+        else if (maxBlocks > 0 && (int)P.blocks.size() >= maxBlocks) done[i] = 1;
     };
     while (true) {
         std::vector<D4GProbeIn> ex;
         std::vector<size_t> exStream;
         for (size_t i = 0; i < n; i++) {
             while (!done[i]) {
-                auto& v = byStream[i];
+                auto& v = M.byStream[starts[i].stream];
                 auto it = std::lower_bound(v.begin(), v.end(), std::make_pair(cur[i], -1));
-                if (it != v.end() && it->first == cur[i]) accept(i, cur[i], pout[it->second], true);
-                else { ex.push_back({(int32_t)i, 0, cur[i]}); exStream.push_back(i); break; }
+                if (it != v.end() && it->first == cur[i]) accept(i, cur[i], M.pout[it->second], true);
+                else { ex.push_back({starts[i].stream, 0, cur[i]}); exStream.push_back(i); break; }
             }
         }
         if (ex.empty()) break;
@@ -163,13 +170,27 @@ inline void Batch::parse_probe() {
         for (size_t k = 0; k < ex.size(); k++) accept(exStream[k], ex[k].bitPos, eo[k], false);
     }
     dEx.reset(); dExOut.reset();
+    for (size_t i = 0; i < n; i++) {
+        out[i].nU = upos[i];
+        out[i].sizeBits = spos[i];
+        if (out[i].status != 0) { out[i].blocks.clear(); out[i].nTok = 0; out[i].nU = 0; }
+    }
+}
+
+// Steps 1-2 + host chain walk: fills `ps` (block list per stream, exact token/byte counts) — one chain per stream, from
+// its first bit.
+inline void Batch::parse_probe() {
+    size_t n = streams.size();
+    diagnosed = false; parseErrors.clear();   // (answers of an earlier parse go with it)
+    RtEvent e0, e1;
+    e0.record();
+    BlockMap M;
+    scan_inputs(M);
+    std::vector<ChainStart> starts(n);
+    for (size_t i = 0; i < n; i++) starts[i] = {(int32_t)i, 0};
+    walk_chains(starts, M, ps, 0);
     e1.record();
     msParseKernels += rt_elapsed_ms(e0, e1);
-    for (size_t i = 0; i < n; i++) {
-        ps[i].nU = upos[i];
-        ps[i].sizeBits = spos[i];
-        if (ps[i].status != 0) { ps[i].blocks.clear(); ps[i].nTok = 0; ps[i].nU = 0; }
-    }
 }
 
 // ---- why a stream did not parse (d4g_batch_parse_error) ----

@@ -53,27 +53,32 @@ inline void Batch::phase_write() {
 inline void Batch::checksums() {
     if (!csums.empty() || streams.empty()) return;
     if (!dU) throw std::runtime_error("checksums: the batch has not been parsed");
+    RtScratch tmp;
+    RtEvent e0, e1;
+    e0.record();
+    D4GCsumOut* dOutC = launch_checksums(tmp);
+    e1.record();
+    csums.resize(streams.size());
+    rt_d2h(csums.data(), dOutC, streams.size() * sizeof(D4GCsumOut));
+    stats.ms_checksum_kernels = rt_elapsed_ms(e0, e1);
+    tmp.release();
+}
+// the two checksum kernels, queued: one record per stream in device memory (`tmp` owns it)
+inline D4GCsumOut* Batch::launch_checksums(RtScratch& tmp) {
     size_t n = streams.size();
     std::vector<long long> base(n + 1, 0);
     for (size_t i = 0; i < n; i++) base[i + 1] = base[i] + (streams[i].status == 0 ? (streams[i].nU + D4G_CSUM_TILE - 1) / D4G_CSUM_TILE : 0);
     long long nTiles = base[n];
-    RtScratch tmp;
     long long* dBase = tmp.upload(base);
     D4GCsumRec* dCh = tmp.alloc<D4GCsumRec>((size_t)nTiles, 16);
     D4GCsumOut* dOutC = tmp.alloc<D4GCsumOut>(n);
-    RtEvent e0, e1;
-    e0.record();
     if (nTiles) {
         RT_LAUNCH(k_csum_tiles, nTiles, 256, dStreams, dBase, (int)n, dU, engine().dCrcTab, dCh);
         stats.kernel_launches++;
     }
     RT_LAUNCH(k_csum_combine, n, 256, dStreams, dBase, dCh, engine().dCrcTab + 1024, dOutC);
     stats.kernel_launches++;
-    e1.record();
-    csums.resize(n);
-    rt_d2h(csums.data(), dOutC, n * sizeof(D4GCsumOut));
-    stats.ms_checksum_kernels = rt_elapsed_ms(e0, e1);
-    tmp.release();
+    return dOutC;
 }
 
 inline void Batch::run(bool merge) {

@@ -7,6 +7,7 @@
 #include "d4g_host.h"
 #include "d4g_lz77_host.h"
 #include "d4g_zopfli_host.h"
+#include "d4g_host_find.h"
 
 using namespace d4g;
 
@@ -637,6 +638,33 @@ int d4g_inflate(const uint8_t* in, size_t len, uint8_t** out, size_t* out_len, s
         }
         return D4G_OK;
     }));
+}
+
+static_assert(D4G_FOUND_KIND_ZLIB == D4G_FOUND_ZLIB && D4G_FOUND_KIND_GZIP == D4G_FOUND_GZIP, "kind values");
+int d4g_find_streams(size_t n, const uint8_t* const* file, const size_t* file_len, const d4g_find_options* opt, d4g_found_stream** found,
+                     size_t* n_found, d4g_find_stats* stats) {
+    if (!found || !n_found || (n && (!file || !file_len))) return fail(D4G_ERR_ARG, "null argument");
+    const int known = (1 << D4G_FOUND_ZLIB) | (1 << D4G_FOUND_GZIP);
+    if (opt && ((opt->kinds & ~known) || opt->min_decoded < 0)) return fail(D4G_ERR_ARG, "bad find options");
+    if (n >= ((size_t)1 << 31)) return fail(D4G_ERR_ARG, "too many files");
+    for (size_t i = 0; i < n; i++) {
+        if (file_len[i] && !file[i]) return fail(D4G_ERR_ARG, "null argument");
+        if (file_len[i] >= ((size_t)1 << 31)) return fail(D4G_ERR_ARG, "a file of 2 GiB or more");
+    }
+    return api(nullptr, [&] {
+        FindRun R;
+        R.run(n, file, file_len, opt ? opt->kinds : 0, opt ? opt->min_decoded : 0);
+        d4g_found_stream* out = nullptr;
+        if (!R.found.empty()) {
+            out = (d4g_found_stream*)malloc(R.found.size() * sizeof(d4g_found_stream));
+            if (!out) throw std::bad_alloc();
+            memcpy(out, R.found.data(), R.found.size() * sizeof(d4g_found_stream));
+        }
+        *found = out;
+        *n_found = R.found.size();
+        if (stats) *stats = R.st;
+        return D4G_OK;
+    });
 }
 
 // ---- Zopfli encoder ----

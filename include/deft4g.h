@@ -297,6 +297,50 @@ int d4g_batch_parse_error(d4g_batch* b, size_t i, d4g_parse_error* out);  /* aft
 int d4g_diagnose_streams(size_t n, const uint8_t* const* in, const size_t* in_len, d4g_parse_error* out);
 const char* d4g_parse_reason_name(int reason);  /* "OK", "EOF", "BLOCK_TYPE", ...; "UNKNOWN" for any other value; NULL before d4g_init */
 
+/* ---- embedded streams: where, in a file whose layout the library does not know, are the zlib and gzip streams? ----
+ * (the reference's own wish list, deft4j-cmd/.../cmd/CMDUtil.java:120-125: "General support for optimising embedded GZip /
+ * ZLib / deflate streams in other files".)  Every byte offset of every file is tested on the device; the survivors are
+ * parsed, decoded and checked against their own trailer there, so a reported stream is wrong only when a 32-bit checksum
+ * matches by accident.  What counts as a stream:
+ *   zlib at offset o: o + 2 <= len; CMF = file[o], FLG = file[o+1]; (CMF & 15) == 8; (CMF >> 4) <= 7;
+ *     (CMF * 256 + FLG) % 31 == 0; (FLG & 0x20) == 0 (no preset dictionary).  The payload starts at o + 2.  The trailer is
+ *     the 4 bytes right after the consumed payload, inside the file, big-endian, equal to the Adler-32 of the decoded bytes.
+ *   gzip at offset o: the header bytes are 1f 8b 08 and FLG = file[o+3] has (FLG & 0xE0) == 0.  The 10 fixed header bytes
+ *     are followed, in RFC 1952 order, by FEXTRA (XLEN, little-endian 16 bits, plus that many bytes), FNAME
+ *     (zero-terminated), FCOMMENT (zero-terminated) and FHCRC (2 bytes, skipped and not checked — as
+ *     containers.GZFile.read and K/GZFile.java:42-87 do).  All of these lie inside the file.  The trailer is the 8 bytes
+ *     after the payload: CRC-32, little-endian, equal to that of the decoded bytes, then ISIZE, little-endian, equal to
+ *     decoded_len mod 2^32.
+ *   payload: it parses by the library's own parser rule, exactly as d4g_inflate would on file[payload_offset:], through a
+ *     block with BFINAL set; no back-reference reaches before payload_offset; decoded_len >= min_decoded (default 0).
+ *     Raw DEFLATE without a wrapper is not searched for: nothing confirms it.
+ *   overlap: within a file, in ascending offset, a confirmed stream is reported iff offset >= the end (offset + total_len)
+ *     of the last reported stream.  So a wrapper that lies inside another stream's compressed bytes, or inside its header
+ *     or trailer, is not reported — a complete zlib stream carried verbatim in a stored block, for one.
+ * Results are sorted by (file, offset); *found is released with d4g_free (NULL when nothing was found).  A file of 2 GiB or
+ * more is refused with D4G_ERR_ARG.  A gzip FNAME / FCOMMENT is walked by one thread to its terminator. */
+#define D4G_FOUND_ZLIB 1
+#define D4G_FOUND_GZIP 2
+typedef struct d4g_found_stream {
+    int32_t file, kind;          /* index into the call's file list; D4G_FOUND_* */
+    int64_t offset;              /* first byte of the wrapper's header */
+    int64_t payload_offset;      /* first byte of the raw DEFLATE stream */
+    int64_t payload_len;         /* bytes the parse consumed (d4g_inflate's *consumed) */
+    int64_t total_len;           /* header + payload + trailer */
+    int64_t decoded_len, size_bits;   /* size_bits = DeflateStream.getSizeBits */
+    uint32_t crc32, adler32;     /* of the decoded bytes, both always filled */
+    int32_t n_blocks, reserved;
+} d4g_found_stream;
+typedef struct d4g_find_options { int32_t kinds /* OR of (1 << D4G_FOUND_*), 0 = all */, reserved; int64_t min_decoded; } d4g_find_options;
+typedef struct d4g_find_stats {
+    /* offsets tested; offsets whose header predicate held; of those, first block parsed; whole chain parsed; trailer
+     * matched; reported after the overlap rule */
+    int64_t bytes_scanned, header_candidates, first_block_ok, parsed, confirmed, reported, kernel_launches;
+    double ms_total, ms_kernels; /* host wall clock of the call; device time of its kernels (HIP events) */
+} d4g_find_stats;
+int d4g_find_streams(size_t n, const uint8_t* const* file, const size_t* file_len, const d4g_find_options* opt /* NULL: defaults */,
+                     d4g_found_stream** found /* d4g_free */, size_t* n_found, d4g_find_stats* stats /* may be NULL */);
+
 /* ---- one-shot wrappers ----
  * Deft.optimiseDeflateStream for n streams: out[i]/out_len[i] are set only when status[i] ==
  * D4G_STREAM_CHANGED (else out[i] = NULL and the caller returns its original array). */
