@@ -39,7 +39,9 @@ class d4g_stats(ctypes.Structure):
                 ("ms_zopfli_emit", ctypes.c_double), ("zopfli_blocks", ctypes.c_int64), ("zopfli_position_iterations", ctypes.c_int64),
                 ("rounds_fused", ctypes.c_int64), ("fused_fallbacks", ctypes.c_int64), ("persist_fallbacks", ctypes.c_int64), ("rounds_cluster", ctypes.c_int64),
                 ("ms_verify", ctypes.c_double), ("ms_verify_kernels", ctypes.c_double), ("verify_streams", ctypes.c_int64), ("verify_bytes", ctypes.c_int64),
-                ("copy_segments", ctypes.c_int64), ("copy_rounds", ctypes.c_int64)]
+                ("copy_segments", ctypes.c_int64), ("copy_rounds", ctypes.c_int64),
+                ("recover_streams", ctypes.c_int64), ("recover_bytes", ctypes.c_int64), ("ms_recover", ctypes.c_double),
+                ("ms_recover_kernels", ctypes.c_double)]
 
 
 class d4g_encoder_spec(ctypes.Structure):
@@ -101,7 +103,7 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
            "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
            "d4g_debug_device_blocks", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name",
-           "d4g_find_streams"]
+           "d4g_find_streams", "d4g_batch_recover", "d4g_batch_copy_recovered", "d4g_recover_streams"]
 
 
 def load_library(path=None):
@@ -220,6 +222,13 @@ def load_library(path=None):
     L.d4g_find_streams.restype = ctypes.c_int
     L.d4g_find_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_find_options),
                                    ctypes.POINTER(ctypes.POINTER(d4g_found_stream)), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_find_stats)]
+    L.d4g_batch_recover.restype = ctypes.c_int
+    L.d4g_batch_recover.argtypes = [ctypes.c_void_p]
+    L.d4g_batch_copy_recovered.restype = ctypes.c_int
+    L.d4g_batch_copy_recovered.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.d4g_recover_streams.restype = ctypes.c_int
+    L.d4g_recover_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p),
+                                      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_parse_error)]
     if path is None:
         _lib = L
     return L
@@ -412,6 +421,26 @@ class Batch:
             raise RuntimeError("d4g_batch_parse_error: " + self.L.d4g_last_error().decode())
         return _parse_error_dict(e)
 
+    def recover(self):
+        """d4g_batch_recover: decode what precedes the first failure of every failed stream (once; recovered() asks by itself)."""
+        rc = self.L.d4g_batch_recover(self.h)
+        if rc != 0:
+            raise RuntimeError("d4g_batch_recover: " + self.L.d4g_last_error().decode())
+        return self
+
+    def recovered(self, i):
+        """d4g_batch_copy_recovered: the bytes of stream i that decode before its first failure — parse_error(i)["decoded_offset"]
+        of them; the whole decoded stream where it parsed."""
+        n = ctypes.c_size_t()
+        rc = self.L.d4g_batch_copy_recovered(self.h, i, None, 0, ctypes.byref(n))
+        if rc != 0:
+            raise RuntimeError("d4g_batch_copy_recovered: " + self.L.d4g_last_error().decode())
+        buf = ctypes.create_string_buffer(max(1, n.value))
+        rc = self.L.d4g_batch_copy_recovered(self.h, i, buf, n.value, ctypes.byref(n))
+        if rc != 0:
+            raise RuntimeError("d4g_batch_copy_recovered: " + self.L.d4g_last_error().decode())
+        return buf.raw[:n.value]
+
     def locate(self, i, offset, final=True):
         """Decoded byte `offset` of stream i -> (block index, byte within that block), by the stream's block list."""
         at = 0
@@ -533,6 +562,28 @@ def diagnose_streams(streams, lib=None):
     if rc != 0:
         raise RuntimeError("d4g_diagnose_streams: " + L.d4g_last_error().decode())
     return [_parse_error_dict(out[i]) for i in range(n)]
+
+
+def recover_streams(streams, lib=None):
+    """d4g_recover_streams: inflate every raw DEFLATE stream as far as it goes -> list of (bytes, the dict of Batch.parse_error);
+    a stream that parses gives all its bytes and reason PARSE_OK, one that does not the decoded_offset bytes before its first
+    failure."""
+    L = lib or _need()
+    n = len(streams)
+    keep = [bytes(s) for s in streams]
+    arr = (ctypes.c_char_p * max(1, n))(*keep)
+    lens = (ctypes.c_size_t * max(1, n))(*[len(s) for s in keep])
+    out = (ctypes.c_void_p * max(1, n))()
+    olen = (ctypes.c_size_t * max(1, n))()
+    why = (d4g_parse_error * max(1, n))()
+    rc = L.d4g_recover_streams(n, arr, lens, out, olen, why)
+    if rc != 0:
+        raise RuntimeError("d4g_recover_streams: " + L.d4g_last_error().decode())
+    res = []
+    for i in range(n):
+        res.append((ctypes.string_at(out[i], olen[i]), _parse_error_dict(why[i])))
+        L.d4g_free(out[i])
+    return res
 
 
 def find_streams(files, kinds=0, min_decoded=0, lib=None, stats=False):

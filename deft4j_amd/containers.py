@@ -460,6 +460,28 @@ def explain_failures(files, formats=None, lib=None):
     return out
 
 
+def recover_files(files, formats=None, lib=None):
+    """What can be saved of damaged files: the containers are read as optimise_files and explain_failures read them (a file
+    they refuse has no streams: its list is empty), every stream of every file is parsed in one batch, and per file the answer
+    is a list of dict(stream, name, data, complete, error) — stream index within the file, stream name, the decoded bytes
+    (all of them where the stream parsed: complete=True, error=None; else the bytes before its first failure and the dict of
+    Batch.parse_error, whose decoded_offset is len(data)).  Later intact members of a multi-member file are not pieced on;
+    find_streams locates those."""
+    _, payloads, owner = _read_files(files, formats, lib)
+    out = [[] for _ in files]
+    if not payloads:
+        return out
+    batch = Batch(payloads, lib=lib).parse()
+    try:
+        for q, (i, name) in enumerate(owner):
+            ok = batch.result(q)["status"] >= 0
+            out[i].append(dict(stream=len(out[i]), name=name, data=batch.recovered(q), complete=ok,
+                               error=None if ok else batch.parse_error(q)))
+    finally:
+        batch.close()
+    return out
+
+
 def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, verify=False):
     """files: list of bytes.  formats: optional list of container instances / None (auto-detect) / "raw" /
     "embedded" (EmbeddedFile: zlib and gzip streams wherever they lie in the file).

@@ -75,15 +75,17 @@ struct HStream {
 };
 
 struct Batch {
-    struct PBlock { int type, bfinal; i64 bitPos, endBit, nTok, uLen, sizeBits, nRef; int firstBatch; i64 refSpan = -1; i64 hdrBits = 0; };   // refSpan: records the block occupies in refs even when it is STORED (LZ77 front end)
+    struct PBlock { int type, bfinal; i64 bitPos, endBit, nTok, uLen, sizeBits, nRef; int firstBatch; i64 refSpan = -1; i64 hdrBits = 0; int partial = 0; };   // refSpan: records the block occupies in refs even when it is STORED (LZ77 front end); partial: the tokens before a failure (recover), uLen their bytes
     struct PStream {
         int status = 0; std::vector<PBlock> blocks; i64 nTok = 0, nU = 0, consumed = 0, sizeBits = 0; i64 uBaseFixed = -1;   // uBaseFixed: the decoded bytes already sit in U (LZ77 front end: the raw input)
         i64 failBlock = -1, failBit = -1, failU = 0;   // status != 0: the block that did not parse (blocks accepted before it), its first bit, the bytes decoded before it
+        std::vector<PBlock> accepted;                  // status != 0: those blocks (`blocks` is empty then), for recover()
     };
     struct ParseError { int reason = 0; i64 block = -1, blockBit = -1, bitPos = -1, decoded = -1, value = -1; };
     struct Layout {     // layout_blocks: the running totals of the per-block arrays and what the emit / copy passes need
         std::vector<int32_t> realBlocks;   // device blocks that come straight from the parse (not merge arenas)
         std::vector<D4GEmitIn> emits;
+        std::vector<D4GRecoverIn> partials;   // blocks decoded up to a failure (a recovery's side batch only)
         std::vector<D4GTokRange> ranges;
         int masksAlloc = 1;
         i64 maskWords = 0, binMaskWords = 0, passMemoWords = 0, tokTot = 0, uTot = 0, refTot = 0;
@@ -123,6 +125,10 @@ struct Batch {
     std::vector<PStream> ps;
     std::vector<ParseError> parseErrors;   // why a stream did not parse: one record per stream, made on the first question
     bool diagnosed = false;
+    // what decodes before each failed stream's first failure: made on the first question (recover), kept until the batch goes
+    bool recovered = false;
+    RtBuf<uint8_t> dRecU;                  // the side batch's decoded bytes
+    std::vector<i64> recBase, recLen;      // per stream: where its recovered bytes start in dRecU, and how many (parsed streams: 0)
     RtBuf<D4GChunkBatch> dChunkBatches;    // the probe's verified chunk starts, replayed by the emit pass: what chunkPool points to
     RtBuf<unsigned> dChunkNext;
     D4GChunkPool chunkPool = {nullptr, nullptr, 0};
@@ -166,6 +172,7 @@ struct Batch {
     void walk_chains(const std::vector<ChainStart>& starts, const BlockMap& M, std::vector<PStream>& out, int maxBlocks);
     void scan_candidates(const std::vector<D4GScanTile>& tiles, i64 totalBytes, std::vector<D4GProbeIn>& cands, std::vector<D4GProbeOut>& pout);
     void diagnose();
+    void recover();
     void layout_blocks(bool merge, bool needSlots, Layout& LY);
     int add_block(Layout& LY, bool needSlots, int stream, const HBlock& hb, i64 maskWordsCap, int type);
     void alloc_block_tables(const Layout& LY, bool needSlots);

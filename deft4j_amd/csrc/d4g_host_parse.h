@@ -173,7 +173,7 @@ inline void Batch::walk_chains(const std::vector<ChainStart>& starts, const Bloc
     for (size_t i = 0; i < n; i++) {
         out[i].nU = upos[i];
         out[i].sizeBits = spos[i];
-        if (out[i].status != 0) { out[i].blocks.clear(); out[i].nTok = 0; out[i].nU = 0; }
+        if (out[i].status != 0) { out[i].accepted.swap(out[i].blocks); out[i].blocks.clear(); out[i].nTok = 0; out[i].nU = 0; }
     }
 }
 
@@ -182,6 +182,7 @@ inline void Batch::walk_chains(const std::vector<ChainStart>& starts, const Bloc
 inline void Batch::parse_probe() {
     size_t n = streams.size();
     diagnosed = false; parseErrors.clear();   // (answers of an earlier parse go with it)
+    recovered = false; dRecU.reset(); recBase.clear(); recLen.clear();
     RtEvent e0, e1;
     e0.record();
     BlockMap M;
@@ -229,6 +230,96 @@ inline void Batch::diagnose() {
     }
     parseErrors.swap(res);
     diagnosed = true;
+}
+
+// ---- what decodes before the first failure (d4g_batch_recover) ----
+// The diagnosis says where every failed stream stops: `decoded` bytes into the stream, `decoded - failU` of them in the
+// failing block.  A side batch over this batch's device input decodes, per failed stream, the accepted blocks and those
+// tokens of the failing block that fit this budget, through the ordinary layout, emit and copy passes; its decoded bytes
+// stay here.  Nothing of this batch's own tables is touched, and a batch without failed streams launches and allocates nothing.
+inline void Batch::recover() {
+    if (recovered) return;
+    diagnose();
+    const double t0 = now_ms();
+    const size_t n = std::min(ps.size(), streams.size());
+    std::vector<size_t> owner;
+    for (size_t i = 0; i < n; i++) {
+        if (ps[i].status == 0 || parseErrors[i].decoded <= 0) continue;
+        if (parseErrors[i].decoded >= (1LL << 31)) throw std::runtime_error("recover: stream " + std::to_string(i) + " decodes to 2 GiB or more before its failure");
+        if (parseErrors[i].decoded < ps[i].failU) throw std::runtime_error("recover: the diagnosis of stream " + std::to_string(i) + " lies before its failing block");
+        owner.push_back(i);
+    }
+    std::vector<i64> base(streams.size(), 0), len(streams.size(), 0);
+    if (owner.empty()) { recBase.swap(base); recLen.swap(len); recovered = true; return; }
+    const size_t m = owner.size();
+    double msKernels = 0;
+    // the failing blocks with a budget: how many tokens and records fit it
+    std::vector<D4GRecoverIn> part;
+    std::vector<size_t> partOf;
+    for (size_t k = 0; k < m; k++) {
+        const PStream& P = ps[owner[k]];
+        const i64 budget = parseErrors[owner[k]].decoded - P.failU;
+        if (budget <= 0) continue;
+        D4GRecoverIn ri;
+        memset(&ri, 0, sizeof(ri));
+        ri.em.stream = (int32_t)owner[k]; ri.em.bitPos = P.failBit; ri.em.firstBatch = -1; ri.budget = budget;
+        part.push_back(ri);
+        partOf.push_back(k);
+    }
+    std::vector<D4GProbeOut> cnt(part.size());
+    if (!part.empty()) {
+        RtScratch tmp;
+        RtEvent e0, e1;
+        D4GRecoverIn* dPart = tmp.upload(part);
+        D4GProbeOut* dCnt = tmp.alloc<D4GProbeOut>(part.size());
+        e0.record();
+        RT_LAUNCH(k_recover_count, part.size(), parse_threads(), dStreams, dPart, dCnt);
+        e1.record();
+        stats.kernel_launches++;
+        rt_d2h(cnt.data(), dCnt, part.size() * sizeof(D4GProbeOut));
+        tmp.release();
+        msKernels += rt_elapsed_ms(e0, e1);
+        for (size_t q = 0; q < part.size(); q++)
+            if (cnt[q].status != 0 || cnt[q].uLen != part[q].budget)   // the diagnosis is the authority: the decode has to meet it
+                throw std::runtime_error("recover: the failing block of stream " + std::to_string(owner[partOf[q]]) + " does not decode to the diagnosed offset");
+    }
+    struct Borrow {   // the input bytes go back to this batch on every way out
+        Batch& F; Batch& G;
+        Borrow(Batch& F, Batch& G) : F(F), G(G) { G.dIn = std::move(F.dIn); }
+        ~Borrow() { try { rt_sync_all(); } catch (...) {} F.dIn = std::move(G.dIn); }
+    };
+    Batch G;
+    memset(&G.stats, 0, sizeof(G.stats));
+    Borrow borrow(*this, G);
+    G.streams.resize(m);
+    G.ps.resize(m);
+    for (size_t k = 0; k < m; k++) {
+        const PStream& P = ps[owner[k]];
+        G.streams[k].inOff = streams[owner[k]].inOff;
+        G.streams[k].inLen = streams[owner[k]].inLen;
+        PStream& Q = G.ps[k];
+        Q.blocks = P.accepted;
+        for (PBlock& pb : Q.blocks) { pb.firstBatch = -1; Q.nTok += pb.nTok; Q.nU += pb.uLen; }   // (the scan's chunk records went back with the parse)
+        if (Q.nU != P.failU) throw std::runtime_error("recover: the accepted blocks of stream " + std::to_string(owner[k]) + " do not add up");
+    }
+    for (size_t q = 0; q < part.size(); q++) {
+        PStream& Q = G.ps[partOf[q]];
+        PBlock pb = {cnt[q].type, 0, part[q].em.bitPos, 0, cnt[q].nTok, cnt[q].uLen, 0, (i64)cnt[q].nRef, -1};
+        pb.partial = 1;
+        Q.blocks.push_back(pb);
+        Q.nTok += pb.nTok;
+        Q.nU += pb.uLen;
+    }
+    G.build_blocks(false, false);
+    msKernels += G.msParseKernels;
+    for (size_t k = 0; k < m; k++) { base[owner[k]] = G.streams[k].uBase; len[owner[k]] = G.streams[k].nU; stats.recover_bytes += G.streams[k].nU; }
+    dRecU = std::move(G.dU);
+    recBase.swap(base); recLen.swap(len);
+    recovered = true;
+    stats.kernel_launches += G.stats.kernel_launches;
+    stats.recover_streams += (i64)m;
+    stats.ms_recover_kernels += msKernels;
+    stats.ms_recover += now_ms() - t0;
 }
 
 // ---- device block table: host block lists, device descriptors and every per-block array, from `ps` ----
@@ -318,7 +409,8 @@ inline void Batch::layout_blocks(bool merge, bool needSlots, Layout& LY) {
                 nHuff++;
             }
             hb.ordinal = (int)s.blocks.size();
-            LY.emits.push_back(em);
+            if (pb.partial) LY.partials.push_back({em, pb.uLen, pb.nTok, pb.nRef});
+            else LY.emits.push_back(em);
             LY.ranges.push_back({(int32_t)si, pb.type == D4G_STORED ? 1 : 0, hb.tokStart, hb.tokCount, upos, pb.uLen});
             s.blocks.push_back(hb);
             tpos += pb.nTok;
@@ -392,12 +484,19 @@ inline void Batch::build_blocks(bool merge, bool needSlots) {
     e0.record();
     int32_t* dBad = nullptr;          // per stream: a back-reference reached before the start of the stream
     RtScratch tmp;                    // device buffers the queued kernels still read: released after the wait below
-    if (!LY.emits.empty()) {
+    if (!LY.emits.empty() || !LY.partials.empty()) {
         // 3. emit
-        D4GEmitIn* dEm = tmp.upload(LY.emits);
         D4GParseOut po = {dTok, dU, dStates, dRefs, dTokRef};
-        RT_LAUNCH(k_emit_blocks, LY.emits.size(), parse_threads(), dStreams, dEm, po, errors(), chunkPool);
-        stats.kernel_launches++;
+        if (!LY.emits.empty()) {
+            D4GEmitIn* dEm = tmp.upload(LY.emits);
+            RT_LAUNCH(k_emit_blocks, LY.emits.size(), parse_threads(), dStreams, dEm, po, errors(), chunkPool);
+            stats.kernel_launches++;
+        }
+        if (!LY.partials.empty()) {
+            D4GRecoverIn* dPart = tmp.upload(LY.partials);
+            RT_LAUNCH(k_recover_emit, LY.partials.size(), parse_threads(), dStreams, dPart, po, errors());
+            stats.kernel_launches++;
+        }
         // 4. decoded bytes (no wait in here: the bin statistics follow on the same stream; the flags come back behind them, one wait for both)
         dBad = tmp.alloc_zero<int32_t>(n, 16);
         if (!R.segs.empty()) copy_block_local(LY.ranges, R, dBad, tmp);

@@ -496,11 +496,15 @@ __device__ inline void d4g_diag_token(const D4GDecTab* lit, const D4GDecTab* dis
 
 // DIAG (k_diagnose_blocks): the block is known not to parse; the same decode, but every way out records why in `dg`, and the
 // token loop goes on past an invalid code to find the first failure in token order (`hist` = bytes decoded before the block).
-template <bool EMIT, bool DIAG = false>
+// PART (k_recover_count / k_recover_emit): the block is known not to parse after `budget` decoded bytes (the diagnosis says
+// so); the same decode, but only the tokens that fit the budget are counted (EMIT: written, at most capTok tokens and
+// capRef records).  No state, histogram or chunk record is kept for such a block.
+template <bool EMIT, bool DIAG = false, bool PART = false>
 __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long long bitPos, int strict, D4GProbeOut& po,
                                 const D4GEmitIn* em, const D4GParseOut& out, const D4GChunkPool& pool, D4GDiagRec* dg = nullptr,
-                                long long hist = 0) {
+                                long long hist = 0, long long budget = 0, long long capTok = 0, long long capRef = 0) {
     static_assert(!(EMIT && DIAG), "a diagnosis writes no tokens");
+    static_assert(!(PART && DIAG), "the diagnosis comes first: a partial decode follows its answer");
     __shared__ D4GParseLds L;
     const int tid = threadIdx.x, NL = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = NL >> 6;
     D4GBitReader br;   // thread 0's
@@ -548,6 +552,9 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
         return;
     }
     if (strict && btype != 2) return;
+    if constexpr (PART) {
+        if (btype == 0) return;   // (a stored block fails in its header only: nothing of it is recovered)
+    }
     if (btype == 0) {
         // DeflateBlockUncompressed.parse — B/deflate/DeflateBlockUncompressed.java:23-36
         // BitInputStream.readBits returns -1 once EOF is hit (B/io/BitInputStream.java:59-82) and `-1 & 0xffff` is
@@ -733,15 +740,21 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
     long long endBit = 0;
     constexpr int C = D4G_CHUNK_BITS;
     // one chunk: mode 0 counts, mode 1 also stores the tokens (the thread's output offsets are known then), mode 2 (the
-    // diagnosis) stops at the first back-reference that reaches further back than the `uAt` bytes decoded before the chunk
+    // diagnosis) stops at the first back-reference that reaches further back than the `uAt` bytes decoded before the chunk,
+    // modes 3 and 4 (the partial decode) count / store the tokens that decode to no more than `room` bytes
     [[maybe_unused]] int farPos = 0x7fffffff, farDist = 0;
     [[maybe_unused]] unsigned farU = 0;
+    [[maybe_unused]] unsigned room = 0;
     auto decode_chunk = [&](auto writeTag, int start, int endc, int limRel, unsigned tokAt, unsigned uAt, unsigned refAt, int& exitp,
                             unsigned& n, unsigned& u, unsigned& r, unsigned& lb, int& need, int& fl) D4G_LAMBDA_INLINE {
-        constexpr bool WRITE = decltype(writeTag)::value == 1, FAR = decltype(writeTag)::value == 2;
+        constexpr bool CAP = decltype(writeTag)::value >= 3;
+        constexpr bool WRITE = decltype(writeTag)::value == 1 || decltype(writeTag)::value == 4, FAR = decltype(writeTag)::value == 2;
         int pos = start;
         n = 0; u = 0; r = 0; lb = 0; need = -0x40000000; fl = 0;
         while (pos < endc) {
+            if constexpr (CAP) {
+                if (u >= room) break;   // the next token is the failing one, or lies behind it
+            }
             uint64_t bits = d4g_peek64(L.inbuf, pos);
             int avail = limRel - pos;
             int cl = 0, sym;
@@ -750,7 +763,7 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
             int used = cl;
             if (sym <= 256) {
                 if (WRITE) {
-                    atomicAdd(&S->hist[sym], 1u);
+                    if constexpr (!CAP) atomicAdd(&S->hist[sym], 1u);
                     tokOut[tokAt + n] = make_uint2((uint32_t)sym, uStart32 + uAt + u);
                 }
                 n++;
@@ -773,10 +786,15 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
                 if constexpr (FAR) {
                     if (dist > (int)uAt + (int)u) { farPos = pos; farDist = dist; farU = u; break; }
                 }
+                if constexpr (CAP) {
+                    if (u + (unsigned)len > room) break;
+                }
                 if (dist - (int)u > need) need = dist - (int)u;
                 if (WRITE) {
-                    atomicAdd(&S->hist[sym], 1u);
-                    atomicAdd(&S->hist[D4G_NLIT + ds], 1u);
+                    if constexpr (!CAP) {
+                        atomicAdd(&S->hist[sym], 1u);
+                        atomicAdd(&S->hist[D4G_NLIT + ds], 1u);
+                    }
                     tokOut[tokAt + n] = make_uint2((uint32_t)len | ((uint32_t)edge << 15) | ((uint32_t)dist << 16), uStart32 + uAt + u);
                     refOut[refAt + r] = make_uint4(d4g_ref_pack(len, sym, ds, eb + deb), uStart32 + uAt + u, 0u, 0u);
                     tokRefOut[tokAt + n] = refBase32 + refAt + r;
@@ -847,7 +865,7 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
         __syncthreads();
         const int f = L.firstStop;
         const bool valid = tid <= f;
-        if constexpr (!DIAG) {
+        if constexpr (!DIAG && !PART) {
             if (f < NL && L.xFlag[f] == 2) return;   // invalid code or out of input: the block does not parse
         }
         unsigned pn = valid ? n : 0u, pu = valid ? u : 0u, pr = valid ? r : 0u, plb = valid ? lb : 0u;
@@ -903,6 +921,43 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
                 }
                 return;
             }
+        }
+        if constexpr (PART) {
+            // Threads up to f hold true tokens and know the bytes decoded before their chunk.  The tokens before the failing
+            // element decode to exactly `budget` bytes and the failing token adds none that fit, so every thread takes its
+            // tokens while they stay within what is left of the budget: a second count, a second scan, then the stores.
+            const long long before = (long long)nU + (long long)(su - pu);
+            room = valid && before < budget ? (unsigned)(budget - before) : 0u;   // (budget < 2^31)
+            int e2, need2, fl2;
+            unsigned n2 = 0, u2 = 0, r2 = 0, lb2 = 0;
+            if (room) decode_chunk(std::integral_constant<int, 3>{}, start, endc, limRel, 0u, 0u, 0u, e2, n2, u2, r2, lb2, need2, fl2);
+            unsigned tn = n2, tu = u2, tr = r2;
+            for (int d = 1; d < 64; d <<= 1) {
+                unsigned a = __shfl_up(tn, d), b = __shfl_up(tu, d), c2 = __shfl_up(tr, d);
+                if (lane >= d) { tn += a; tu += b; tr += c2; }
+            }
+            __syncthreads();   // (the wave totals of the first scan have been read)
+            if (lane == 63) { L.wsN[wave] = tn; L.wsU[wave] = tu; L.wsR[wave] = tr; }
+            __syncthreads();
+            unsigned oN = 0, oR = 0, tN = 0, tU = 0, tR = 0;
+            for (int w = 0; w < nw; w++) {
+                if (w < wave) { oN += L.wsN[w]; oR += L.wsR[w]; }
+                tN += L.wsN[w]; tU += L.wsU[w]; tR += L.wsR[w];
+            }
+            tn += oN; tr += oR;
+            if (EMIT) {
+                if ((long long)nTok + tN > capTok || (long long)nRef + tR > capRef) return;   // more than the count pass saw: write nothing (uniform)
+                if (room) decode_chunk(std::integral_constant<int, 4>{}, start, endc, limRel, nTok + (tn - n2), (unsigned)before, nRef + (tr - r2), e2, n2,
+                                       u2, r2, lb2, need2, fl2);
+            }
+            nTok += tN;
+            nU += tU;
+            nRef += tR;
+            if (f < NL || (long long)nU >= budget) break;
+            s0 = baseBits + L.xExit[NL - 1];
+            G += (long long)NL * C;
+            __syncthreads();   // (xExit / wave sums are rewritten by the next batch)
+            continue;
         }
         if (EMIT && valid) {
             int e2, need2, fl2;
@@ -961,7 +1016,7 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
     po.needHist = (long long)needHist;
     po.nRef = (int32_t)nRef;
     po.firstBatch = firstBatch == -2 ? -1 : firstBatch;
-    if (EMIT) {
+    if (EMIT && !PART) {
         D4GState* g = out.states + em->stateIdx;
         for (int i = tid; i < (int)(sizeof(D4GState) / 4); i += NL) ((uint32_t*)g)[i] = ((uint32_t*)S)[i];
     }
@@ -1016,6 +1071,28 @@ __global__ void __launch_bounds__(D4G_PARSE_MAXTHREADS) k_emit_blocks(const D4GS
     D4GProbeOut po;
     d4g_parse_block<true>(streams[em.stream], em.bitPos, 0, po, &em, out, pool);
     if (threadIdx.x == 0 && (po.status != 0 || po.uLen != em.uLen)) atomicAdd(errors, 1);
+}
+
+// Recovery (d4g_batch_recover): the block that did not parse, decoded up to the failure the diagnosis found.  One workgroup
+// per block; the count pass sizes the token arrays, the emit pass fills them like k_emit_blocks does for a whole block.
+struct D4GRecoverIn {
+    D4GEmitIn em;          // count pass: stream and bitPos only
+    long long budget;      // bytes the block's tokens before the failing element decode to
+    long long nTok, nRef;  // emit pass: what the count pass found
+};
+__global__ void __launch_bounds__(D4G_PARSE_MAXTHREADS) k_recover_count(const D4GStreamDesc* streams, const D4GRecoverIn* in, D4GProbeOut* outp) {
+    const D4GRecoverIn ri = in[blockIdx.x];
+    D4GProbeOut po;
+    D4GParseOut none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    d4g_parse_block<false, false, true>(streams[ri.em.stream], ri.em.bitPos, 0, po, nullptr, none, D4GChunkPool{nullptr, nullptr, 0u}, nullptr, 0, ri.budget);
+    if (threadIdx.x == 0) outp[blockIdx.x] = po;
+}
+__global__ void __launch_bounds__(D4G_PARSE_MAXTHREADS) k_recover_emit(const D4GStreamDesc* streams, const D4GRecoverIn* in, D4GParseOut out, int32_t* errors) {
+    const D4GRecoverIn ri = in[blockIdx.x];
+    D4GProbeOut po;
+    d4g_parse_block<true, false, true>(streams[ri.em.stream], ri.em.bitPos, 0, po, &ri.em, out, D4GChunkPool{nullptr, nullptr, 0u}, nullptr, 0, ri.budget,
+                                       ri.nTok, ri.nRef);
+    if (threadIdx.x == 0 && (po.status != 0 || po.uLen != ri.budget || po.nTok != ri.nTok || po.nRef != ri.nRef)) atomicAdd(errors, 1);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -226,6 +226,18 @@ d4g_parse_error batch_parse_error(d4g_batch& b, size_t i) {
     const Batch::ParseError& e = b.impl.parseErrors[i];
     return d4g_parse_error{e.reason, (int32_t)e.block, e.blockBit, e.bitPos, e.decoded, e.value};
 }
+// ---- what decodes before the first failure (Batch::recover, d4g_host_parse.h) ----
+// where stream i's recovered bytes lie (device) and how many: a stream that parsed answers with its decoded bytes
+const uint8_t* batch_recovered(d4g_batch& b, size_t i, size_t* len) {
+    Batch& B = b.impl;
+    if (b.lz || B.ps[i].status == 0) {
+        *len = (size_t)B.streams[i].nU;
+        return B.dU + B.streams[i].uBase;
+    }
+    B.recover();
+    *len = (size_t)B.recLen[i];
+    return *len ? B.dRecU + B.recBase[i] : nullptr;
+}
 // has the library written stream i's final bytes?  (an encoder batch writes every output; an optimiser batch only what changed)
 bool stream_written(const d4g_batch& b, size_t i) {
     return b.lz ? b.impl.streams[i].status == 0 : stream_status(b, i) == D4G_STREAM_CHANGED;
@@ -1267,6 +1279,53 @@ int d4g_diagnose_streams(size_t n, const uint8_t* const* in, const size_t* in_le
         for (size_t i = 0; i < n; i++) out[i] = batch_parse_error(*b, i);
         return D4G_OK;
     });
+}
+
+int d4g_batch_recover(d4g_batch* b) {
+    return api(b, [&] {
+        if (!b) return fail(D4G_ERR_ARG, "null batch");
+        if (b->lz) return D4G_OK;
+        if (b->impl.ps.size() < b->impl.streams.size()) return fail(D4G_ERR_ARG, "the batch has not been parsed");
+        b->impl.recover();
+        return D4G_OK;
+    });
+}
+
+int d4g_batch_copy_recovered(d4g_batch* b, size_t i, uint8_t* dst, size_t cap, size_t* len) {
+    return api(b, [&] {
+        if (!b) return fail(D4G_ERR_ARG, "null batch");
+        if (i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
+        if (!b->lz && i >= b->impl.ps.size()) return fail(D4G_ERR_ARG, "the batch has not been parsed");
+        if ((b->lz || b->impl.ps[i].status == 0) && b->impl.streams[i].nU > 0 && !b->impl.dU) return fail(D4G_ERR_ARG, "the batch has not been decoded");
+        size_t n = 0;
+        const uint8_t* src = batch_recovered(*b, i, &n);
+        if (len) *len = n;
+        if (!dst) return D4G_OK;
+        if (cap < n) return fail(D4G_ERR_ARG, "output buffer too small");
+        if (n) rt_d2h(dst, src, n);
+        return D4G_OK;
+    });
+}
+
+int d4g_recover_streams(size_t n, const uint8_t* const* in, const size_t* in_len, uint8_t** out, size_t* out_len, d4g_parse_error* why) {
+    if (n && (!in || !in_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
+    for (size_t i = 0; why && i < n; i++) why[i] = PARSE_ERROR_NONE;
+    Outputs o(n, out, out_len);
+    const int rc = o.commit(api(nullptr, [&] {
+        std::unique_ptr<d4g_batch> b = make_batch(n, in, in_len);
+        engine().init();
+        b->impl.parse_probe();
+        b->impl.build_blocks(false, false);
+        for (size_t i = 0; i < n; i++) {
+            const uint8_t* src = batch_recovered(*b, i, &out_len[i]);
+            out[i] = host_copy(src, out_len[i]);
+            if (why) why[i] = batch_parse_error(*b, i);
+        }
+        return D4G_OK;
+    }));
+    if (rc != D4G_OK)
+        for (size_t i = 0; why && i < n; i++) why[i] = PARSE_ERROR_NONE;
+    return rc;
 }
 
 const char* d4g_parse_reason_name(int reason) {   // (NULL, like the batch creators, when the guard refuses the call)

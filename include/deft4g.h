@@ -83,6 +83,10 @@ typedef struct d4g_stats {
     /* decoded bytes by block-local copies (D4G_COPY, the default path): segments decoded (one workgroup each) and rounds of
      * the window scan; jump_rounds counts the rounds of the doubling path and stays 0 where no stream takes it */
     int64_t copy_segments, copy_rounds;
+    /* recovery (d4g_batch_recover): failed streams whose leading bytes were decoded, those bytes, wall clock, and device time
+     * of the count pass plus the side batch's emit and copy kernels */
+    int64_t recover_streams, recover_bytes;
+    double ms_recover, ms_recover_kernels;
 } d4g_stats;
 
 /* Select the HIP device (one process per GPU) and create the library's stream.
@@ -296,6 +300,28 @@ typedef struct d4g_parse_error {
 int d4g_batch_parse_error(d4g_batch* b, size_t i, d4g_parse_error* out);  /* after parse / run / run_recompress */
 int d4g_diagnose_streams(size_t n, const uint8_t* const* in, const size_t* in_len, d4g_parse_error* out);
 const char* d4g_parse_reason_name(int reason);  /* "OK", "EOF", "BLOCK_TYPE", ...; "UNKNOWN" for any other value; NULL before d4g_init */
+
+/* ---- what decodes before the first failure ----
+ * The recovered bytes R of stream i.  A stream that parses: its decoded bytes, exactly what d4g_batch_copy_decoded gives.  A
+ * stream that does not: what a sequential decoder following the library's parser rule has produced when it meets the first
+ * failure in token order — the decoded bytes of every block before the failing one, then those of the failing block's tokens
+ * that precede the failing element.  The failing token contributes nothing (an invalid literal/length code; a length whose
+ * distance code or extra bits fail or run out of input; a distance that reaches before the first decoded byte), and a failure
+ * in a block's header (the 3 header bits, BTYPE 3, LEN / NLEN, the counts, the code lengths) contributes nothing of that
+ * block.  len(R) == d4g_parse_error.decoded_offset always (0 included): the diagnosis decides where the failure is, recovery
+ * decodes up to it.  (A stored block whose payload runs past the end of input parses, its missing bytes read as 0xff.)
+ * Recovery runs only when asked: the first question decodes the leading bytes of all failed streams of the batch together, in
+ * a side batch over the same device input, and keeps them until the batch is destroyed; a batch whose streams all parse
+ * launches and allocates nothing.  Nothing else the batch reports changes, before or after a run, and
+ * d4g_batch_copy_decoded still refuses a failed stream.  A prefix of 2 GiB or more is refused (D4G_ERR_RUNTIME).
+ * Later intact members of a multi-member file are not pieced on: d4g_find_streams finds those. */
+int d4g_batch_recover(d4g_batch* b);   /* after parse / run / run_recompress; idempotent; no failed stream: no work */
+int d4g_batch_copy_recovered(d4g_batch* b, size_t i, uint8_t* dst, size_t cap, size_t* len);
+    /* asks d4g_batch_recover itself; dst NULL: length only; a stream that parsed (and every stream of an encoder batch): as copy_decoded */
+int d4g_recover_streams(size_t n, const uint8_t* const* in, const size_t* in_len, uint8_t** out, size_t* out_len,
+                        d4g_parse_error* why /* may be NULL */);
+    /* inflate as far as it goes: out[i] always set (d4g_free), why[i].reason == D4G_PARSE_OK for a stream that parsed;
+     * on failure every out[i] is NULL, out_len[i] 0 and nothing is left allocated */
 
 /* ---- embedded streams: where, in a file whose layout the library does not know, are the zlib and gzip streams? ----
  * (the reference's own wish list, deft4j-cmd/.../cmd/CMDUtil.java:120-125: "General support for optimising embedded GZip /

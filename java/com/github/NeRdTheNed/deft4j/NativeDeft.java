@@ -86,6 +86,11 @@ public final class NativeDeft {
      *  (include/deft4g.h).  The reference prints "Failed to parse deflate stream data" and nothing more. */
     public static native long[] parseError(long batch, int i) throws java.io.IOException;
 
+    /** Inflate every stream as far as it goes: result[i] holds the bytes that decode before stream i's first failure (all of them, and
+     *  reason[i] == 0, where it parses); decodedOffset[i] is their count, reason[i] as in parseError.  The reference returns nothing
+     *  for a stream that does not parse. */
+    public static native byte[][] recoverStreams(byte[][] in, long[] decodedOffset, int[] reason) throws java.io.IOException;
+
     /** Deft.optimiseDeflateStream(byte[], boolean): same contract, including "returns the SAME array when nothing was saved" */
     public static byte[] optimiseDeflateStream(byte[] original, boolean mergeBlocks) {
         final int[] status = new int[1];

@@ -273,6 +273,31 @@ JNIEXPORT jintArray JNICALL JFN(verifyStreams)(JNIEnv* e, jclass c, jobjectArray
     return res;
 }
 
+/* byte[][] recoverStreams(byte[][] in, long[] decodedOffset, int[] reason): inflate every stream as far as it goes.  Entry i is
+ * what decodes before stream i's first failure (all of it, reason[i] == 0, where the stream parses); decodedOffset[i] is its
+ * length.  zcat delivers as much of a cut-off download; the reference delivers nothing. */
+JNIEXPORT jobjectArray JNICALL JFN(recoverStreams)(JNIEnv* e, jclass c, jobjectArray in, jlongArray decodedOut, jintArray reasonOut) {
+    (void)c;
+    in_list L = {0};
+    jobjectArray res = NULL;
+    if (pin(e, in, &L) == 0) {
+        uint8_t** out = calloc((size_t)L.n + 1, sizeof *out);
+        size_t* olen = calloc((size_t)L.n + 1, sizeof *olen);
+        d4g_parse_error* why = calloc((size_t)L.n + 1, sizeof *why);
+        jlong* dec = calloc((size_t)L.n + 1, sizeof *dec);
+        jint* reason = calloc((size_t)L.n + 1, sizeof *reason);
+        if (out && olen && why && dec && reason && d4g_recover_streams((size_t)L.n, L.ptr, L.len, out, olen, why) == D4G_OK) {
+            for (jsize i = 0; i < L.n; i++) { dec[i] = (jlong)olen[i]; reason[i] = why[i].reason; }
+            res = to_java(e, L.n, out, olen);
+            if (res && (*e)->GetArrayLength(e, decodedOut) >= L.n) (*e)->SetLongArrayRegion(e, decodedOut, 0, L.n, dec);
+            if (res && (*e)->GetArrayLength(e, reasonOut) >= L.n) (*e)->SetIntArrayRegion(e, reasonOut, 0, L.n, reason);
+        } else throw_io(e, "d4g_recover_streams");
+        free(out); free(olen); free(why); free(dec); free(reason);
+    }
+    unpin(e, &L);
+    return res;
+}
+
 /* long[6] parseError(long batch, int i): why stream i of a d4g_batch did not parse, as {reason (D4G_PARSE_*, 0: it parsed),
  * block, block_bit_pos, bit_pos, decoded_offset, value}.  `batch` is a d4g_batch* a native caller holds.  The reference only
  * prints "Failed to parse deflate stream data". */
