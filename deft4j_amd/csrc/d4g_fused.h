@@ -74,6 +74,11 @@ struct D4FParams {
     int32_t nOps[2];
     int32_t maxRounds;      // optimiseBlock rounds to run while the block keeps improving (1 for a merge attempt)
     int32_t regWords;       // blocks of up to this many mask words take the register forms of the mask tasks (64 * D4F_NWR; tests: 0)
+    // ids a round may hand out before it reports D4F_INFO_FALLBACK, in one word (D4F_CAPS): at most D4F_MAXM / D4F_MAXC /
+    // D4F_MAXH, which size the tables (the tests lower them to reach that exit on small blocks; the code cap counts the
+    // reserved ids 0 and 1)
+    uint32_t caps;
+    int32_t pad;
     D4GRoundResult* results;   // [nActive][D4F_MAXROUNDS]
     int32_t* roundInfo;        // [nActive]: rounds completed | D4F_INFO_*
     long long* stats;          // optional [32] counters
@@ -116,6 +121,7 @@ struct D4FClArena {
     D4FClCmd slot[D4F_CL_SLOTS];
 };
 
+#define D4F_CAPS(masks, codes, hdrs) ((uint32_t)(masks) | (uint32_t)(hdrs) << 10 | (uint32_t)(codes) << 20)
 #define D4F_INFO_FALLBACK 0x10000   // the round after the completed ones did not fit the tables: run it with the level executor
 #define D4F_INFO_MORE 0x20000       // still improving when maxRounds was reached
 
@@ -242,7 +248,7 @@ struct D4FLds {
     alignas(4) uint8_t hsState[D4F_MAXC];
     int32_t hsBits[D4F_MAXC];
     alignas(4) uint8_t hsLane[D4F_MAXC];
-    int32_t nCode, pad2;
+    int32_t nCode, capC;       // capC, capM, capH: ids a round may hand out (unpacked from D4FParams.caps, D4F_CAPS)
     // what the kernel was called with, the block, the round in progress
     D4GCtx c;
     D4GBlock b;
@@ -251,7 +257,8 @@ struct D4FLds {
     int32_t nOps, curType, rounds, info, improved, regWords;
     struct D4FClArena* cl;    // cluster mode (k_search_cluster): the command area shared with the helper workgroups, else null
     int32_t clEpoch, clDoneWg; // commands posted so far / items this workgroup finished in the command in hand
-    int32_t which, pad3;       // the block's index in the launch's active list
+    int32_t which;             // the block's index in the launch's active list
+    int16_t capM, capH;
     long long curSize;
 };
 
@@ -926,7 +933,7 @@ D4F_TASK void d4f_apply_task(int idx) {
         }
         int mNew = m;
         if (!leaf) {
-            if (lane == 0) { int id = atomicAdd(&F.nMask, 1); if (id >= D4F_MAXM) { F.fallback = 1; id = 0; } W.misc[0] = id; }
+            if (lane == 0) { int id = atomicAdd(&F.nMask, 1); if (id >= F.capM) { F.fallback = 1; id = 0; } W.misc[0] = id; }
             d4g_wave_sync();
             mNew = W.misc[0];
             d4g_wave_sync();
@@ -978,7 +985,7 @@ D4F_TASK void d4f_apply_task(int idx) {
     }
     int mNew = m;
     if (!leaf) {
-        if (lane == 0) { int id = atomicAdd(&F.nMask, 1); if (id >= D4F_MAXM) { F.fallback = 1; id = 0; } W.misc[0] = id; }
+        if (lane == 0) { int id = atomicAdd(&F.nMask, 1); if (id >= F.capM) { F.fallback = 1; id = 0; } W.misc[0] = id; }
         d4g_wave_sync();
         mNew = W.misc[0];
         d4g_wave_sync();
@@ -1140,7 +1147,7 @@ D4F_TASK void d4f_least_task(int idx) {
             }
             W.misc[1] = rem; W.misc[2] = remSize;
             int id = 0;
-            if (rem >= 0) { id = atomicAdd(&F.nMask, 1); if (id >= D4F_MAXM) { F.fallback = 1; id = 0; } }
+            if (rem >= 0) { id = atomicAdd(&F.nMask, 1); if (id >= F.capM) { F.fallback = 1; id = 0; } }
             W.misc[0] = id;
         }
         d4g_wave_sync();
@@ -1252,7 +1259,7 @@ D4F_TASK void d4f_least_task(int idx) {
         }
         W.misc[1] = rem; W.misc[2] = remSize;
         int id = 0;
-        if (rem >= 0) { id = atomicAdd(&F.nMask, 1); if (id >= D4F_MAXM) { F.fallback = 1; id = 0; } }
+        if (rem >= 0) { id = atomicAdd(&F.nMask, 1); if (id >= F.capM) { F.fallback = 1; id = 0; } }
         W.misc[0] = id;
     }
     d4g_wave_sync();
@@ -1462,7 +1469,7 @@ D4F_TASK void d4f_hdr_task(int idx) {
     }
     d4g_wave_sync();
     if (err && lane == 0) atomicAdd(c.errors, 1);
-    if (lane == 0) { int id = atomicAdd(&F.nHdr, 1); if (id >= D4F_MAXH) { F.fallback = 1; id = 0; } H.pad = id; }
+    if (lane == 0) { int id = atomicAdd(&F.nHdr, 1); if (id >= F.capH) { F.fallback = 1; id = 0; } H.pad = id; }
     d4g_wave_sync();
     const int hNew = H.pad;
     D4FHdr& dst = G.hdr[hNew];
@@ -1572,7 +1579,7 @@ D4F_TASK void d4f_tree_publish(int slotIdx) {
     const int nCodeNow = __shfl(F.nCode, 0);   // (every lane reads before lane 0 writes)
     if (code < 0) {
         code = nCodeNow;
-        if (code >= D4F_MAXC) { if (lane == 0) F.fallback = 1; code = 0; }
+        if (code >= F.capC) { if (lane == 0) F.fallback = 1; code = 0; }
         else {
             D4FCode& cd = G.code[code];
             for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) ((uint32_t*)cd.lens)[i] = lw[i];
@@ -1592,7 +1599,7 @@ D4F_TASK void d4f_tree_publish(int slotIdx) {
     const int nHdrNow = __shfl(F.nHdr, 0);
     if (defNow < 0) {   // the code's default header (rewriteHeader()) — a function of the lengths
         int hid = nHdrNow;
-        if (hid >= D4F_MAXH) { if (lane == 0) F.fallback = 1; hid = 0; }
+        if (hid >= F.capH) { if (lane == 0) F.fallback = 1; hid = 0; }
         else {
             D4FPairs& pb = G.pairs[1 + code];
             for (int i = lane; i < T.nPairs; i += 64) pb.pairs[i] = T.pairs[i];
@@ -1936,7 +1943,7 @@ D4F_TASK void d4f_cl_apply_phase(int nq) {
             const uint32_t key = F.pass[F.qAll[d4f_qoff(D4F_Q_APPLY) + base + threadIdx.x]].key - 1;
             const int leaf = (int)((key >> 16) & 1u);
             int mNew = 0;
-            if (!leaf) { mNew = atomicAdd(&F.nMask, 1); if (mNew >= D4F_MAXM) { F.fallback = 1; mNew = 0; } }
+            if (!leaf) { mNew = atomicAdd(&F.nMask, 1); if (mNew >= F.capM) { F.fallback = 1; mNew = 0; } }
             D4FClTask& T = C.task[threadIdx.x];
             d4f_cl_set(&T.m, (int)(key & 255u)); d4f_cl_set(&T.code, (int)((key >> 8) & 127u)); d4f_cl_set(&T.prune, (int)((key >> 15) & 1u));
             d4f_cl_set(&T.leaf, leaf); d4f_cl_set(&T.mNew, mNew); d4f_cl_set(&T.rem, -1);
@@ -2016,7 +2023,7 @@ D4F_TASK void d4f_cl_least_phase(int nq) {
                 }
             }
             int mNew = 0;
-            if (rem >= 0) { mNew = atomicAdd(&F.nMask, 1); if (mNew >= D4F_MAXM) { F.fallback = 1; mNew = 0; } }
+            if (rem >= 0) { mNew = atomicAdd(&F.nMask, 1); if (mNew >= F.capM) { F.fallback = 1; mNew = 0; } }
             D4FClTask& U = C2->task[threadIdx.x];
             d4f_cl_set(&U.m, T.m); d4f_cl_set(&U.code, T.code); d4f_cl_set(&U.mode, mode); d4f_cl_set((int32_t*)&U.full, (int)T.full);
             d4f_cl_set(&U.rem, rem); d4f_cl_set(&U.mNew, mNew); d4f_cl_set(&U.pad0[0], remSize);
@@ -2288,6 +2295,10 @@ __device__ __forceinline__ void d4f_block_init(const D4GCtx& cArg, const D4FPara
         const int blk = cArg.active[which];
         F.nCode = 2;
         F.regWords = P.regWords < 64 * D4F_NWR ? P.regWords : 64 * D4F_NWR;
+        const int capM = (int)(P.caps & 1023u), capH = (int)((P.caps >> 10) & 1023u), capC = (int)(P.caps >> 20);
+        F.capM = (int16_t)(capM < D4F_MAXM ? capM : D4F_MAXM);
+        F.capC = capC < D4F_MAXC ? capC : D4F_MAXC;
+        F.capH = (int16_t)(capH < D4F_MAXH ? capH : D4F_MAXH);
         F.c = cArg;
         F.b = cArg.blocks[blk];
         F.G = d4f_glob(cArg, blk);

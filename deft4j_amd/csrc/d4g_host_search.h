@@ -26,6 +26,7 @@ inline D4FParams Batch::fused_params(int maxRounds, D4GRoundResult* results, int
     P.nOps[0] = (int)E.progDyn.ops.size(); P.nOps[1] = (int)E.progFixed.ops.size();
     P.maxRounds = maxRounds;
     P.regWords = fused_reg_words();
+    P.caps = D4F_CAPS(fused_cap_masks(), fused_cap_codes(), fused_cap_hdrs());
     P.results = results;
     P.roundInfo = info;
     P.stats = fused_stats() ? E.dOpStats.get() : nullptr;
@@ -110,7 +111,7 @@ inline bool Batch::run_cluster(int blk, D4GRoundResult* out) {
     stats.ms_state_kernels += ms;
     tmp.release();
     if (debug_rounds()) fprintf(stderr, "cluster search: block of %lld back-references, %.3f ms%s\n", (long long)hBlocks[blk].refCount, ms, (info & D4F_INFO_FALLBACK) ? " (did not fit)" : "");
-    if ((info & D4F_INFO_FALLBACK) || (info & 0xffff) < 1) return false;
+    if ((info & D4F_INFO_FALLBACK) || (info & 0xffff) < 1) { stats.cluster_fallbacks++; return false; }
     gpuType[blk] = r.newType;
     stats.rounds_fused += 1;
     stats.rounds_cluster += 1;
@@ -141,7 +142,7 @@ inline std::vector<std::vector<D4GRoundResult>> Batch::run_fused(const std::vect
         D4GCtx c = make_ctx(E.progDyn, nA);
         int cap = 0;   // most rounds any of them may still run
         for (int i = 0; i < nA; i++) cap = std::max(cap, maxRounds - (int)chains[todo[i]].size());
-        const D4FParams P = fused_params(std::min(cap, (int)D4F_MAXROUNDS), dRes, dInfo);
+        const D4FParams P = fused_params(std::min(cap, fused_cap_rounds()), dRes, dInfo);
         RtEvent e0, e1;
         e0.record();
         RT_LAUNCH(k_search_fused, nA, fused_block(), c, P);
@@ -163,7 +164,7 @@ inline std::vector<std::vector<D4GRoundResult>> Batch::run_fused(const std::vect
             for (int k = 0; k < n; k++) ch.push_back(r[(size_t)i * D4F_MAXROUNDS + k]);
             if (n) gpuType[sub[i]] = ch.back().newType;
             stats.rounds_fused += n;
-            if (info[i] & D4F_INFO_FALLBACK) fb.push_back(todo[i]);
+            if (info[i] & D4F_INFO_FALLBACK) { fb.push_back(todo[i]); stats.fused_fallbacks_mid += n > 0; }
             else if ((info[i] & D4F_INFO_MORE) && (int)ch.size() < maxRounds) next.push_back(todo[i]);
         }
         if (!fb.empty()) {   // one round with the level executor, then back here if it improved
@@ -177,6 +178,7 @@ inline std::vector<std::vector<D4GRoundResult>> Batch::run_fused(const std::vect
             }
         }
         std::sort(next.begin(), next.end());
+        stats.fused_relaunches += (int64_t)next.size();
         todo.swap(next);
     }
     tmp.release();

@@ -81,6 +81,17 @@ static inline int fused_block() {
 // the LDS path.  D4G_FUSED_STATS, now: set = per-phase accounting into the op statistics (scripts/fused_profile.py).
 static inline int fused_reg_words() { return knob_now("D4G_FUSED_REG_WORDS", 64 * D4F_NWR); }
 static inline bool fused_stats() { return knob_now("D4G_FUSED_STATS") != nullptr; }
+// D4G_FUSED_CAP_MASKS / _CODES / _HDRS, now (defaults D4F_MAXM, D4F_MAXC, D4F_MAXH: the tables' sizes): ids a round of the fused
+// and cluster kernels may hand out before it reports a table overflow; the tests lower them to take that exit on small blocks.
+// Clamped to [1, D4F_MAXM], [2, D4F_MAXC] (ids 0 and 1 are reserved, and the code table lasts a launch) and [1, D4F_MAXH];
+// mask 0 and header 0 are the block's own.  (The code cap bounds the ids a Huffman rebuild is given; d4f_round_setup's reset of a
+// nearly full code table, at D4F_MAXC - 32, and the id it gives the incoming code do not look at it.)  D4G_FUSED_CAP_ROUNDS, now (default D4F_MAXROUNDS, clamped to [1, D4F_MAXROUNDS]):
+// rounds of a block per launch of k_search_fused, after which a block that still improves is launched again.
+static inline int knob_clamped(const char* name, int lo, int hi) { return std::min(std::max(knob_now(name, hi), lo), hi); }
+static inline int fused_cap_masks() { return knob_clamped("D4G_FUSED_CAP_MASKS", 1, D4F_MAXM); }
+static inline int fused_cap_codes() { return knob_clamped("D4G_FUSED_CAP_CODES", 2, D4F_MAXC); }
+static inline int fused_cap_hdrs() { return knob_clamped("D4G_FUSED_CAP_HDRS", 1, D4F_MAXH); }
+static inline int fused_cap_rounds() { return knob_clamped("D4G_FUSED_CAP_ROUNDS", 1, D4F_MAXROUNDS); }
 // D4G_WIDE_BLOCK, once: threads per workgroup of a separate launch for token-pass-only ops: 256, 512, 1024, or 0 (default and
 // fallback) = same launch as the others.  Emulator: 0.  D4G_WIDE_KINDS, once: bit k = ops of kind k go to that launch.
 static inline int wide_block() {

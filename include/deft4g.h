@@ -87,6 +87,11 @@ typedef struct d4g_stats {
      * of the count pass plus the side batch's emit and copy kernels */
     int64_t recover_streams, recover_bytes;
     double ms_recover, ms_recover_kernels;
+    /* fused executor, which way a block left a launch: fused_fallbacks_mid = fallbacks (counted in fused_fallbacks too) of a
+     * launch that had completed at least one round of that block; fused_relaunches = blocks launched again in k_search_fused,
+     * after the per-launch round limit or after an improving level-executor round; cluster_fallbacks = rounds the cluster
+     * kernel could not hold and handed to the level / persistent executors */
+    int64_t fused_fallbacks_mid, fused_relaunches, cluster_fallbacks;
 } d4g_stats;
 
 /* Select the HIP device (one process per GPU) and create the library's stream.
