@@ -42,7 +42,8 @@ class d4g_stats(ctypes.Structure):
                 ("copy_segments", ctypes.c_int64), ("copy_rounds", ctypes.c_int64),
                 ("recover_streams", ctypes.c_int64), ("recover_bytes", ctypes.c_int64), ("ms_recover", ctypes.c_double),
                 ("ms_recover_kernels", ctypes.c_double),
-                ("fused_fallbacks_mid", ctypes.c_int64), ("fused_relaunches", ctypes.c_int64), ("cluster_fallbacks", ctypes.c_int64)]
+                ("fused_fallbacks_mid", ctypes.c_int64), ("fused_relaunches", ctypes.c_int64), ("cluster_fallbacks", ctypes.c_int64),
+                ("scan_kept", ctypes.c_int64)]
 
 
 class d4g_encoder_spec(ctypes.Structure):

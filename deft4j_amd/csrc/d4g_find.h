@@ -10,6 +10,7 @@
 #define D4G_FOUND_KIND_ZLIB 1   // = D4G_FOUND_ZLIB / D4G_FOUND_GZIP of the C ABI
 #define D4G_FOUND_KIND_GZIP 2
 struct D4GFindCand { int32_t file, kind; long long offset, payload; };
+struct D4GScanTile { int32_t stream; int32_t pad; long long byteStart; };   // one workgroup's bytes of a file
 #define D4G_FIND_TILE 2048
 #define D4G_FIND_LOCAL 64   // candidates a workgroup collects before it touches the global list (random bytes give about one per tile)
 
@@ -33,7 +34,7 @@ D4G_DEV long long d4g_gzip_payload(const uint8_t* data, long long len, long long
 }
 
 // One thread per byte offset, the tile staged in LDS as k_scan_headers stages its own.  Candidates are collected per
-// workgroup and take one global atomic per tile (the scheme and the reason of k_scan_headers); a tile with more than
+// workgroup and take one global atomic per tile (an atomic per hit on one counter is far slower); a tile with more than
 // D4G_FIND_LOCAL of them sends the rest straight to the global list.  The count may pass `cap`: the host then runs the
 // kernel again with a list that holds them all.
 __global__ void __launch_bounds__(256) k_find_wrappers(const D4GStreamDesc* files, const D4GScanTile* tiles, int kinds, D4GFindCand* cands,

@@ -170,7 +170,7 @@ struct Batch {
     void parse_probe();
     void scan_inputs(BlockMap& M);
     void walk_chains(const std::vector<ChainStart>& starts, const BlockMap& M, std::vector<PStream>& out, int maxBlocks);
-    void scan_candidates(const std::vector<D4GScanTile>& tiles, i64 totalBytes, std::vector<D4GProbeIn>& cands, std::vector<D4GProbeOut>& pout);
+    void scan_candidates(const uint32_t* dTileStart, unsigned nTiles, i64 totalBytes, std::vector<D4GProbeIn>& cands, std::vector<D4GProbeOut>& pout);
     void diagnose();
     void recover();
     void layout_blocks(bool merge, bool needSlots, Layout& LY);

@@ -16,7 +16,7 @@ inline void Batch::create(size_t n, const uint8_t* const* in, const size_t* len,
         off += 16;
         stats.bytes_in += (i64)len[i];
     }
-    i64 total = off + D4G_INCH + 64;
+    i64 total = off + D4G_INCH + 64;   // (the block decoders and the header scan stage whole windows from a stream's last bytes)
     dIn.alloc_zero((size_t)total);
     for (size_t i = 0; i < n; i++) {
         if (fromDevice) rt_d2d(dIn + streams[i].inOff, in[i], len[i]);
@@ -28,53 +28,54 @@ inline void Batch::create(size_t n, const uint8_t* const* in, const size_t* len,
 }
 
 // ---- parse: header scan -> block probes -> chain -> emit -> pointer jumping ----
-// Steps 1-2: header scan, header pre-filter (one lane per candidate), speculative probes of the survivors.  Only the
-// candidates that parse come back, with their probe results; the probe also fills the chunk pool the emit pass replays.
-inline void Batch::scan_candidates(const std::vector<D4GScanTile>& tiles, i64 totalBytes, std::vector<D4GProbeIn>& cands, std::vector<D4GProbeOut>& pout) {
+// hit records that come back with the hit count, in one read: up to 45 KB whatever the count turns out to be, the price
+// of not waiting for the count first (a batch of config 2 has about 340 hits)
+#ifndef D4G_PROBE_HITS_FIRST
+#define D4G_PROBE_HITS_FIRST 512
+#endif
+// Steps 1-2: header scan (one launch: prolog, code-length code, walk over the coded lengths), speculative probes of the
+// survivors.  Only the candidates that parse come back, with their probe results; the probe also fills the chunk pool the
+// emit pass replays.  dTileStart: per stream the index of its first tile (scan_inputs).
+inline void Batch::scan_candidates(const uint32_t* dTileStart, unsigned nTiles, i64 totalBytes, std::vector<D4GProbeIn>& cands, std::vector<D4GProbeOut>& pout) {
     // (every step below ends in a blocking read: a buffer that goes back here is no longer in use)
-    RtBuf<D4GScanTile> dTiles;
-    dTiles.alloc(tiles.size());
-    rt_h2d(dTiles, tiles.data(), tiles.size() * sizeof(D4GScanTile));
-    unsigned cap = (unsigned)std::max<i64>(65536, totalBytes / 4);
-    RtBuf<unsigned> dN;
-    dN.alloc(1);
+    // One result buffer: the scan's two counters and the probe's hit count (16 bytes, cleared together), then the hit
+    // records, so that one read brings the hit count and the first records.  The survivors are about the streams' blocks;
+    // the list is sized for a block per 128 input bytes and made again when a batch holds more.
+    const size_t head = 16;
+    unsigned cap = (unsigned)std::max<i64>(4096, totalBytes / 128);
+    RtBuf<uint8_t> dRes;
     RtBuf<D4GProbeIn> dCands;
-    unsigned nc = 0;
+    unsigned counts[2] = {0, 0};
     for (int attempt = 0; attempt < 2; attempt++) {
         dCands.alloc((size_t)cap);
-        rt_memset(dN, 0, 4);
-        RT_LAUNCH(k_scan_headers, tiles.size(), 256, dStreams, dTiles, dCands, dN, cap);
+        dRes.alloc(head + (size_t)cap * sizeof(D4GProbeHit));
+        rt_memset(dRes, 0, head);
+        RT_LAUNCH(k_scan_headers, nTiles, 256, dStreams, dTileStart, (unsigned)streams.size(), dCands, (unsigned*)dRes.get(), cap);
         stats.kernel_launches++;
-        rt_d2h(&nc, dN, 4);
-        if (nc <= cap) break;
-        cap = nc + 1024;
+        rt_d2h(counts, dRes, sizeof(counts));
+        if (counts[0] <= cap) break;
+        cap = counts[0] + 1024;
     }
-    // 1b. header pre-filter (one lane per candidate) — 2. speculative probes of the survivors; only the candidates
-    // that parse come back
-    stats.scan_candidates = (i64)nc;
+    // 2. speculative probes of the survivors; only the candidates that parse come back
+    const unsigned nc = counts[0];
+    stats.scan_candidates = (i64)counts[1];
+    stats.scan_kept = (i64)nc;
     if (nc) {
-        RtBuf<D4GProbeIn> dKept;
-        dKept.alloc((size_t)nc);
-        rt_memset(dN, 0, 4);
-        RT_LAUNCH(k_prefilter_headers, (nc + 63) / 64, 64, dStreams, dCands, nc, dKept, dN);
-        stats.kernel_launches++;
-        rt_d2h(&nc, dN, 4);
-        dCands = std::move(dKept);
-    }
-    if (nc) {
-        RtBuf<D4GProbeHit> dHits;
-        dHits.alloc((size_t)nc);
-        rt_memset(dN, 0, 4);
+        D4GProbeHit* dHits = (D4GProbeHit*)(dRes.get() + head);
+        unsigned* dN = (unsigned*)dRes.get() + 2;
         chunkPool.cap = (unsigned)std::min<i64>(1 << 30, totalBytes * 8 / (64 * D4G_CHUNK_BITS) + 2 * (i64)nc * (parse_threads() / 64) + 64);   // one record per wave and batch
         chunkPool.batches = dChunkBatches.alloc((size_t)chunkPool.cap);
         chunkPool.next = dChunkNext.alloc_zero(4);
         RT_LAUNCH(k_probe_blocks, nc, parse_threads(), dStreams, dCands, (D4GProbeOut*)nullptr, nc, dHits, dN, chunkPool);
         stats.kernel_launches++;
+        const size_t first = std::min<size_t>(nc, D4G_PROBE_HITS_FIRST);
+        std::vector<uint8_t> back(head + first * sizeof(D4GProbeHit));
+        rt_d2h(back.data(), dRes, back.size());
         unsigned nh = 0;
-        rt_d2h(&nh, dN, 4);
+        memcpy(&nh, back.data() + 8, 4);
         std::vector<D4GProbeHit> hits(nh);
-        rt_d2h(hits.data(), dHits, (size_t)nh * sizeof(D4GProbeHit));
-        dHits.reset();
+        if (nh) memcpy(hits.data(), back.data() + head, std::min<size_t>(nh, first) * sizeof(D4GProbeHit));
+        if (nh > first) rt_d2h(hits.data() + first, dHits + first, (nh - first) * sizeof(D4GProbeHit));
         cands.resize(nh);
         pout.resize(nh);
         for (unsigned k = 0; k < nh; k++) { cands[k] = hits[k].in; pout[k] = hits[k].out; }
@@ -85,21 +86,27 @@ inline void Batch::scan_candidates(const std::vector<D4GScanTile>& tiles, i64 to
 // (per stream: bit position -> probe result), which every chain that crosses the stream shares.
 inline void Batch::scan_inputs(BlockMap& M) {
     size_t n = streams.size();
-    std::vector<D4GStreamDesc> sd(n);
-    std::vector<D4GScanTile> tiles;
-    i64 totalBytes = 0;
+    // the stream table and, behind it in the same upload, where each stream's scan tiles begin (n + 1 entries: a scan
+    // workgroup finds its stream there by binary search, so no per-tile table is made or sent)
+    const size_t startBytes = (n + 1) * sizeof(uint32_t);
+    std::vector<D4GStreamDesc> sd(n + (startBytes + sizeof(D4GStreamDesc) - 1) / sizeof(D4GStreamDesc));
+    uint32_t* tileStart = (uint32_t*)(sd.data() + n);
+    i64 totalBytes = 0, nTiles = 0;
     for (size_t i = 0; i < n; i++) {
         sd[i].data = dIn + streams[i].inOff;
         sd[i].len = streams[i].inLen;
         sd[i].uBase = 0;
         sd[i].uLen = 0;
-        for (i64 b = 0; b < streams[i].inLen; b += D4G_SCAN_TILE) tiles.push_back({(int32_t)i, 0, b});
+        tileStart[i] = (uint32_t)nTiles;
+        nTiles += (streams[i].inLen + D4G_SCAN_TILE - 1) / D4G_SCAN_TILE;
+        if (nTiles > 0x7fffffffLL) throw std::runtime_error("batch holds 2^31 or more scan tiles: split it");
         totalBytes += streams[i].inLen;
     }
-    dStreams.alloc(n);
-    rt_h2d(dStreams, sd.data(), n * sizeof(D4GStreamDesc));
+    tileStart[n] = (uint32_t)nTiles;
+    dStreams.alloc(n, startBytes);
+    rt_h2d(dStreams, sd.data(), n * sizeof(D4GStreamDesc) + startBytes);
     std::vector<D4GProbeIn> cands;
-    if (!tiles.empty()) scan_candidates(tiles, totalBytes, cands, M.pout);
+    if (nTiles) scan_candidates((const uint32_t*)(dStreams.get() + n), (unsigned)nTiles, totalBytes, cands, M.pout);
     // candidate maps: bit position -> probe result
     M.byStream.assign(n, {});
     for (size_t k = 0; k < cands.size(); k++)

@@ -5,8 +5,8 @@
 // decoded bytes, and one initial state per Huffman block (code lengths, header RLE pairs,
 // symbol histogram, bit sizes).  The reference walks the stream serially; here
 //   1. k_scan_headers     tests EVERY bit position for a plausible dynamic-block header
-//                         (BTYPE, HLIT/HDIST range, complete code-length code) — brute force
-//                         that a 256-CU chip does in well under a millisecond per 10 MB;
+//                         (BTYPE, HLIT/HDIST range, complete code-length code, complete codes behind
+//                         it) — brute force that a 256-CU chip does in well under a millisecond per 10 MB;
 //   2. k_probe_blocks     one wave per candidate decodes the block without output and reports
 //                         where it ends (speculative candidates must also have complete codes);
 //                         the host links candidates into the one chain that starts at bit 0 and
@@ -241,195 +241,277 @@ __device__ __forceinline__ int d4g_decode_sym_packed(const D4GDecTab* T, uint64_
     } while (0)
 
 // ---------------------------------------------------------------------------------------
-// 1. Header scan.  One thread per input byte tests its 8 bit positions.
+// 1. Header scan: which bit positions are worth a probe.  One workgroup per tile of a stream, one launch, three phases
+// over the tile's bytes staged in LDS, each phase fed by a compacted list of the one before it:
+//   A  every bit position: the 13-bit prolog (BTYPE = dynamic, HLIT <= 29, HDIST <= 29)              -> list A
+//   B  list A, one lane per entry: the code-length code is complete (Kraft sum) and has two codes   -> list B,
+//      the scan's candidates (stats.scan_candidates)
+//   C  list B, one lane per entry, packed into one wave: the walk over the coded code lengths
+//      (d4g_header_survives)                                                                        -> the global list
+// A plausible prolog and a complete code-length code at a random bit position are common (22 % and 0.09 % of all
+// positions in zlib output); the probe would spend a whole workgroup and ~300 serial symbol decodes on each, the walk
+// leaves little more than the stream's true blocks.  A full list is drained through the next phase and scanning goes on:
+// no list size drops a position or lets it past a test.
 // ---------------------------------------------------------------------------------------
-struct D4GScanTile { int32_t stream; int32_t pad; long long byteStart; };
-#define D4G_SCAN_TILE 2048
-#define D4G_SCAN_LOCAL 1024   // candidates a workgroup collects before it touches the global list
+#ifndef D4G_SCAN_TILE
+#define D4G_SCAN_TILE 4096   // bytes of a stream per workgroup
+#endif
+// A header begun in the tile's last bit ends at most 17 + 19 x 3 + 316 x 14 = 4498 bits (563 bytes) later, and the walk's
+// window reads 12 bytes from its position; rounded to the 16-byte staging loads.  The input buffer is readable this far
+// past any stream's end: Batch::create pads the input buffer with D4G_INCH + 64 bytes for the block decoders' staging.
+#define D4G_SCAN_HALO 576
+#ifndef D4G_SCAN_LIST_A
+#define D4G_SCAN_LIST_A 2048   // prolog passers collected before phase B runs
+#endif
+#ifndef D4G_SCAN_LIST_B
+#define D4G_SCAN_LIST_B 1024   // candidates collected before phase C runs
+#endif
+// The prolog wants bit 1 clear and bit 2 set, so no two neighbouring positions pass: 256 bytes hold at most 1024 passers.
+#define D4G_SCAN_ROUNDS_A (D4G_SCAN_LIST_A / 1024)
+static_assert(D4G_SCAN_LIST_A >= 1024 && D4G_SCAN_LIST_A % 1024 == 0, "list A holds whole rounds of 256 bytes");
+static_assert(D4G_SCAN_LIST_B >= 256, "list B holds at least what one pass of the workgroup over list A can add");
+static_assert(D4G_SCAN_TILE % 256 == 0 && D4G_SCAN_TILE * 8 <= 65536, "tile-relative bit offsets are 16-bit list entries");
+static_assert(D4G_SCAN_TILE + D4G_SCAN_HALO <= D4G_INCH, "a stream's last tile and its halo are staged from inside the input buffer's padding");
+static_assert((D4G_SCAN_TILE * 8 + 4498 + 31) / 32 + 3 <= (D4G_SCAN_TILE + D4G_SCAN_HALO) / 4, "the halo holds the longest header and its window");
 
-__global__ void __launch_bounds__(256) k_scan_headers(const D4GStreamDesc* streams, const D4GScanTile* tiles, D4GProbeIn* cands,
-                                                      unsigned* nCands, unsigned capCands) {
-    alignas(16) __shared__ uint8_t buf[D4G_SCAN_TILE + 32];
-    __shared__ uint32_t lpos[D4G_SCAN_LOCAL];   // bit offsets (inside the tile) of this workgroup's candidates
-    __shared__ unsigned lcount, gbase;
-    if (threadIdx.x == 0) lcount = 0;
-    const D4GScanTile tile = tiles[blockIdx.x];
-    const D4GStreamDesc sd = streams[tile.stream];
-    for (int i = threadIdx.x * 16; i < D4G_SCAN_TILE + 32; i += blockDim.x * 16)
-        *(uint4*)(buf + i) = *(const uint4*)(sd.data + tile.byteStart + i);  // the input buffer is padded past len
+// Bits of a staged tile for d4g_header_survives: positions count from the first bit of `words`.
+struct D4GStagedBits {
+    const uint32_t* words;
+    __device__ __forceinline__ uint64_t peek(int p) const {   // 64 bits at bit p
+        const int w = p >> 5, sh = p & 31;
+        const uint64_t lo = words[w] | ((uint64_t)words[w + 1] << 32);
+        const uint64_t hi = words[w + 2];
+        return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+    }
+    __device__ __forceinline__ uint32_t peek32(int p) const {   // 32 bits at bit p
+        return d4g_alignbit(words[(p >> 5) + 1], words[p >> 5], p & 31);
+    }
+};
+
+// Phase C's predicate on one candidate (prolog at bit `pos` of `src`, the stream ends at bit `nbits`; both count from
+// src's first bit).  The lane walks the coded code lengths with a private 128-entry decode table (T, CLN: the lane's
+// slices of LDS, elements `stride` bytes apart), keeping only the Kraft sums: a candidate survives when its literal/length
+// code is complete with an end-of-block code and its distance code is complete or has at most one code — the conditions
+// the strict probe applies (d4g_parse_block), so nothing the probe would accept is dropped.  The candidate's code-length code must be
+// complete (phase B's test): its table build then writes all 128 entries of T, which therefore needs no clearing between
+// candidates and holds no entry without a code.
+template <class Src>
+__device__ __forceinline__ bool d4g_header_survives(const Src& src, int pos, const int nbits, uint8_t* T, uint8_t* CLN, const int stride) {
+    uint64_t b = src.peek(pos);
+    const int nLit = (int)((b >> 3) & 31) + 257;
+    const int nDist = (int)((b >> 8) & 31) + 1;
+    const int nCl = (int)((b >> 13) & 15) + 4;
+    if (!(((b >> 1) & 3) == 2 && nLit <= 286 && nDist <= 30 && pos + 17 + 3 * nCl <= nbits)) return false;
+    pos += 17;
+    // 19 x 3 bits = 57 bits: one window.  Counts and next codes per length live in 8-bit fields of a word
+    // (no dynamically indexed register arrays); the lengths themselves in the lane's LDS slice.
+    const uint64_t c = src.peek(pos);
+    uint64_t cnt64 = 0;
+    for (int k = 0; k < 19; k++) CLN[k * stride] = 0;
+    for (int i = 0; i < nCl; i++) {
+        const int l = (int)((c >> (3 * i)) & 7);
+        CLN[D4G_CL_ORDER[i] * stride] = (uint8_t)l;
+        if (l) cnt64 += 1ULL << (8 * l);
+    }
+    pos += 3 * nCl;
+    // canonical codes (Huffman.buildCodes), LUT over 7 bits (LSB-first windows: codes are bit-reversed)
+    uint64_t next64 = 0;
+    int code = 0;
+    for (int l = 1; l <= 7; l++) {
+        code = (code + (l > 1 ? (int)((cnt64 >> (8 * (l - 1))) & 255) : 0)) << 1;
+        next64 |= (uint64_t)(code & 255) << (8 * l);
+    }
+#pragma unroll 1
+    for (int k = 0; k < 19; k++) {
+        const int l = CLN[k * stride];
+        if (l) {
+            const int cd = (int)((next64 >> (8 * l)) & 255);
+            next64 += 1ULL << (8 * l);
+            unsigned r = 0;
+            for (int bI = 0; bI < l; bI++) r |= ((cd >> bI) & 1u) << (l - 1 - bI);
+            for (unsigned e = r; e < 128; e += (1u << l)) T[e * stride] = (uint8_t)(k | (l << 5));
+        }
+    }
+    const int combined = nLit + nDist;
+    // The walk itself, in 32-bit arithmetic (a complete code of up to 286 lengths sums to 2^15; 316 x 2^14 fits easily).
+    unsigned kraftLit = 0, kraftDist = 0;
+    int i = 0, prev = 0, nDistCodes = 0, eob = 0;
+    uint32_t win = 0;
+    int have = 0;   // bits of win still ahead of pos: a step takes at most 7 + 7, so the window is fetched again below 14
+    while (i < combined) {
+        if (pos + 14 > nbits + 64) return false;
+        if (have < 14) { win = src.peek32(pos); have = 32; }
+        const unsigned e = T[(win & 127) * stride];
+        const int sym = (int)(e & 31), l = (int)(e >> 5);
+        win >>= l;
+        // 16: repeat the previous length 3..6 times (2 extra bits); 17 / 18: 3..10 / 11..138 zeros (3 / 7 extra bits)
+        const int k = sym - 16;
+        const bool rep = k >= 0;
+        const int extra = rep ? (0x070302 >> (8 * k)) & 0xff : 0;
+        const int run = rep ? ((0x0b0303 >> (8 * k)) & 0xff) + (int)(win & ((1u << extra) - 1)) : 1;
+        const int value = rep ? (k == 0 ? prev : 0) : sym;
+        if (k == 0 && i < 1) return false;
+        win >>= extra;
+        pos += l + extra;
+        have -= l + extra;
+        if (pos > nbits || i + run > combined) return false;
+        if (value) {
+            // the run may span the literal/distance boundary
+            const int inLit = i < nLit ? (i + run <= nLit ? run : nLit - i) : 0;
+            kraftLit += (unsigned)inLit << (15 - value);
+            kraftDist += (unsigned)(run - inLit) << (15 - value);
+            nDistCodes += run - inLit;
+            if (i <= 256 && i + run > 256) eob = 1;
+        }
+        prev = value;
+        i += run;
+    }
+    return kraftLit == (1 << 15) && eob && (kraftDist == (1 << 15) || nDistCodes <= 1);
+}
+
+// tileStart: per stream the index of its first tile, nStreams + 1 entries (a stream's tiles are consecutive workgroups).
+// counters[0] counts the survivors (also those past capKept: the host sizes the list again), counters[1] list B's entries.
+__global__ void __launch_bounds__(256, 8) k_scan_headers(const D4GStreamDesc* streams, const uint32_t* tileStart, unsigned nStreams, D4GProbeIn* kept,
+                                                      unsigned* counters, unsigned capKept) {
+    alignas(16) __shared__ uint8_t buf[D4G_SCAN_TILE + D4G_SCAN_HALO];
+    __shared__ uint8_t lut[128 * 64];     // phase C, per lane: 7-bit window -> sym | len << 5; lane-interleaved (entry e of lane j at e * 64 + j)
+    __shared__ uint8_t clens[20 * 64];    // phase C, per lane: the code-length code's lengths, interleaved the same way
+    __shared__ uint16_t listA[D4G_SCAN_LIST_A], listB[D4G_SCAN_LIST_B];   // bit offsets inside the tile
+    __shared__ unsigned cntA, cntB;       // entries ever added; the lists hold those from baseA / baseB on
+    unsigned sLo = 0, sHi = nStreams;     // the last stream whose first tile is not after this one
+    while (sHi - sLo > 1) {
+        const unsigned mid = (sLo + sHi) >> 1;
+        if (tileStart[mid] <= blockIdx.x) sLo = mid; else sHi = mid;
+    }
+    const int stream = (int)sLo;
+    const long long byteStart = (long long)(blockIdx.x - tileStart[sLo]) * D4G_SCAN_TILE;
+    const D4GStreamDesc sd = streams[stream];
+    if (threadIdx.x == 0) { cntA = 0; cntB = 0; }
+    for (int i = threadIdx.x * 16; i < D4G_SCAN_TILE + D4G_SCAN_HALO; i += blockDim.x * 16)
+        *(uint4*)(buf + i) = *(const uint4*)(sd.data + byteStart + i);  // the input buffer is padded past len
     __syncthreads();
-    long long nbits = sd.len * 8;
-    int lane = threadIdx.x & 63;
-    for (int b = threadIdx.x; b < D4G_SCAN_TILE; b += blockDim.x) {
-        // 96 bits starting at byte b: four aligned words of the tile, shifted into place
-        const uint32_t* bw = (const uint32_t*)buf + (b >> 2);
-        const int bsh = (b & 3) * 8;
-        const uint32_t w0 = bw[0], w1 = bw[1], w2 = bw[2], w3 = bw[3];
-        uint64_t lo = (uint64_t)d4g_alignbit(w1, w0, bsh) | ((uint64_t)d4g_alignbit(w2, w1, bsh) << 32);
-        uint32_t hi = d4g_alignbit(w3, w2, bsh);
-        long long bit0 = (tile.byteStart + b) * 8;
-        for (int s = 0; s < 8; s++) {
-            uint64_t v = s ? ((lo >> s) | ((uint64_t)hi << (64 - s))) : lo;   // window bits 0..63
-            uint64_t w = (v >> 32) | ((uint64_t)(hi >> s) << 32);             // window bits 32..95
-            long long p = bit0 + s;
-            bool ok = ((v >> 1) & 3) == 2 && ((v >> 3) & 31) <= 29 && ((v >> 8) & 31) <= 29;
-            int ncl = (int)((v >> 13) & 15) + 4;
-            ok = ok && (p + 17 + 3 * ncl <= nbits);
-            if (ok) {
-                // the code-length code must be complete: sum 2^(7-l) == 128, at least two codes.  Branch-free over the
-                // 3-bit fields: bit planes of the (masked) 57-bit field, one popcount per length value
-                uint64_t f = (v >> 17) | ((w >> 32) << 47);           // window bits 17..80
-                f &= (1ULL << (3 * ncl)) - 1;
-                const uint64_t M = 0x1249249249249249ULL;              // bit 0 of every 3-bit field
-                const uint64_t p0 = f & M, p1 = (f >> 1) & M, p2 = (f >> 2) & M;
-                const uint64_t n0 = ~p0, n1 = ~p1, n2 = ~p2;
-                int kraft = 64 * __popcll(p0 & n1 & n2) + 32 * __popcll(n0 & p1 & n2) + 16 * __popcll(p0 & p1 & n2) +
-                            8 * __popcll(n0 & n1 & p2) + 4 * __popcll(p0 & n1 & p2) + 2 * __popcll(n0 & p1 & p2) + __popcll(p0 & p1 & p2);
-                int used = __popcll(p0 | p1 | p2);
-                ok = kraft == 128 && used >= 2;
+    const long long tileBit0 = byteStart * 8;
+    const long long restBits = sd.len * 8 - tileBit0;   // the stream's end, from the tile's first bit (> 0: the tile begins inside it)
+    const int nbits = restBits > 0x3fffffff ? 0x3fffffff : (int)restBits;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ULL << lane) - 1;
+    // (the waves that run phase C alone take turns from tile to tile, so that those of a compute unit's resident workgroups
+    // do not all sit on one SIMD)
+    const int waveC = (int)(blockIdx.x & 3);
+    const long long restBytes = sd.len - byteStart;
+    const int nRounds = restBytes >= D4G_SCAN_TILE ? D4G_SCAN_TILE / 256 : (int)((restBytes + 255) / 256);   // 256-byte rounds that hold any of the stream
+    unsigned baseA = 0, baseB = 0;
+
+    // Phases A, B and C take turns: after every D4G_SCAN_ROUNDS_A rounds of phase A, phase B empties list A; phase C empties
+    // list B when a pass of phase B might overfill it, and behind the last round.  (One place in the code for each phase:
+    // inlined at two, the walk and its table build made the kernel eight times as long.)
+    for (int r0 = 0;; r0 += D4G_SCAN_ROUNDS_A) {
+        const bool last = r0 >= nRounds;   // the turn behind the last round only empties list B
+        // Phase A: a thread takes the 8 positions of a byte, 256 bytes a round; a wave adds its round to the list with one atomic
+        for (int r = r0; !last && r < r0 + D4G_SCAN_ROUNDS_A && r < nRounds; r++) {
+            const int by = r * 256 + (int)threadIdx.x;
+            const uint32_t* bw = (const uint32_t*)buf + (by >> 2);
+            const uint32_t x = d4g_alignbit(bw[1], bw[0], (by & 3) * 8);   // 32 bits from the byte on: 7 + 13 are needed
+            unsigned long long m[8];   // per position of the byte: the wave's lanes that pass (uniform: scalar registers)
+            unsigned total = 0;
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                const uint32_t v = x >> s;
+                m[s] = __ballot(((v >> 1) & 3) == 2 && ((v >> 3) & 31) <= 29 && ((v >> 8) & 31) <= 29);
+                total += (unsigned)__popcll(m[s]);
             }
-            // candidates are collected per workgroup (one global atomic per tile instead of one per hit: tens of
-            // thousands of atomics on a single counter were most of this kernel's time)
-            unsigned long long m = __ballot(ok);
-            if (m) {
-                unsigned base = 0;
-                if (lane == 0) base = atomicAdd(&lcount, (unsigned)__popcll(m));
-                base = __shfl(base, 0);
+            unsigned base = 0;
+            if (lane == 0 && total) base = atomicAdd(&cntA, total);
+            base = __shfl(base, 0) - baseA;
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                if ((m[s] >> lane) & 1) listA[base + (unsigned)__popcll(m[s] & below)] = (uint16_t)(by * 8 + s);
+                base += (unsigned)__popcll(m[s]);
+            }
+        }
+        __syncthreads();
+        const unsigned nA = cntA - baseA;
+        unsigned heldB = cntB - baseB;
+        __syncthreads();   // (both counts read before anyone adds to them again)
+        const bool tight = heldB + nA > D4G_SCAN_LIST_B;   // list B may fill up on the way: look before every pass
+        unsigned at = 0;
+        for (;;) {
+            // Phase B over list A, 256 entries a pass
+            bool drain = last;
+            for (; at < nA; at += 256) {
+                if (tight) {
+                    __syncthreads();
+                    heldB = cntB - baseB;
+                    __syncthreads();
+                    if (heldB + 256 > D4G_SCAN_LIST_B) { drain = true; break; }
+                }
+                const unsigned idx = at + threadIdx.x;
+                bool ok = idx < nA;
+                unsigned q = 0;
                 if (ok) {
-                    unsigned idx = base + (unsigned)__popcll(m & ((1ULL << lane) - 1));
-                    if (idx < D4G_SCAN_LOCAL) lpos[idx] = (uint32_t)(p - tile.byteStart * 8);
-                    else {   // (a tile with more plausible headers than the local list holds: straight to the global list)
-                        unsigned g = atomicAdd(nCands, 1u);
-                        if (g < capCands) { D4GProbeIn c; c.stream = tile.stream; c.strict = 1; c.bitPos = p; cands[g] = c; }
+                    q = listA[idx];
+                    // 96 bits starting at the position's byte: four aligned words of the tile, shifted into place
+                    const int by = (int)(q >> 3), s = (int)(q & 7);
+                    const uint32_t* bw = (const uint32_t*)buf + (by >> 2);
+                    const int bsh = (by & 3) * 8;
+                    const uint32_t w0 = bw[0], w1 = bw[1], w2 = bw[2], w3 = bw[3];
+                    const uint64_t lo = (uint64_t)d4g_alignbit(w1, w0, bsh) | ((uint64_t)d4g_alignbit(w2, w1, bsh) << 32);
+                    const uint32_t hi = d4g_alignbit(w3, w2, bsh);
+                    const uint64_t v = s ? ((lo >> s) | ((uint64_t)hi << (64 - s))) : lo;   // window bits 0..63
+                    const uint64_t w = (v >> 32) | ((uint64_t)(hi >> s) << 32);             // window bits 32..95
+                    const int ncl = (int)((v >> 13) & 15) + 4;
+                    ok = (int)q + 17 + 3 * ncl <= nbits;
+                    if (ok) {
+                        // the code-length code must be complete: sum 2^(7-l) == 128, at least two codes.  Branch-free over the
+                        // 3-bit fields: bit planes of the (masked) 57-bit field, one popcount per length value
+                        uint64_t f = (v >> 17) | ((w >> 32) << 47);           // window bits 17..80
+                        f &= (1ULL << (3 * ncl)) - 1;
+                        const uint64_t M = 0x1249249249249249ULL;              // bit 0 of every 3-bit field
+                        const uint64_t p0 = f & M, p1 = (f >> 1) & M, p2 = (f >> 2) & M;
+                        const uint64_t n0 = ~p0, n1 = ~p1, n2 = ~p2;
+                        const int kraft = 64 * __popcll(p0 & n1 & n2) + 32 * __popcll(n0 & p1 & n2) + 16 * __popcll(p0 & p1 & n2) +
+                                          8 * __popcll(n0 & n1 & p2) + 4 * __popcll(p0 & n1 & p2) + 2 * __popcll(n0 & p1 & p2) + __popcll(p0 & p1 & p2);
+                        const int used = __popcll(p0 | p1 | p2);
+                        ok = kraft == 128 && used >= 2;
+                    }
+                }
+                // (a ballot and one LDS atomic per wave: an atomic per lane on one counter was most of an earlier scan's time)
+                const unsigned long long m = __ballot(ok);
+                if (m) {
+                    unsigned base = 0;
+                    if (lane == 0) base = atomicAdd(&cntB, (unsigned)__popcll(m));
+                    base = __shfl(base, 0) - baseB;
+                    if (ok) listB[base + (unsigned)__popcll(m & below)] = (uint16_t)q;
+                }
+            }
+            if (!drain) break;
+            // Phase C over list B (every thread comes here behind a barrier that follows list B's last entry).  Survivors are
+            // rare: they go straight to the global list, one atomic per 64 candidates that hold any.
+            const unsigned nB = cntB - baseB;
+            if (wave == waveC) {
+                const D4GStagedBits src = {(const uint32_t*)buf};
+                for (unsigned atB = 0; atB < nB; atB += 64) {
+                    bool ok = atB + lane < nB;
+                    const int q = ok ? listB[atB + lane] : 0;
+                    if (ok) ok = d4g_header_survives(src, q, nbits, lut + lane, clens + lane, 64);
+                    const unsigned long long m = __ballot(ok);
+                    if (m) {
+                        unsigned g = 0;
+                        if (lane == 0) g = atomicAdd(&counters[0], (unsigned)__popcll(m));
+                        g = __shfl(g, 0) + (unsigned)__popcll(m & below);
+                        if (ok && g < capKept) { D4GProbeIn c; c.stream = stream; c.strict = 1; c.bitPos = tileBit0 + q; kept[g] = c; }
                     }
                 }
             }
+            baseB += nB;
+            __syncthreads();
+            if (at >= nA) break;
         }
+        baseA += nA;
+        __syncthreads();   // list A is free again, list B complete so far
+        if (last) break;
     }
-    __syncthreads();
-    const unsigned nl = lcount < D4G_SCAN_LOCAL ? lcount : D4G_SCAN_LOCAL;
-    if (threadIdx.x == 0) gbase = nl ? atomicAdd(nCands, nl) : 0u;
-    __syncthreads();
-    for (unsigned i = threadIdx.x; i < nl; i += blockDim.x) {
-        unsigned g = gbase + i;
-        if (g < capCands) { D4GProbeIn c; c.stream = tile.stream; c.strict = 1; c.bitPos = tile.byteStart * 8 + lpos[i]; cands[g] = c; }
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// 1b. Header pre-filter.  The scan's candidates are almost all false positives (a plausible prolog and a
-// complete code-length code at a random bit position); the probe would spend a whole wave and ~300 serial symbol
-// decodes on each.  Here one LANE per candidate walks the coded code lengths straight from global memory with a
-// private 128-entry decode table, keeping only the Kraft sums: a candidate survives when its literal/length code is
-// complete with an end-of-block code and its distance code is complete or has at most one code — the conditions
-// the strict probe applies (d4g_parse_block), so nothing the probe would accept is dropped.  Survivors are
-// compacted for the probe.
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_prefilter_headers(const D4GStreamDesc* streams, const D4GProbeIn* in, unsigned n, D4GProbeIn* kept,
-                                                          unsigned* nKept) {
-    __shared__ uint8_t lut[64 * 128];   // per lane: 7-bit window -> sym | len << 5
-    const int lane = threadIdx.x & 63;
-    const unsigned idx = blockIdx.x * 64 + lane;
-    bool ok = idx < n;
-    D4GProbeIn pi;
-    pi.stream = 0; pi.strict = 1; pi.bitPos = 0;
-    if (ok) pi = in[idx];
-    const D4GStreamDesc sd = streams[pi.stream];
-    const long long nbits = sd.len * 8;
-    long long pos = pi.bitPos;
-    const uint32_t* words = (const uint32_t*)sd.data;   // 16-byte aligned, readable past len
-    auto peek = [&](long long p) -> uint64_t {          // 57+ valid bits at bit p
-        long long w = p >> 5;
-        int sh = (int)(p & 31);
-        uint64_t lo = words[w] | ((uint64_t)words[w + 1] << 32);
-        uint64_t hi = words[w + 2];
-        return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-    };
-    __shared__ uint8_t clens[64 * 20];
-    uint8_t* T = lut + lane * 128;
-    uint8_t* CLN = clens + lane * 20;
-    int nLit = 0, nDist = 0;
-    if (ok) {
-        uint64_t b = peek(pos);
-        nLit = (int)((b >> 3) & 31) + 257;
-        nDist = (int)((b >> 8) & 31) + 1;
-        int nCl = (int)((b >> 13) & 15) + 4;
-        ok = ((b >> 1) & 3) == 2 && nLit <= 286 && nDist <= 30 && pos + 17 + 3 * nCl <= nbits;
-        if (ok) {
-            pos += 17;
-            // 19 x 3 bits = 57 bits: one window.  Counts and next codes per length live in 8-bit fields of a word
-            // (no dynamically indexed register arrays); the lengths themselves in the lane's LDS row.
-            uint64_t c = peek(pos);
-            uint64_t cnt64 = 0;
-            for (int k = 0; k < 19; k++) CLN[k] = 0;
-            for (int i = 0; i < nCl; i++) {
-                int l = (int)((c >> (3 * i)) & 7);
-                CLN[D4G_CL_ORDER[i]] = (uint8_t)l;
-                if (l) cnt64 += 1ULL << (8 * l);
-            }
-            pos += 3 * nCl;
-            // canonical codes (Huffman.buildCodes), LUT over 7 bits (LSB-first windows: codes are bit-reversed)
-            uint64_t next64 = 0;
-            int code = 0;
-            for (int l = 1; l <= 7; l++) {
-                code = (code + (l > 1 ? (int)((cnt64 >> (8 * (l - 1))) & 255) : 0)) << 1;
-                next64 |= (uint64_t)(code & 255) << (8 * l);
-            }
-            for (int e = 0; e < 128; e++) T[e] = 0xff;
-            for (int k = 0; k < 19; k++) {
-                int l = CLN[k];
-                if (l) {
-                    int cd = (int)((next64 >> (8 * l)) & 255);
-                    next64 += 1ULL << (8 * l);
-                    unsigned r = 0;
-                    for (int bI = 0; bI < l; bI++) r |= ((cd >> bI) & 1u) << (l - 1 - bI);
-                    for (unsigned e = r; e < 128; e += (1u << l)) T[e] = (uint8_t)(k | (l << 5));
-                }
-            }
-        }
-    }
-    if (ok) {
-        const int combined = nLit + nDist;
-        long long kraftLit = 0, kraftDist = 0;
-        int i = 0, prev = 0, nDistCodes = 0, eob = 0;
-        while (i < combined) {
-            if (pos + 14 > nbits + 64) { ok = false; break; }
-            uint64_t b = peek(pos);
-            unsigned e = T[b & 127];
-            if (e == 0xff) { ok = false; break; }
-            int sym = e & 31, l = e >> 5;
-            pos += l;
-            b >>= l;
-            int run = 1, value = sym;
-            if (sym == 16) {
-                if (i < 1) { ok = false; break; }
-                run = (int)(b & 3) + 3; pos += 2; value = prev;
-            } else if (sym == 17) {
-                run = (int)(b & 7) + 3; pos += 3; value = 0;
-            } else if (sym == 18) {
-                run = (int)(b & 127) + 11; pos += 7; value = 0;
-            }
-            if (pos > nbits || i + run > combined) { ok = false; break; }
-            if (value) {
-                // the run may span the literal/distance boundary
-                int inLit = i < nLit ? (i + run <= nLit ? run : nLit - i) : 0;
-                kraftLit += (long long)inLit << (15 - value);
-                kraftDist += (long long)(run - inLit) << (15 - value);
-                nDistCodes += run - inLit;
-                if (i <= 256 && i + run > 256) eob = 1;
-            }
-            prev = value;
-            i += run;
-        }
-        ok = ok && kraftLit == (1 << 15) && eob && (kraftDist == (1 << 15) || nDistCodes <= 1);
-    }
-    unsigned long long m = __ballot(ok);
-    if (m) {
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(nKept, (unsigned)__popcll(m));
-        base = __shfl(base, 0);
-        if (ok) kept[base + (unsigned)__popcll(m & ((1ULL << lane) - 1))] = pi;
-    }
+    if (threadIdx.x == 0 && cntB) atomicAdd(&counters[1], cntB);
 }
 
 // ---------------------------------------------------------------------------------------

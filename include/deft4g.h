@@ -92,6 +92,9 @@ typedef struct d4g_stats {
      * after the per-launch round limit or after an improving level-executor round; cluster_fallbacks = rounds the cluster
      * kernel could not hold and handed to the level / persistent executors */
     int64_t fused_fallbacks_mid, fused_relaunches, cluster_fallbacks;
+    /* header scan: scan_candidates = bit positions with a plausible prolog and a complete code-length code; scan_kept = those
+     * whose coded code lengths also give complete codes, which is what the probe is run on */
+    int64_t scan_kept;
 } d4g_stats;
 
 /* Select the HIP device (one process per GPU) and create the library's stream.
