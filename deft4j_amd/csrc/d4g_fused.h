@@ -204,7 +204,7 @@ union D4FScratch {
     D4FTreeScr tree[D4F_TREE_SLOTS];
     D4FWaveScr wave[8];
     D4FSweepScr sweep;
-    D4GLds legacy;           // assembling the winner (the level executor's header functions)
+    D4GLds levelLds;         // assembling the winner (the level executor's header functions)
 };
 static_assert(sizeof(D4FHdrScr) <= sizeof(D4FWaveScr), "header scratch overlays the wave scratch");
 
@@ -2247,7 +2247,7 @@ D4F_TASK bool d4f_select(long long best, D4GRoundResult* out) {
             if (F.fallback) return false;
         }
         __syncthreads();
-        D4GLds& L = F.scr.legacy;
+        D4GLds& L = F.scr.levelLds;
         D4GState* S = &L.st;
         d4f_assemble(G, S, mid, ws.c, ws.h, ws.type, ws.litlen);
         if (op.kind == OP_HDRSEARCH) {

@@ -147,17 +147,14 @@ struct Batch {
     RtBuf<D4FClArena> dClArena;                  // the cluster kernel's command slots
     std::vector<D4GMergeJob> pendingCommits;     // merged blocks to move out of their arenas (commit_block)
     std::map<int32_t, D4GBlock> blockPatches;    // descriptor changes, applied by one upload + one scatter kernel
-    // ---- level / persistent executors only: made on their first use (ensure_legacy_tables) — a batch the fused executor
-    // handles alone never allocates or clears them ----
+    // ---- level executor only: made on its first use (ensure_level_tables) — a batch the fused executor handles alone
+    // never allocates or clears them ----
     RtBuf<long long> dKeys;
-    RtBuf<int32_t> dReady;           // per (block, slot): epoch of the round that produced it (persistent executor)
-    RtBuf<unsigned> dHeads;
     RtBuf<D4GHsMemo> dHsMemo;        // per block: header-search memo
     RtBuf<D4GRecodeMemo> dRcMemo;    // per block: Huffman-rebuild memo
     RtBuf<uint64_t> dPassMemo;       // per block: token-pass memo entries
-    int epoch = 0;
-    size_t legacyBlocks = 0;
-    long long legacyPassMemoWords = 0;
+    size_t levelBlocks = 0;
+    long long levelPassMemoWords = 0;
 
     ~Batch() {
         try { rt_sync_all(); } catch (...) {}   // nothing may still be running on a block that goes back to the pool (the members follow)
@@ -183,17 +180,15 @@ struct Batch {
     void launch_jump_tiles(const D4GStreamDesc* dStreamsD, const CopyRoute& R, int tileReps, RtScratch& tmp);
     void block_bins(const std::vector<int32_t>& realBlocks, bool needSlots, RtScratch& tmp);
     // d4g_host_search.h
-    void ensure_legacy_tables();
+    void ensure_level_tables();
     D4FParams fused_params(int maxRounds, D4GRoundResult* results, int32_t* info);
     void count_state_launch(const int32_t* blk, size_t n);
     std::vector<D4GRoundResult> run_round(const std::vector<int>& act);
     bool run_cluster(int blk, D4GRoundResult* out);
     std::vector<std::vector<D4GRoundResult>> run_fused(const std::vector<int>& act, int maxRounds);
     typedef std::vector<std::unique_ptr<RtEvent>> Events;
-    std::vector<D4GRoundResult> run_round_legacy(const std::vector<int>& act);
-    bool run_legacy_pass(const Program& P, std::vector<int32_t> sub, std::vector<size_t> subPos, bool persist, int pass, std::vector<D4GRoundResult>& res);
-    void launch_persistent(const Program& P, const std::vector<int32_t>& sub, const int* xoff, Events& evs);
-    void launch_levels(const Program& P, const std::vector<int32_t>& sub, RtEvent& uploaded, Events& evs, Events& keep);
+    std::vector<D4GRoundResult> run_round_levels(const std::vector<int>& act);
+    void run_levels_pass(const Program& P, const std::vector<int32_t>& sub, const std::vector<size_t>& subPos, int pass, std::vector<D4GRoundResult>& res);
     static bool stored_wins(const D4GRoundResult& r, i64 uLen, i64 pos, i64* storedSize);
     void phase1();
     // d4g_host_merge.h
@@ -228,7 +223,6 @@ inline D4GCtx Batch::make_ctx(const Program& P, int nActive) {
     c.keys = dKeys; c.ops = P.dOps; c.hdrFlags = E.dHdrTables; c.hdrPrune = E.dHdrTables + 64;
     c.active = dActive; c.errors = errors(); c.opStats = E.dOpStats; c.nActive = nActive; c.nOps = (int)P.ops.size();
     c.slotsPerBlock = slotsAlloc; c.masksPerBlock = E.masksPerBlock;
-    c.tileGroups = nActive > 0 ? (nActive + 7) / 8 : 1;
     return c;
 }
 inline void Batch::check_device_errors() {

@@ -464,9 +464,9 @@ inline void Batch::alloc_block_tables(const Layout& LY, bool needSlots) {
     rt_h2d(dBlocks, hBlocks.data(), nb * sizeof(D4GBlock));
     dStates.alloc(nb * (size_t)slotsAlloc);
     dMasks.alloc((size_t)LY.maskWords, 64);
-    legacyBlocks = needSlots ? nb : 0;
-    legacyPassMemoWords = LY.passMemoWords;
-    if (needSlots && !exec_fused()) ensure_legacy_tables();   // (the fused executor's batches make them when a block first falls back)
+    levelBlocks = needSlots ? nb : 0;
+    levelPassMemoWords = LY.passMemoWords;
+    if (needSlots && !exec_fused()) ensure_level_tables();   // (the fused executor's batches make them when a block first falls back)
     dActive.alloc(nb);
     dResults.alloc(nb);
     // mask 0 of every block starts empty (no back-reference expanded); the writer reads it even when no search runs
@@ -485,6 +485,7 @@ inline void Batch::build_blocks(bool merge, bool needSlots) {
     if (maxU >= (1LL << 31)) throw std::runtime_error("a stream decodes to 2 GiB or more");   // (k_fill_src's positions would reach D4G_SRC_FINAL)
     Layout LY;
     layout_blocks(merge, needSlots, LY);
+    (void)exec_fused();   // an unknown D4G_EXEC is refused here, where copy_mode() refuses an unknown D4G_COPY: nothing is in flight yet
     const CopyRoute R = route_streams(LY.ranges, copy_mode());
     if (!R.ranges.empty()) dSrc.alloc((size_t)uTotal, 64);
     RtEvent e0, e1;

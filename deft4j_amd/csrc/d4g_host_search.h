@@ -3,17 +3,15 @@
 
 namespace d4g {
 
-// What only the level / persistent executors use (candidate keys, slot epochs, queue heads, the three memo tables): made
-// on their first use — a batch the fused executor handles alone never allocates or clears them.
-inline void Batch::ensure_legacy_tables() {
-    if (dKeys || !legacyBlocks) return;
+// What only the level executor uses (candidate keys, the three memo tables): made on its first use — a batch the fused
+// executor handles alone never allocates or clears them.
+inline void Batch::ensure_level_tables() {
+    if (dKeys || !levelBlocks) return;
     Engine& E = engine();
-    const size_t nb = legacyBlocks;
+    const size_t nb = levelBlocks;
     dKeys.alloc(nb * (size_t)E.maxOps);
-    dReady.alloc_zero(nb * (size_t)slotsAlloc);
-    dHeads.alloc(16);
     dHsMemo.alloc_zero(nb * (size_t)D4G_HSMEMO_SLOTS);
-    dPassMemo.alloc_zero((size_t)legacyPassMemoWords, 64);
+    dPassMemo.alloc_zero((size_t)levelPassMemoWords, 64);
     dRcMemo.alloc_zero(nb * (size_t)D4G_RCMEMO_SLOTS);
 }
 
@@ -38,10 +36,10 @@ inline void Batch::count_state_launch(const int32_t* blk, size_t n) {
     for (size_t i = 0; i < n; i++) { stats.state_tokens_per_round += hBlocks[blk[i]].tokCount; stats.state_bytes_per_round += hBlocks[blk[i]].uLen; }
 }
 
-// One optimiseBlock call per block of `act`: the fused executor takes the blocks it can hold, the level / persistent
-// executors the rest.
+// One optimiseBlock call per block of `act`: the fused and cluster executors take the blocks they can hold, the level
+// executor the rest.
 inline std::vector<D4GRoundResult> Batch::run_round(const std::vector<int>& act) {
-    if (!exec_fused()) return run_round_legacy(act);
+    if (!exec_fused()) return run_round_levels(act);
     std::vector<D4GRoundResult> res(act.size());
     std::vector<int> small, big;
     std::vector<size_t> smallPos, bigPos;
@@ -70,7 +68,7 @@ inline std::vector<D4GRoundResult> Batch::run_round(const std::vector<int>& act)
         bigPos.swap(restPos);
     }
     if (!big.empty()) {
-        std::vector<D4GRoundResult> r = run_round_legacy(big);
+        std::vector<D4GRoundResult> r = run_round_levels(big);
         for (size_t i = 0; i < big.size(); i++) res[bigPos[i]] = r[i];
     } else {
         stats.rounds++;
@@ -126,7 +124,7 @@ inline std::vector<std::vector<D4GRoundResult>> Batch::run_fused(const std::vect
     std::vector<std::vector<D4GRoundResult>> chains(act.size());
     std::vector<int> todo(act.size());
     for (size_t i = 0; i < act.size(); i++) todo[i] = (int)i;
-    RtScratch tmp;   // (run_round_legacy below waits before it returns or throws its own errors)
+    RtScratch tmp;   // (run_round_levels below waits before it returns or throws its own errors)
     D4GRoundResult* dRes = nullptr;
     int32_t* dInfo = nullptr;
     while (!todo.empty()) {
@@ -170,7 +168,7 @@ inline std::vector<std::vector<D4GRoundResult>> Batch::run_fused(const std::vect
         if (!fb.empty()) {   // one round with the level executor, then back here if it improved
             std::vector<int> fbAct(fb.size());
             for (size_t i = 0; i < fb.size(); i++) fbAct[i] = act[fb[i]];
-            std::vector<D4GRoundResult> rr = run_round_legacy(fbAct);
+            std::vector<D4GRoundResult> rr = run_round_levels(fbAct);
             stats.fused_fallbacks += (int64_t)fb.size();
             for (size_t i = 0; i < fb.size(); i++) {
                 chains[fb[i]].push_back(rr[i]);
@@ -184,48 +182,18 @@ inline std::vector<std::vector<D4GRoundResult>> Batch::run_fused(const std::vect
     tmp.release();
     return chains;
 }
-// Persistent executor: dependency-driven work queues over the blocks of `sub` (grouped by XCD, xoff[x] = start of queue x),
-// state ops on the lane's first stream and header searches on its second, then the selection.
-inline void Batch::launch_persistent(const Program& P, const std::vector<int32_t>& sub, const int* xoff, Events& evs) {
+// One pass (one program) of a level-executor round over `sub`, whose results go to res[subPos[k]]: one launch per program
+// level, then the selection.  The active blocks are split into groups, one stream lane each: the launch tail of one group's
+// level (a few long recode/tree ops) overlaps the other groups' levels.
+inline void Batch::run_levels_pass(const Program& P, const std::vector<int32_t>& sub, const std::vector<size_t>& subPos, int pass, std::vector<D4GRoundResult>& res) {
+    rt().cur = 0;
     const int nA = (int)sub.size();
-    D4GCtx c = make_ctx(P, nA);
-    epoch++;
-    rt_memset(dHeads, 0, 64);
-    const long long spinLimit = spin_limit();
-    D4GQueue qs = {P.dStateFlat, P.nStateFlat, dHeads, dReady, epoch, {0}, spinLimit};
-    D4GQueue qh = {P.dHdrFlat, P.nHdrFlat, dHeads + 8, dReady, epoch, {0}, spinLimit};
-    for (int x = 0; x < 9; x++) { qs.xoff[x] = xoff[x]; qh.xoff[x] = xoff[x]; }
-    RtEvent ready;
-    ready.record();
-    rt_stream2_wait(ready);
-    static const int cus = device_cus();
-    const int sPerCu = state_wgs_per_cu(), hPerCu = hs_wgs_per_cu();
-    i64 ns = (i64)P.nStateFlat * nA, nh = (i64)P.nHdrFlat * nA;
-    i64 gs = std::min<i64>(ns, (i64)cus * sPerCu), gh = std::min<i64>(nh, (i64)cus * hPerCu);
-    evs.emplace_back(new RtEvent());
-    evs.back()->record();
-    RT_LAUNCH(k_persist_state_ops, gs, state_block(), c, qs);
-    evs.emplace_back(new RtEvent());
-    evs.back()->record();
-    stats.kernel_launches++;
-    count_state_launch(sub.data(), sub.size());
-    if (gh > 0) {
-        RT_LAUNCH2(k_persist_hdr_search, gh, 64, c, qh);
-        stats.kernel_launches++;
-    }
-    RtEvent hsDone;
-    hsDone.record2();
-    rt_stream_wait(hsDone);
-    RT_LAUNCH(k_select, nA, state_block(), c, dResults);
-    stats.kernel_launches++;
-    stats.search_lanes = std::max<int64_t>(stats.search_lanes, 1);
-}
-// Level executor: one launch per program level.  The active blocks are split into groups, one stream lane each: the launch
-// tail of one group's level (a few long recode/tree ops) overlaps the other groups' levels.
-inline void Batch::launch_levels(const Program& P, const std::vector<int32_t>& sub, RtEvent& uploaded, Events& evs, Events& keep) {
-    const int nA = (int)sub.size();
-    int G = std::min(lanes(), std::max(1, nA / 16));
-    Events laneDone;
+    rt_h2d(dActive, sub.data(), sub.size() * sizeof(int32_t));
+    RtEvent e0, e1, uploaded;
+    uploaded.record();
+    Events evs, keep, laneDone;
+    e0.record();
+    const int G = std::min(lanes(), std::max(1, nA / 16));
     for (int g = 0; g < G; g++) {
         int lo = (int)((i64)nA * g / G), hi = (int)((i64)nA * (g + 1) / G);
         if (hi <= lo) continue;
@@ -233,10 +201,7 @@ inline void Batch::launch_levels(const Program& P, const std::vector<int32_t>& s
         D4GCtx c = make_ctx(P, hi - lo);
         c.active = dActive + lo;
         rt_stream_wait(uploaded);
-        i64 groups = (hi - lo + 7) / 8;
-        const int tg = tile_groups();   // launch tiles (d4g_map_wg): the whole group by default
-        c.tileGroups = tg > 0 && tg < groups ? tg : (int)groups;
-        groups = (groups + c.tileGroups - 1) / c.tileGroups * c.tileGroups;
+        const i64 groups = (hi - lo + 7) / 8;   // d4g_map_wg
         // Level l's header searches read bases produced at level l-1, so they run on the lane's second
         // stream beside level l's state ops (the searches are LDS-bound at low occupancy).
         RtEvent* lvlPrev = nullptr;
@@ -258,11 +223,6 @@ inline void Batch::launch_levels(const Program& P, const std::vector<int32_t>& s
                 stats.kernel_launches++;
                 count_state_launch(sub.data() + lo, (size_t)(hi - lo));
             }
-            if (P.wideOff[l].second) {
-                i64 grid = 8 * groups * P.wideOff[l].second;
-                RT_LAUNCH(k_exec_state_ops_wide, grid, wide_block(), c, P.dLists + P.wideOff[l].first, P.wideOff[l].second);
-                stats.kernel_launches++;
-            }
             keep.emplace_back(new RtEvent());
             keep.back()->record();
             lvlPrev = keep.back().get();
@@ -278,58 +238,24 @@ inline void Batch::launch_levels(const Program& P, const std::vector<int32_t>& s
     }
     rt().cur = 0;
     for (auto& ev : laneDone) rt_stream_wait(*ev);
-}
-// One pass (one program) of a round over `sub`, whose results go to res[subPos[k]].  false: a wait inside the persistent
-// kernels gave up (see wg_wait_slot): nothing was selected, the blocks are untouched, the error counter is reset.
-inline bool Batch::run_legacy_pass(const Program& P, std::vector<int32_t> sub, std::vector<size_t> subPos, bool persist, int pass, std::vector<D4GRoundResult>& res) {
-    rt().cur = 0;
-    int xoff[9] = {0};
-    if (persist) {
-        // group the active blocks by (position mod 8): one task queue per XCD
-        std::vector<int32_t> g;
-        std::vector<size_t> gp;
-        for (int x = 0; x < 8; x++) {
-            xoff[x] = (int)g.size();
-            for (size_t i = x; i < sub.size(); i += 8) { g.push_back(sub[i]); gp.push_back(subPos[i]); }
-        }
-        xoff[8] = (int)g.size();
-        sub.swap(g);
-        subPos.swap(gp);
-    }
-    rt_h2d(dActive, sub.data(), sub.size() * sizeof(int32_t));
-    RtEvent e0, e1, uploaded;
-    uploaded.record();
-    Events evs, keep;
-    e0.record();
-    if (persist) launch_persistent(P, sub, xoff, evs);
-    else launch_levels(P, sub, uploaded, evs, keep);
     e1.record();
     std::vector<D4GRoundResult> r(sub.size());
     rt_d2h(r.data(), dResults, sub.size() * sizeof(D4GRoundResult));
     const float roundMs = rt_elapsed_ms(e0, e1);
     msSearch += roundMs;
-    if (persist && !r.empty() && r[0].improved < 0) {
-        int32_t zero[2] = {0, 0};
-        rt_h2d(errors() + 1, zero, 4);
-        rt_sync();
-        stats.persist_fallbacks++;
-        return false;
-    }
     if (debug_rounds())
-        fprintf(stderr, "search round %lld (%s program, %s): %d active blocks, %.3f ms\n", (long long)stats.rounds, pass == 0 ? "dynamic" : "fixed",
-                persist ? "persistent" : "levels", (int)sub.size(), roundMs);
+        fprintf(stderr, "search round %lld (%s program, levels): %d active blocks, %.3f ms\n", (long long)stats.rounds, pass == 0 ? "dynamic" : "fixed", nA, roundMs);
     for (size_t k = 0; k + 1 < evs.size(); k += 2) stats.ms_state_kernels += rt_elapsed_ms(*evs[k], *evs[k + 1]);
     for (size_t k = 0; k < sub.size(); k++) {
         res[subPos[k]] = r[k];
         gpuType[sub[k]] = r[k].newType;
     }
-    return true;
 }
-// One optimiseBlock call on every block of `act` with the level / persistent executors: the dynamic program over the
-// blocks that are dynamic now, then the fixed one over the fixed ones.
-inline std::vector<D4GRoundResult> Batch::run_round_legacy(const std::vector<int>& act) {
+// One optimiseBlock call on every block of `act` with the level executor: the dynamic program over the blocks that are
+// dynamic now, then the fixed one over the fixed ones.
+inline std::vector<D4GRoundResult> Batch::run_round_levels(const std::vector<int>& act) {
     Engine& E = engine();
-    ensure_legacy_tables();
+    ensure_level_tables();
     std::vector<D4GRoundResult> res(act.size());
     for (int pass = 0; pass < 2; pass++) {
         const Program& P = pass == 0 ? E.progDyn : E.progFixed;
@@ -338,9 +264,7 @@ inline std::vector<D4GRoundResult> Batch::run_round_legacy(const std::vector<int
         std::vector<size_t> subPos;
         for (size_t i = 0; i < act.size(); i++)
             if (gpuType[act[i]] == wantType) { sub.push_back(act[i]); subPos.push_back(i); }
-        if (sub.empty()) continue;
-        // the same pass again with the level executor, which has no cross-kernel waits, when the persistent one gave up
-        if (exec_persistent((int)sub.size()) == 0 || !run_legacy_pass(P, sub, subPos, true, pass, res)) run_legacy_pass(P, sub, subPos, false, pass, res);
+        if (!sub.empty()) run_levels_pass(P, sub, subPos, pass, res);
     }
     stats.rounds++;
     return res;
@@ -394,7 +318,7 @@ inline void Batch::phase1() {
     }
     // fixpoint rounds: every block follows its own chain of strictly improving Huffman states
     while (!act.empty()) {
-        std::vector<D4GRoundResult> res = run_round_legacy(act);
+        std::vector<D4GRoundResult> res = run_round_levels(act);
         std::vector<int> nact;
         std::vector<std::pair<int, int>> nowner;
         for (size_t i = 0; i < act.size(); i++) {

@@ -122,7 +122,6 @@ inline void Batch::release_scratch() {
     dHsMemo.reset(); dRcMemo.reset(); dPassMemo.reset();
     dBlocks.reset(); dStates.reset(); dMasks.reset();
     dKeys.reset(); dActive.reset(); dResults.reset();
-    dReady.reset(); dHeads.reset();
 }
 
 // ---- round-trip verification: the one routine behind d4g_batch_verify, d4g_verify_streams and D4G_VERIFY=1 ----

@@ -23,28 +23,19 @@ static inline long long knob_now_ll(const char* name, long long def) { const cha
 static inline bool knob_is_zero(const char* t) { return t && t[0] == '0'; }   // "0..." switches a default-on feature off
 
 // ---- executors ----
-// D4G_EXEC, now.  fused (default; anything unknown, "auto" included, counts as unset for the level / persistent choice),
-// levels, persistent.  "fused": one workgroup per block runs the whole search out of LDS (d4g_fused.h); the other two remain
-// for the blocks it does not take (very large merged blocks, table overflows) and as cross-checks.
-static inline bool exec_fused() { const char* t = knob_now("D4G_EXEC"); return !t || !strcmp(t, "fused"); }
-// Level or persistent executor for a round of nActive blocks: 1 = persistent (dependency-driven work queues, no launch per
-// level: wins while the round is latency-bound, nerd.png 115 -> 68 ms), 0 = levels (one launch per program level: wins once
-// the blocks fill the chip, config 2 with 332 blocks 79 vs 87 ms).  Unforced, the switch is at D4G_PERSIST_MAX_BLOCKS (now;
-// default 128) active blocks.  Emulator: persistent unless D4G_EXEC=levels.
-static inline int exec_persistent(int nActive = 0) {
+// D4G_EXEC, now.  "fused" (default, also when unset): one workgroup per block runs the whole search out of LDS (d4g_fused.h),
+// a lone long block gets the whole device (k_search_cluster), and the level executor (one launch per program level) takes what
+// those two hand back: table overflows, cluster refusals, very large merged blocks.  "levels": the level executor runs every
+// round — the cross-check.  Anything else throws (a stale environment should be loud): Batch::build_blocks asks before anything is launched.
+static inline bool exec_fused() {
     const char* t = knob_now("D4G_EXEC");
-    const int mode = !t ? 2 : !strcmp(t, "levels") ? 0 : !strcmp(t, "persistent") ? 1 : 2;
-    const int maxBlocks = knob_now("D4G_PERSIST_MAX_BLOCKS", 128);
-#ifdef D4G_HOSTSIM
-    return mode == 0 ? 0 : 1;
-#endif
-    if (mode == 2) return nActive <= maxBlocks ? 1 : 0;
-    return mode;
+    if (!t || !strcmp(t, "fused")) return true;
+    if (!strcmp(t, "levels")) return false;
+    throw std::runtime_error("D4G_EXEC must be fused or levels");
 }
-// D4G_FUSED_MAX_REFS, now.  Blocks with more back-references go to the cluster / level / persistent executors.  One workgroup
-// per block is unbeatable while there are blocks enough to fill the device, but a lone long block (100 k back-references:
-// 3.8 ms per round persistent, 7.5 ms fused) is better served by op-level parallelism.  Default 2^17 when the round has 8 or
-// more blocks of over 16384 back-references (nLong), else 2^14.
+// D4G_FUSED_MAX_REFS, now.  Blocks with more back-references go to the cluster / level executors.  One workgroup per block is
+// unbeatable while there are blocks enough to fill the device, but a lone long block is better served by op-level
+// parallelism.  Default 2^17 when the round has 8 or more blocks of over 16384 back-references (nLong), else 2^14.
 static inline long long fused_max_refs(size_t nLong) { return knob_now_ll("D4G_FUSED_MAX_REFS", nLong >= 8 ? (1LL << 17) : (1LL << 14)); }
 // D4G_CLUSTER_MIN_REFS, now (default 2^14): a lone block with more back-references gets the whole device (k_search_cluster).
 // D4G_CLUSTER, now: a value starting with 0 = never.
@@ -92,28 +83,10 @@ static inline int fused_cap_masks() { return knob_clamped("D4G_FUSED_CAP_MASKS",
 static inline int fused_cap_codes() { return knob_clamped("D4G_FUSED_CAP_CODES", 2, D4F_MAXC); }
 static inline int fused_cap_hdrs() { return knob_clamped("D4G_FUSED_CAP_HDRS", 1, D4F_MAXH); }
 static inline int fused_cap_rounds() { return knob_clamped("D4G_FUSED_CAP_ROUNDS", 1, D4F_MAXROUNDS); }
-// D4G_WIDE_BLOCK, once: threads per workgroup of a separate launch for token-pass-only ops: 256, 512, 1024, or 0 (default and
-// fallback) = same launch as the others.  Emulator: 0.  D4G_WIDE_KINDS, once: bit k = ops of kind k go to that launch.
-static inline int wide_block() {
-#ifdef D4G_HOSTSIM
-    return 0;
-#else
-    const int v = KNOB_ONCE("D4G_WIDE_BLOCK", 0);
-    return v == 256 || v == 512 || v == 1024 ? v : 0;
-#endif
-}
-static inline int wide_kinds() { return KNOB_ONCE("D4G_WIDE_KINDS", (1 << OP_OPT) | (1 << OP_LEAST)); }
 // D4G_LANES, now (bench.py's roofline leg sets 1 so that a launch's event time is not inflated by the neighbouring lane):
 // block groups of the level executor running concurrently, clamped to 1..RT_MAX_LANES.  Default 2, measured on config 2:
 // 1 -> 587, 2 -> 627, 4 -> 494, 8 -> 349 MB/s.
 static inline int lanes() { return std::min(std::max(knob_now("D4G_LANES", 2), 1), RT_MAX_LANES); }
-// D4G_TILE_GROUPS, once: launch tile of the level executor in groups of 8 blocks (d4g_map_wg); 0 (default) = the whole group.
-static inline int tile_groups() { return KNOB_ONCE("D4G_TILE_GROUPS", 0); }
-// Persistent executor.  D4G_STATE_WGS_PER_CU (8) and D4G_HS_WGS_PER_CU (4), once: resident workgroups per CU of its two
-// kernels.  D4G_SPIN_LIMIT, now (default 2^21): polls after which a wait gives up and the round goes to the level executor.
-static inline int state_wgs_per_cu() { return KNOB_ONCE("D4G_STATE_WGS_PER_CU", 8); }
-static inline int hs_wgs_per_cu() { return KNOB_ONCE("D4G_HS_WGS_PER_CU", 4); }
-static inline long long spin_limit() { return knob_now_ll("D4G_SPIN_LIMIT", 1LL << 21); }
 // D4G_MEMO, now: a value starting with 0 = every op computes (the run-time memos are an optimisation only).
 static inline bool memo_enabled() { return !knob_is_zero(knob_now("D4G_MEMO")); }
 

@@ -84,7 +84,6 @@ struct D4GCtx {
     int32_t nOps;
     int32_t slotsPerBlock;
     int32_t masksPerBlock;
-    int32_t tileGroups;       // blocks per launch tile / 8 (d4g_map_wg)
 };
 
 // LDS working set of one state-op workgroup
@@ -1168,45 +1167,7 @@ __device__ __forceinline__ void wg_recode_to_fixed(D4GLds* L) {
     wg_litlen_bits_from_hist(L);
 }
 
-// ---------------------------------------------------------------------------------------
-// Dependency-driven execution.  Instead of one launch per program level, persistent workgroups pull
-// (block, op) tasks from a queue ordered by level; an op waits for its source slot's ready flag and
-// publishes its own.  Tasks are pulled in queue order, so a task's producer was always pulled earlier
-// by a workgroup that is resident and running: waiting never deadlocks, whatever subset of the grid
-// is resident.  Hand-off protocol (MI355X_MICROARCH.md, inter-workgroup visibility): producer stores ->
-// every wave s_waitcnt vmcnt(0) -> workgroup barrier -> lane 0 agent-scope release -> relaxed agent
-// flag store; consumer lane 0 relaxed agent poll -> agent-scope acquire -> barrier -> plain loads.
-// ---------------------------------------------------------------------------------------
-struct D4GQueue {
-    const int32_t* opFlat;   // op ids in level order
-    int32_t nOpsFlat;
-    unsigned* head;          // [8] next task index of each XCD's queue
-    int32_t* ready;          // [numBlocks * slotsPerBlock]: epoch in which the slot was last produced
-    int32_t epoch;
-    int32_t xoff[9];         // the active list is grouped by XCD: group x = active[xoff[x], xoff[x+1])
-    long long spinLimit;     // polls before a wait gives up (D4G_SPIN_LIMIT; < 0: every wait gives up at once — tests)
-};
-
-// Pull the next task: first from the queue of this workgroup's XCD (workgroup ids equal mod 8 share an XCD
-// and its L2, so a deflate block's tokens and decoded bytes stay in one L2), then steal from the others.
-// Returns false when every queue is empty.  Thread 0 only.
-D4G_DEV bool d4g_pull_task(const D4GQueue& q, int& cursor, int& opIdx, int& actIdx) {
-    for (; cursor < 8; cursor++) {
-        int x = (int)((blockIdx.x + cursor) & 7);
-        int nA = q.xoff[x + 1] - q.xoff[x];
-        long long nTasks = (long long)q.nOpsFlat * nA;
-        if (nTasks == 0) continue;
-        long long t = atomicAdd(q.head + x, 1u);
-        if (t < nTasks) {
-            opIdx = (int)(t / nA);
-            actIdx = q.xoff[x] + (int)(t % nA);
-            return true;
-        }
-    }
-    return false;
-}
-
-
+// a state between global memory and LDS, and a mask from slot to slot: all threads call
 D4G_DEV void wg_load_state(D4GState* S, const D4GState* g) {
     __syncthreads();
     for (int i = threadIdx.x; i < (int)(sizeof(D4GState) / 4); i += blockDim.x) ((uint32_t*)S)[i] = d4g_ld_agent((const uint32_t*)g + i);
@@ -1220,35 +1181,6 @@ D4G_DEV void wg_store_state(D4GState* g, const D4GState* S) {
 D4G_DEV void wg_copy_mask(uint64_t* dst, const uint64_t* src, long long words) {
     for (long long i = threadIdx.x; i < words; i += blockDim.x) d4g_st_agent(dst + i, d4g_ld_agent(src + i));
     __syncthreads();
-}
-
-// All threads call.  Returns false if the slot never became ready: the producer runs in another workgroup (for header
-// searches: another kernel), and HIP promises no co-residency — under a profiler that serialises kernels, or with the
-// device full of someone else's long kernel, a wait can outlast any bound.  That is not an error: it is counted in
-// c.errors[1], k_select then leaves the block untouched and the host runs the round with the level executor.
-__device__ bool wg_wait_slot(const D4GCtx& c, const D4GQueue& q, int blk, int slot, int* lds) {
-    if (slot == 0) return true;  // the block's current state was written by an earlier kernel
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int32_t* f = q.ready + (long long)blk * c.slotsPerBlock + slot;
-        int ok = 0;
-        // bounded: ~1 s in total by default, and every waiter gives up as soon as any other has
-        for (long long spin = 0; spin < q.spinLimit; spin++) {
-            if (d4g_ld_agent(f) == q.epoch) { ok = 1; break; }
-            if ((spin & 63) == 63 && d4g_ld_agent(c.errors + 1) != 0) break;
-            d4g_sleep();
-        }
-        if (!ok && q.spinLimit >= 0 && d4g_ld_agent(f) == q.epoch) ok = 1;
-        if (!ok) atomicAdd(c.errors + 1, 1);
-        *lds = ok;
-    }
-    __syncthreads();
-    return *lds != 0;
-}
-__device__ void wg_publish_slot(const D4GCtx& c, const D4GQueue& q, int blk, int slot) {
-    d4g_drain_stores();
-    __syncthreads();
-    if (threadIdx.x == 0) d4g_st_agent(q.ready + (long long)blk * c.slotsPerBlock + slot, q.epoch);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1380,19 +1312,14 @@ __device__ __forceinline__ void d4g_exec_state_op(D4GLds* L, const D4GCtx& c, in
 // XCD-aware (block, op) mapping: workgroups g and g+8 share an XCD (and its L2), so all ops
 // of one deflate block are given workgroup ids that are equal mod 8 — they re-read the same
 // tokens and decoded bytes.  Speed only; nothing depends on placement.
-// Blocks are taken in tiles of 8 x tileGroups (D4G_TILE_GROUPS, default: the whole launch is one tile); inside a tile
-// the order is op-major: the level's ops are sorted longest first, so every block's long ops start before anyone's
-// short ones and the short ones fill the tail.  Smaller tiles keep a block's ops closer in time (less L2 re-fetch,
-// measured 152 -> 53 MB per launch with 64-block tiles) but cost ~7 % in time: HBM is nowhere near the limit here.
-D4G_DEV bool d4g_map_wg(int nActive, int nOpsLevel, int tileGroups, int& blkSlot, int& opRel) {
+// The order is op-major: the level's ops are sorted longest first, so every block's long ops start before anyone's
+// short ones and the short ones fill the tail.
+D4G_DEV bool d4g_map_wg(int nActive, int nOpsLevel, int& blkSlot, int& opRel) {
     int g = blockIdx.x;
     int x = g & 7, j = g >> 3;
-    int perTile = tileGroups * nOpsLevel;
-    int tile = j / perTile;
-    int rem = j - tile * perTile;
-    opRel = rem / tileGroups;
-    int local = tile * tileGroups + (rem - opRel * tileGroups);
-    blkSlot = local * 8 + x;
+    int groups = (nActive + 7) >> 3;
+    opRel = j / groups;
+    blkSlot = (j - opRel * groups) * 8 + x;
     return blkSlot < nActive && opRel < nOpsLevel;
 }
 
@@ -1403,51 +1330,8 @@ __global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_STATE_WAVES) k_exe
     D4G_SETPRIO(D4G_BASE_PRIO);
     __shared__ D4GLds L;
     int bs, orel;
-    if (!d4g_map_wg(c.nActive, nOpsLevel, c.tileGroups, bs, orel)) return;
+    if (!d4g_map_wg(c.nActive, nOpsLevel, bs, orel)) return;
     d4g_exec_state_op(&L, c, c.active[bs], opList[orel]);
-}
-
-// Same body for the token-pass-only ops (optimise / least-expensive pruning): they have no single-lane
-// section, so they run with wide workgroups (up to 16 waves sweep the block's tokens together).
-__global__ void __launch_bounds__(1024) k_exec_state_ops_wide(D4GCtx c, const int32_t* opList, int nOpsLevel) {
-    D4G_SETPRIO(D4G_BASE_PRIO);
-    __shared__ D4GLds L;
-    int bs, orel;
-    if (!d4g_map_wg(c.nActive, nOpsLevel, c.tileGroups, bs, orel)) return;
-    d4g_exec_state_op(&L, c, c.active[bs], opList[orel]);
-}
-
-// The persistent executor serves small launches (merge rounds, few-block batches) where a workgroup's own latency is
-// what is waited for, not the occupancy: a 128-VGPR budget removes its spills (merge phase of an 8 MiB stream -9 %).
-#ifndef D4G_PERSIST_WAVES
-#define D4G_PERSIST_WAVES 4
-#endif
-__global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_PERSIST_WAVES) k_persist_state_ops(D4GCtx c, D4GQueue q) {
-    D4G_SETPRIO(D4G_BASE_PRIO);
-    __shared__ D4GLds L;
-    __shared__ int sTask[3], sOk;
-    int cursor = 0;
-    while (true) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int oi = 0, ai = 0;
-            sTask[0] = d4g_pull_task(q, cursor, oi, ai) ? 1 : 0;
-            sTask[1] = oi;
-            sTask[2] = ai;
-        }
-        __syncthreads();
-        if (!sTask[0]) break;
-        int opId = q.opFlat[sTask[1]];
-        int blk = c.active[sTask[2]];
-        const D4GOp op = c.ops[opId];
-        bool ok = wg_wait_slot(c, q, blk, op.src, &sOk);
-        if (ok) d4g_exec_state_op(&L, c, blk, opId);
-        else if (threadIdx.x == 0) {
-            c.keys[(long long)blk * c.nOps + opId] = D4G_KEY_NONE;
-            if (op.dst >= 0) d4g_st_agent((uint32_t*)&state_ptr(c, blk, op.dst)->valid, 0u);
-        }
-        if (op.dst >= 0) wg_publish_slot(c, q, blk, op.dst);
-    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1785,32 +1669,8 @@ __global__ void __launch_bounds__(64) k_exec_hdr_search(D4GCtx c, const int32_t*
     __shared__ D4GHdrLds H;
     __shared__ __attribute__((aligned(16))) uint8_t comb[D4G_NLIT + D4G_NDIST];   // (compared word-wise against the memo's key)
     int bs, orel;
-    if (!d4g_map_wg(c.nActive, nOpsLevel, c.tileGroups, bs, orel)) return;
+    if (!d4g_map_wg(c.nActive, nOpsLevel, bs, orel)) return;
     d4g_exec_hdr_search(H, comb, c, c.active[bs], opList[orel]);
-}
-
-__global__ void __launch_bounds__(64) k_persist_hdr_search(D4GCtx c, D4GQueue q) {
-    D4G_SETPRIO(D4G_BASE_PRIO);
-    __shared__ D4GHdrLds H;
-    __shared__ __attribute__((aligned(16))) uint8_t comb[D4G_NLIT + D4G_NDIST];   // (compared word-wise against the memo's key)
-    __shared__ int sTask[3], sOk;
-    int cursor = 0;
-    while (true) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int oi = 0, ai = 0;
-            sTask[0] = d4g_pull_task(q, cursor, oi, ai) ? 1 : 0;
-            sTask[1] = oi;
-            sTask[2] = ai;
-        }
-        __syncthreads();
-        if (!sTask[0]) break;
-        int opId = q.opFlat[sTask[1]];
-        int blk = c.active[sTask[2]];
-        bool ok = wg_wait_slot(c, q, blk, c.ops[opId].src, &sOk);
-        if (ok) d4g_exec_hdr_search(H, comb, c, blk, opId);
-        else if (threadIdx.x == 0) c.keys[(long long)blk * c.nOps + opId] = D4G_KEY_NONE;
-    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1825,14 +1685,6 @@ __global__ void __launch_bounds__(256) k_select(D4GCtx c, D4GRoundResult* result
     const D4GBlock b = c.blocks[blk];
     D4GState* S = &L.st;
     D4GState* cur = state_ptr(c, blk, 0);
-    if (d4g_ld_agent(c.errors + 1) != 0) {   // a wait of the persistent executor gave up: the keys are incomplete — nothing is selected
-        if (threadIdx.x == 0) {
-            D4GRoundResult r;
-            r.curSize = cur->sizeBits; r.bestSize = cur->sizeBits; r.bestSeq = -1; r.improved = -1; r.newType = cur->type; r.pad = 0;
-            results[blockIdx.x] = r;
-        }
-        return;
-    }
     const long long* keys = c.keys + (long long)blk * c.nOps;
     long long best = D4G_KEY_NONE;
     for (int i = threadIdx.x; i < c.nOps; i += blockDim.x) best = keys[i] < best ? keys[i] : best;

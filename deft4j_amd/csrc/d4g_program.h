@@ -26,9 +26,7 @@ struct Program {
     std::vector<std::vector<int>> stateLevels, hdrLevels;
     RtBuf<D4GOp> dOps;
     RtBuf<int32_t> dLists;
-    RtBuf<int32_t> dStateFlat, dHdrFlat;  // level-ordered op ids for the persistent executor
-    int nStateFlat = 0, nHdrFlat = 0;
-    std::vector<std::pair<size_t, int>> stateOff, hdrOff, wideOff;  // per level: (offset into dLists, count)
+    std::vector<std::pair<size_t, int>> stateOff, hdrOff;  // per level: (offset into dLists, count)
     int nRequested = 0;  // ops the plain unrolling would have emitted (for the record)
     std::set<int> hsCodes;  // distinct code-length sets among the header searches (for the record)
 
@@ -248,37 +246,21 @@ struct Program {
         for (auto& v : stateLevels) std::stable_sort(v.begin(), v.end(), [&](int x, int y) { return cost(x) > cost(y); });
     }
     void release() {
-        dOps.reset(); dLists.reset(); dStateFlat.reset(); dHdrFlat.reset();
-        stateOff.clear(); hdrOff.clear(); wideOff.clear();
+        dOps.reset(); dLists.reset();
+        stateOff.clear(); hdrOff.clear();
     }
     void upload() {
         dOps.alloc(ops.size());
         rt_h2d(dOps, ops.data(), ops.size() * sizeof(D4GOp));
         std::vector<int32_t> lists;
         for (int l = 0; l < nLevels; l++) {
-            // token-pass-only ops (no single-lane section) go to the wide-workgroup launch
-            std::vector<int> narrow, wide;
-            for (int id : stateLevels[l]) (wide_block() > 0 && ((wide_kinds() >> ops[id].kind) & 1) ? wide : narrow).push_back(id);
-            stateOff.push_back({lists.size(), (int)narrow.size()});
-            lists.insert(lists.end(), narrow.begin(), narrow.end());
-            wideOff.push_back({lists.size(), (int)wide.size()});
-            lists.insert(lists.end(), wide.begin(), wide.end());
+            stateOff.push_back({lists.size(), (int)stateLevels[l].size()});
+            lists.insert(lists.end(), stateLevels[l].begin(), stateLevels[l].end());
             hdrOff.push_back({lists.size(), (int)hdrLevels[l].size()});
             lists.insert(lists.end(), hdrLevels[l].begin(), hdrLevels[l].end());
         }
         dLists.alloc(lists.size());
         rt_h2d(dLists, lists.data(), lists.size() * sizeof(int32_t));
-        std::vector<int32_t> sf, hf;
-        for (int l = 0; l < nLevels; l++) {
-            sf.insert(sf.end(), stateLevels[l].begin(), stateLevels[l].end());
-            hf.insert(hf.end(), hdrLevels[l].begin(), hdrLevels[l].end());
-        }
-        nStateFlat = (int)sf.size();
-        nHdrFlat = (int)hf.size();
-        dStateFlat.alloc(sf.size(), 16);
-        dHdrFlat.alloc(hf.size(), 16);
-        rt_h2d(dStateFlat, sf.data(), sf.size() * sizeof(int32_t));
-        rt_h2d(dHdrFlat, hf.data(), hf.size() * sizeof(int32_t));
         rt_sync();
     }
 };

@@ -99,7 +99,7 @@ struct RtGlobals {
         // in creation order, and a thread that created sixteen streams up front pushed the next thread's main stream back onto
         // the first thread's queue — where that thread's candidate search (one launch of milliseconds) held up the other batch's
         // parse (measured: two batches in flight 9.7 ms per step when they collided, 7.0 when they did not).
-        // For the same reason a lane's header-search stream is made when a persistent or level-executor round first launches on
+        // For the same reason a lane's header-search stream is made when a level-executor round first launches on
         // it: the fused search runs on the state-op stream alone, so every thread makes one stream, and the threads' streams
         // take HIP's hardware queues in turn.  With both made up front, each thread's state-op stream could take the same queue
         // as the last thread's (two queues, six batches in flight: 8.3 against 5.7-5.9 ms per step, profiles/stream_creation_ab.json).

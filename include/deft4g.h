@@ -72,8 +72,6 @@ typedef struct d4g_stats {
     int64_t zopfli_blocks, zopfli_position_iterations;
     /* fused executor (one workgroup per block, all rounds): optimiseBlock rounds it ran, rounds handed to the level executor */
     int64_t rounds_fused, fused_fallbacks;
-    /* rounds of the persistent executor that were run again by the level executor because a cross-kernel wait gave up */
-    int64_t persist_fallbacks;
     /* optimiseBlock rounds of long merged blocks run by the cluster kernel (the whole device on one block) */
     int64_t rounds_cluster;
     /* round-trip verification (d4g_batch_verify, D4G_VERIFY=1): wall clock; device time of the re-parse of the written
@@ -90,7 +88,7 @@ typedef struct d4g_stats {
     /* fused executor, which way a block left a launch: fused_fallbacks_mid = fallbacks (counted in fused_fallbacks too) of a
      * launch that had completed at least one round of that block; fused_relaunches = blocks launched again in k_search_fused,
      * after the per-launch round limit or after an improving level-executor round; cluster_fallbacks = rounds the cluster
-     * kernel could not hold and handed to the level / persistent executors */
+     * kernel could not hold and handed to the level executor */
     int64_t fused_fallbacks_mid, fused_relaunches, cluster_fallbacks;
     /* header scan: scan_candidates = bit positions with a plausible prolog and a complete code-length code; scan_kept = those
      * whose coded code lengths also give complete codes, which is what the probe is run on */

@@ -17,7 +17,7 @@ print("streams", n, "idat", sum(1 for g in gen if g[0] == "idat"), "decoded MiB 
 for it in range(2):
     L.d4g_debug_fused_stats(buf)
     b = D.Batch(streams); t0 = time.time(); b.run(True); dt = time.time() - t0; st = b.stats(); b.close()
-keys = ["n_blocks", "ms_parse", "ms_optimise", "ms_merge", "ms_write", "ms_total", "rounds_fused", "rounds_cluster", "fused_fallbacks", "persist_fallbacks", "kernel_launches", "state_launches", "ms_state_kernels"]
+keys = ["n_blocks", "ms_parse", "ms_optimise", "ms_merge", "ms_write", "ms_total", "rounds_fused", "rounds_cluster", "fused_fallbacks", "cluster_fallbacks", "kernel_launches", "state_launches", "ms_state_kernels"]
 print("%.2f s;" % dt, {k: st[k] for k in keys if k in st}, flush=True)
 L.d4g_debug_fused_stats(buf)
 names = ["sweep", "apply", "binbase", "least", "tree", "hdr", "hs", "fixdot"]

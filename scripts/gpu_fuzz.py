@@ -8,7 +8,7 @@ HUFFMAN_ONLY and RLE strategies, long runs (len-258 matches), tiny blocks.
 usage: gpu_fuzz.py [seconds] [seed] [--big] [--sim] [--diff]
   --sim   the CPU emulation of the kernels, tests/hostsim — small inputs
   --diff  no oracle: every batch runs under each executor configuration (fused, fused with cluster mode for every block
-          above 2000 back-references, levels, persistent) and the outputs must be identical — fast, so also 4-8 MiB inputs;
+          above 2000 back-references, levels) and the outputs must be identical — fast, so also 4-8 MiB inputs;
           the level executor is the one the oracle runs of rounds 1-2 pinned"""
 import os, random, sys, time, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +21,7 @@ rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 and not sys.argv[2].st
 SIM = "--sim" in sys.argv
 DIFF = "--diff" in sys.argv
 CONFIGS = [{"D4G_EXEC": "fused"}, {"D4G_EXEC": "fused", "D4G_CLUSTER_MIN_REFS": "2000", "D4G_FUSED_MAX_REFS": "2000"},
-           {"D4G_EXEC": "levels"}, {"D4G_EXEC": "persistent"}]
+           {"D4G_EXEC": "levels"}]
 LIB = None
 if SIM:
     os.environ.setdefault("D4G_SIM_BLOCK", "64")

@@ -82,7 +82,7 @@ def one_shot_with_a_corrupt_stream(D, L, env):
 def levels_chain_lookup(D, L, env):
     """the level executor on the tiny dynamic blocks it cannot follow: raised in phase 1, with the whole working set made"""
     env("D4G_EXEC", "levels")
-    for c in H.by_name(H.LEGACY_EXEC_BAD):
+    for c in H.by_name(H.LEVEL_EXEC_BAD):
         b = D.Batch([c.data], lib=L)
         with pytest.raises(RuntimeError, match="phase1: chain lookup failed"):
             b.run(True)

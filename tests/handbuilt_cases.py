@@ -410,10 +410,10 @@ SUBSET = ["hlit_288", "hdist_32", "codes_11_to_15_bits", "oversubscribed_8bit_25
           "zlib1_sync_then_stored_nlen_cut", "stored_payload_past_eof_final", "decoy_stored_shift_3", "zero_run_crosses_into_distances"]
 
 
-# The level and persistent executors (D4G_EXEC=levels|persistent, which the default fused executor hands only blocks
-# of more than 16 Ki back-references) stop with "phase1: chain lookup failed" on these tiny dynamic blocks: their
+# The level executor (D4G_EXEC=levels, which the default fused executor hands only what it and the cluster kernel cannot
+# hold) stops with "phase1: chain lookup failed" on these tiny dynamic blocks: its
 # round's starting size differs from the parsed block's.  Not fixed here; pinned by a strict xfail in the emulator test.
-LEGACY_EXEC_BAD = ["run_ends_at_hlit_plus_hdist", "rep16_crosses_into_distances", "oversubscribed_eob_reachable",
+LEVEL_EXEC_BAD = ["run_ends_at_hlit_plus_hdist", "rep16_crosses_into_distances", "oversubscribed_eob_reachable",
                    "distance_across_fixed_stored_dyn", "empty_dynamic_final"]
 
 

@@ -103,8 +103,8 @@ def test_mixed_batch(sim, monkeypatch):
 
 
 def test_cluster_refusal(sim, monkeypatch):
-    """run_cluster returns false when the cluster kernel's round did not fit: the merge candidate goes to the level /
-    persistent executors; uncapped, the cluster kernel runs it"""
+    """run_cluster returns false when the cluster kernel's round did not fit: the merge candidate goes to the level
+    executor; uncapped, the cluster kernel runs it"""
     for k, v in F.CLUSTER_ENV.items():
         monkeypatch.setenv(k, v)
     a = [F.cluster_stream()]

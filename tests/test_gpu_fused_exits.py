@@ -105,8 +105,8 @@ def test_mixed_blocks_as_one_stream(lib, monkeypatch, table, cap):
 
 
 def test_cluster_refusal(lib, monkeypatch):
-    """run_cluster returns false when the cluster kernel's round did not fit: the merge candidate goes to the level /
-    persistent executors; uncapped, the cluster kernel runs it"""
+    """run_cluster returns false when the cluster kernel's round did not fit: the merge candidate goes to the level
+    executor; uncapped, the cluster kernel runs it"""
     for k, v in F.CLUSTER_ENV.items():
         monkeypatch.setenv(k, v)
     a = [F.cluster_stream()]
@@ -138,7 +138,7 @@ def test_mask_word_edges(lib):
     1, 4, 64 and 256 words — the most the register form of the mask tasks holds"""
     streams = [worth_optimising(n) for n in F.EDGE_REFS]
     _, st = uncapped(lib, "edges", streams, False)
-    # `rounds` counts the fused pass once and every fix-point round of the level / persistent executors: 1 = no block left k_search_fused
+    # `rounds` counts the fused pass once and every fix-point round of the level executor: 1 = no block left k_search_fused
     assert st["n_blocks"] == len(streams) and st["rounds_fused"] >= 2 * len(streams) and st["rounds"] == 1, st
     # 16384 is the most Batch::phase1 hands the fused kernel by default: that block as a batch of its own
     one = [F.edge_block(16384)]
@@ -148,7 +148,7 @@ def test_mask_word_edges(lib):
 
 def test_mask_word_edges_in_the_chunked_form(lib, monkeypatch):
     """16385 and 16449 back-references are 257 and 258 mask words: with D4G_FUSED_MAX_REFS raised the fused kernel takes them,
-    in the chunked form of its mask tasks; left alone they are the level / persistent executors' (the uncapped batch)"""
+    in the chunked form of its mask tasks; left alone they are the level executor's (the uncapped batch)"""
     streams = [worth_optimising(n) for n in F.EDGE_REFS_CHUNKED]
     _, base = uncapped(lib, "edges_chunked", streams, False)
     assert base["rounds_fused"] == 0 and base["rounds"] >= 2, base

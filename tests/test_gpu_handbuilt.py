@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 CONFIGS = {"fused": {"D4G_EXEC": "fused"},
            "cluster": {"D4G_EXEC": "fused", "D4G_CLUSTER_MIN_REFS": "2000", "D4G_FUSED_MAX_REFS": "2000"},
-           "levels": {"D4G_EXEC": "levels"}, "persistent": {"D4G_EXEC": "persistent"}}
+           "levels": {"D4G_EXEC": "levels"}}
 
 
 @pytest.fixture(scope="module")
@@ -30,7 +30,7 @@ def test_corpus_as_one_batch(lib, monkeypatch, cfg):
     for k, v in CONFIGS[cfg].items():
         monkeypatch.setenv(k, v)
     D, L = lib
-    cs = [c for c in H.cases() if cfg in ("fused", "cluster") or c.name not in H.LEGACY_EXEC_BAD]
+    cs = [c for c in H.cases() if cfg in ("fused", "cluster") or c.name not in H.LEVEL_EXEC_BAD]
     assert not names(cs, H.compare(D, L, O, [c.data for c in cs], abi=cfg == "fused"))
 
 

@@ -42,11 +42,11 @@ def test_all_reference_fixture_pairs_bit_exact(D):
         b.close()
 
 
-@pytest.mark.parametrize("mode", ["levels", "persistent", "fused"])
+@pytest.mark.parametrize("mode", ["levels", "fused"])
 def test_fixture_pairs_under_each_executor(D, monkeypatch, mode):
-    """The candidate search has two executors (d4g_host.h exec_persistent): `persistent` work-queue kernels (default at
-    <= 128 active blocks) and one launch per program level (`levels`, the one bench.py's 332-block stream runs).
-    Both must reproduce all 30 reference pairs."""
+    """D4G_EXEC (d4g_knobs.h exec_fused): `fused`, the default (one workgroup per block, k_search_fused, with the cluster
+    kernel for a lone long block), and `levels` (one launch per program level), which takes what those hand back and is
+    the cross-check.  Both must reproduce all 30 reference pairs."""
     monkeypatch.setenv("D4G_EXEC", mode)
     for merge in (True, False):
         pairs = [p for p in MAN["pairs"] if p["merge_blocks"] == merge]
@@ -58,6 +58,20 @@ def test_fixture_pairs_under_each_executor(D, monkeypatch, mode):
         b.close()
 
 
+def test_unknown_executor_name_is_refused(D, monkeypatch):
+    """D4G_EXEC accepts `fused` and `levels`; anything else (here the name of the retired third executor) fails the call with
+    an error that names the knob, and the same call succeeds in the same process once the knob is unset (it is read "now")."""
+    a = synth.make_stream(1500, 3)
+    monkeypatch.setenv("D4G_EXEC", "persistent")
+    with pytest.raises(RuntimeError, match="D4G_EXEC"):
+        D.Batch([a]).run(False)
+    monkeypatch.delenv("D4G_EXEC")
+    b = D.Batch([a]).run(False)
+    rc, want, saved, _, _ = O.optimise(a, False)
+    assert rc >= 0 and b.result(0)["status"] == rc and b.result(0)["saved_bits"] == saved and b.output(0) == want
+    b.close()
+
+
 def _oracle_many(ins, merge):
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:   # ctypes releases the GIL
@@ -66,9 +80,9 @@ def _oracle_many(ins, merge):
 
 @pytest.mark.parametrize("merge", [False, True])
 def test_levels_executor_large_batch_vs_oracle(D, merge, monkeypatch):
-    """More than 128 dynamic blocks in one batch, so without the fused executor the choice is `levels` with two stream lanes
-    (round 2's launch sequencing): 28 x 1 MiB reptext members, every output byte-compared with the oracle."""
-    monkeypatch.setenv("D4G_EXEC", "auto")   # the level / persistent executors, chosen by block count
+    """More than 128 dynamic blocks in one batch under the level executor, which then uses two stream lanes: 28 x 1 MiB
+    reptext members, every output byte-compared with the oracle."""
+    monkeypatch.setenv("D4G_EXEC", "levels")
     raws = [synth.reptext(1 << 20, 0x5EED + i) for i in range(28)]
     ins = [synth.deflate9(r) for r in raws]
     b = D.Batch(ins).run(merge)
@@ -227,20 +241,6 @@ def test_fuzz_regressions(D):
             b.close()
 
 
-def test_persistent_wait_expiry_is_recovered_by_the_level_executor(D, monkeypatch):
-    """A wait of the persistent executor that gives up (D4G_SPIN_LIMIT=0: any wait whose slot is not there yet) is not an
-    error: nothing is selected, the round runs again with the level executor; output == oracle, fallback counted."""
-    monkeypatch.setenv("D4G_EXEC", "persistent")
-    monkeypatch.setenv("D4G_SPIN_LIMIT", "-1")
-    a = synth.make_stream(300000, 4)
-    for merge in (False, True):
-        b = D.Batch([a]).run(merge)
-        rc, want, saved, _, _ = O.optimise(a, merge)
-        assert b.output(0) == want and b.result(0)["saved_bits"] == saved
-        assert b.stats()["persist_fallbacks"] > 0
-        b.close()
-
-
 def test_config5_mix_through_the_sharded_path(D):
     """BASELINE config 5 at reduced size on the real library: 14 streams of the PNG-IDAT-like / gzip-member mix
     (synth.mixed_spec, sizes divided by 32 -> 32-512 KiB) through shard.optimise_sharded with one rank, merge on (the CLI
@@ -264,8 +264,7 @@ def test_config5_mix_through_the_sharded_path(D):
 
 def test_cluster_mode_on_a_merge_chain_vs_oracle(D):
     """A 4 MiB stream with merge on: its merge chain grows one block past the length at which a lone block gets the whole
-    device (k_search_cluster: the control workgroup's commands worked off by every workgroup); output == the oracle's, and
-    == the persistent executor's with D4G_CLUSTER=0."""
+    device (k_search_cluster: the control workgroup's commands worked off by every workgroup); output == the oracle's."""
     a = synth.make_stream(4 << 20, 77)
     b = D.Batch([a]).run(True)
     st = b.stats()

@@ -77,7 +77,7 @@ def test_all_reference_fixture_pairs_verify(D):
     _fixture_pairs_verify(D, "default")
 
 
-@pytest.mark.parametrize("mode", ["levels", "persistent", "fused"])
+@pytest.mark.parametrize("mode", ["levels", "fused"])
 def test_fixture_pairs_verify_under_each_executor(D, monkeypatch, mode):
     monkeypatch.setenv("D4G_EXEC", mode)
     _fixture_pairs_verify(D, mode)

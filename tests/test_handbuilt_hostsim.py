@@ -62,8 +62,8 @@ def test_every_prefix_in_the_emulator(sim):
     assert not named(cs, H.compare_parse(D, L, O, [c.data for c in cs]))
 
 
-@pytest.mark.parametrize("cfg", [{"D4G_EXEC": "fused"}, {"D4G_EXEC": "levels"}, {"D4G_EXEC": "persistent"}, {"D4G_MEMO": "0"}],
-                         ids=["fused", "levels", "persistent", "memo0"])
+@pytest.mark.parametrize("cfg", [{"D4G_EXEC": "fused"}, {"D4G_EXEC": "levels"}, {"D4G_MEMO": "0"}],
+                         ids=["fused", "levels", "memo0"])
 def test_subset_under_each_executor(sim, monkeypatch, cfg):
     for k, v in cfg.items():
         monkeypatch.setenv(k, v)
@@ -82,10 +82,10 @@ def test_recompress_loop_in_the_emulator(sim):
             assert r == OC.recompress(a, merge), merge
 
 
-@pytest.mark.xfail(strict=True, raises=RuntimeError, reason="level / persistent executors: chain lookup fails on tiny dynamic blocks")
-@pytest.mark.parametrize("mode", ["levels", "persistent"])
-def test_legacy_executors_on_tiny_dynamic_blocks(sim, monkeypatch, mode):
+@pytest.mark.xfail(strict=True, raises=RuntimeError, reason="level executor: chain lookup fails on tiny dynamic blocks")
+@pytest.mark.parametrize("mode", ["levels"])
+def test_level_executor_on_tiny_dynamic_blocks(sim, monkeypatch, mode):
     monkeypatch.setenv("D4G_EXEC", mode)
     D, L = sim
-    for c in H.by_name(H.LEGACY_EXEC_BAD):
+    for c in H.by_name(H.LEVEL_EXEC_BAD):
         D.Batch([c.data], lib=L).run(True).close()
