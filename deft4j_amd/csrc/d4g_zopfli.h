@@ -623,6 +623,13 @@ D4G_DEV int zf_sort_leaves(const uint32_t* counts, int n, uint32_t* w, uint16_t*
     d4g_wave_sync();
     return nz;
 }
+// A package's weight.  A package of level l can hold every leaf l times over, so with a total above 2^32 / maxbits the sum
+// no longer fits: it saturates.  A saturated package is still heavier than every leaf (the total stays below 2^32) and keeps
+// its place among the packages, which come in rising order, so the merged order is the exact one.
+D4G_DEV uint32_t zf_pm_pair(uint32_t a, uint32_t b) {
+    const uint32_t s = a + b;
+    return s < a ? 0xffffffffu : s;
+}
 // Package-merge, one lane: level l's list = leaves merged with the pairs of level l-1's list, a pair before a leaf of
 // equal weight (BoundaryPM's `sum > leaf weight` test); the code length of the r-th lightest leaf = the number of
 // levels whose selected prefix holds more than r leaves (ExtractBitLengths).  `out` (indexed by symbol) must be zero.
@@ -644,7 +651,7 @@ D4G_DEV void zf_pm_serial(const ZfPmRef& r, int maxbits, uint8_t* out) {
         while (i < m || k < np) {
             bool takeP = false;
             uint32_t pk = 0;
-            if (k < np) { pk = prev[2 * k] + prev[2 * k + 1]; takeP = i >= m || pk <= r.w[i]; }
+            if (k < np) { pk = zf_pm_pair(prev[2 * k], prev[2 * k + 1]); takeP = i >= m || pk <= r.w[i]; }
             if (takeP) { cur[cnt] = pk; k++; }
             else { cur[cnt] = r.w[i]; i++; bits[cnt >> 5] |= 1u << (cnt & 31); }
             cnt++;
@@ -693,13 +700,13 @@ D4G_DEV void zf_pm_wave(const ZfPmRef& r, int maxbits, uint8_t* out) {
         for (int i = lane; i < m; i += 64) {
             const uint32_t x = r.w[i];
             int lo = 0, hi = np;                       // first pair heavier than the leaf
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (prev[2 * mid] + prev[2 * mid + 1] <= x) lo = mid + 1; else hi = mid; }
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (zf_pm_pair(prev[2 * mid], prev[2 * mid + 1]) <= x) lo = mid + 1; else hi = mid; }
             const int pos = i + lo;
             cur[pos] = x;
             atomicOr(&bits[pos >> 5], 1u << (pos & 31));
         }
         for (int k = lane; k < np; k += 64) {
-            const uint32_t x = prev[2 * k] + prev[2 * k + 1];
+            const uint32_t x = zf_pm_pair(prev[2 * k], prev[2 * k + 1]);
             int lo = 0, hi = m;                        // first leaf at least as heavy as the pair
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (r.w[mid] < x) lo = mid + 1; else hi = mid; }
             cur[k + lo] = x;
