@@ -47,8 +47,12 @@
 struct D4FCode {            // 384 B
     uint8_t lens[D4G_NLIT + D4G_NDIST];
     int32_t nLit, nDist, type, err;
-    int32_t pad[12];
+    // the code's default header as last built in this launch (its pairs stay in D4FGlob.pairs[1 + code]); defStands: the record is there
+    uint8_t defClLen[20];
+    int32_t defNCl, defBits, defStands;
+    int32_t pad[4];
 };
+static_assert(sizeof(D4FCode) == 384, "the carve-up of the block's state slots (D4F_GLOB_BYTES)");
 struct D4FPairs {           // 656 B: a header's RLE pairs without their expanded-to-literals flags
     uint16_t pairs[D4G_MAXPAIRS];
     int32_t nPairs, pad[3];
@@ -81,8 +85,9 @@ struct D4FParams {
     int32_t pad;
     D4GRoundResult* results;   // [nActive][D4F_MAXROUNDS]
     int32_t* roundInfo;        // [nActive]: rounds completed | D4F_INFO_*
-    long long* stats;          // optional [32] counters
+    long long* stats;          // optional [D4F_NSTATS] counters
 };
+#define D4F_NSTATS 80         // (the first 64 are full: d4f_block_rounds lists them)
 // ---- cluster mode: many workgroups on ONE long block (the merge chain of a big stream) ----
 // Workgroup 0 runs the search exactly as k_search_fused does; what scales with the block's length — the sweeps over the
 // records, the mask updates, the record walks of the least-expensive pruning — it posts as *commands* that every workgroup
@@ -167,10 +172,8 @@ struct D4FTreeScr {
     alignas(16) unsigned char treeD[(D4FDistTree::bytes(1) + 15) & ~15];     // distance tree (built beside the literal/length tree)
     uint32_t hist[D4G_HIST];
     alignas(16) uint8_t lens[D4G_NLIT + D4G_NDIST];
-    uint16_t pairs[D4G_MAXPAIRS];
-    uint8_t clLen[32];
-    uint32_t clFreq[20];
-    int32_t nLit, nDist, nCl, nPairs, hdrBits, err, m, pad;
+    int32_t nLit, nDist, err, m, pad, found;     // found: the code id the read-only probe met, -1: none (d4f_tree_probe)
+    unsigned long long codeH;                    // hash of the lengths
     long long litlen;
 };
 // scratch of one wave for mask updates, least-expensive pruning and header operations
@@ -190,6 +193,13 @@ struct D4FHdrScr {           // header operation of one wave (overlays D4FWaveSc
     alignas(16) unsigned char tree[256];
     int32_t nCl, nPairs, bits, pad;
 };
+struct D4FDefScr {           // default header of one code by one wave (overlays D4FWaveScr; after the last tree batch of a step)
+    alignas(16) uint8_t lens[D4G_NLIT + D4G_NDIST];
+    uint16_t pairs[D4G_MAXPAIRS];
+    uint8_t clLen[32];
+    uint32_t clFreq[20];
+    alignas(16) unsigned char tree[256];
+};
 struct D4FSweepScr {
     uint16_t lc[D4F_SWEEP_K][256];
     uint8_t cl[D4F_SWEEP_K][64];
@@ -207,6 +217,7 @@ union D4FScratch {
     D4GLds levelLds;         // assembling the winner (the level executor's header functions)
 };
 static_assert(sizeof(D4FHdrScr) <= sizeof(D4FWaveScr), "header scratch overlays the wave scratch");
+static_assert(sizeof(D4FDefScr) <= sizeof(D4FWaveScr), "default-header scratch overlays the wave scratch");
 
 struct D4FLds {
     D4FSlot slot[D4F_MAXSLOTS];
@@ -1531,7 +1542,7 @@ D4F_TASK void d4f_tree_dist(int slotIdx, int m) {     // the slot's second wave:
     if (lane == 0) { T.nDist = nDist; T.pad = err; }
     d4g_wave_sync();
 }
-D4F_TASK void d4f_tree_header(int slotIdx) {          // wave A again, once both trees stand: token bits and the default header
+D4F_TASK void d4f_tree_bits(int slotIdx) {            // wave A again, once both trees stand: token bits
     D4FLds& F = d4fLds;
     D4FTreeScr& T = F.scr.tree[slotIdx];
     const int lane = threadIdx.x & 63;
@@ -1545,24 +1556,16 @@ D4F_TASK void d4f_tree_header(int slotIdx) {          // wave A again, once both
         }
     }
     v = wave_sum_i64(v);
-    int nPairs, nCl, bits;
-    const int err = d4f_wave_default_header(T.lens, T.nLit, T.nDist, T.pairs, T.clFreq, T.clLen, T.tree, nPairs, nCl, bits);
-    if (lane == 0) { T.nCl = nCl; T.nPairs = nPairs; T.hdrBits = bits; T.err |= err | T.pad; T.litlen = v; }
+    if (lane == 0) { T.err |= T.pad; T.litlen = v; }
     d4g_wave_sync();
 }
-// ids of a finished rebuild (one wave, tasks one after the other): an earlier code with the same lengths is reused
-D4F_TASK void d4f_tree_publish(int slotIdx) {
+// the code table's entry with the slot's lengths, or -1; k: where the probe ended (the entry, or the first empty place)
+D4G_DEV int d4f_code_probe(const D4FTreeScr& T, unsigned long long h, uint32_t& k) {
     D4FLds& F = d4fLds;
-    D4F_CTX;
-    D4FTreeScr& T = F.scr.tree[slotIdx];
+    const D4FGlob& G = F.G;
     const int lane = threadIdx.x & 63;
-    unsigned long long h = 0;
     const uint32_t* lw = (const uint32_t*)T.lens;
-    for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) h += d4f_mix1(i, lw[i]);
-    h = (unsigned long long)wave_sum_i64((long long)h) + (unsigned long long)T.nLit * 0x100000001b3ULL + ((unsigned long long)T.nDist << 48);
-    if (h == 0) h = 1;
-    int found = -1;
-    uint32_t k = (uint32_t)(h >> 40) & 255u;
+    k = (uint32_t)(h >> 40) & 255u;
     for (int probe = 0; probe < 256; probe++, k = (k + 1) & 255u) {
         const int e = F.codeHash[k];
         if (e == 0) break;
@@ -1572,19 +1575,89 @@ D4F_TASK void d4f_tree_publish(int slotIdx) {
             int bad = 0;
             for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) bad |= ((const uint32_t*)cd.lens)[i] != lw[i];
             if (lane == 0) bad |= cd.nLit != T.nLit || cd.nDist != T.nDist || cd.type != D4G_DYNAMIC;
-            if (!d4g_ballot(bad)) { found = id; break; }
+            if (!d4g_ballot(bad)) return id;
         }
     }
+    return -1;
+}
+// the slot's second wave, once both trees stand: hash of the lengths and the read-only look into the code table (the codes
+// of earlier steps and batches; what the slots before it in this batch insert is matched by d4f_tree_publish)
+D4F_TASK void d4f_tree_probe(int slotIdx) {
+    D4FLds& F = d4fLds;
+    D4FTreeScr& T = F.scr.tree[slotIdx];
+    const int lane = threadIdx.x & 63;
+    unsigned long long h = 0;
+    const uint32_t* lw = (const uint32_t*)T.lens;
+    for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) h += d4f_mix1(i, lw[i]);
+    h = (unsigned long long)wave_sum_i64((long long)h) + (unsigned long long)T.nLit * 0x100000001b3ULL + ((unsigned long long)T.nDist << 48);
+    if (h == 0) h = 1;
+    uint32_t k;
+    const int found = d4f_code_probe(T, h, k);
+    if (lane == 0) { T.codeH = h; T.found = found; }
+    d4g_wave_sync();
+}
+// the default header of a code (one wave; rewriteHeader() — a function of the lengths): built once in a launch.  Its header
+// id was given by d4f_tree_publish; what a later round needs to register it again stays with the code (D4FCode.def*).
+D4F_TASK void d4f_def_header(int waveSlot, int entry, long long* stats) {
+    D4FLds& F = d4fLds;
+    D4F_CTX;
+    D4FDefScr& X = *(D4FDefScr*)&F.scr.wave[waveSlot];
+    const int lane = threadIdx.x & 63;
+    const long long t0 = stats ? clock64() : 0;
+    const int code = entry >> 16, hid = entry & 0xffff;
+    D4FCode& cd = G.code[code];
+    for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) ((uint32_t*)X.lens)[i] = ((const uint32_t*)cd.lens)[i];
+    d4g_wave_sync();
+    int nPairs, nCl, bits;
+    const int err = d4f_wave_default_header(X.lens, cd.nLit, cd.nDist, X.pairs, X.clFreq, X.clLen, X.tree, nPairs, nCl, bits);
+    D4FPairs& pb = G.pairs[1 + code];
+    for (int i = lane; i < nPairs; i += 64) pb.pairs[i] = X.pairs[i];
+    D4FHdr& hd = G.hdr[hid];
+    if (lane < 32) hd.clLen[lane] = lane < 19 ? X.clLen[lane] : 0;
+    if (lane < 20) cd.defClLen[lane] = lane < 19 ? X.clLen[lane] : 0;
+    if (lane < 10) hd.flags[lane] = 0;
+    if (lane == 0) {
+        if (err) { cd.err |= err; atomicAdd(c.errors, 1); }
+        pb.nPairs = nPairs;
+        hd.nCl = nCl; hd.bits = bits; hd.base = 1 + code;
+        F.hdrBits[hid] = bits;
+        cd.defNCl = nCl; cd.defBits = bits; cd.defStands = 1;
+        if (stats) {
+            atomicAdd((unsigned long long*)&stats[64], 1ull);
+            atomicAdd((unsigned long long*)&stats[65], (unsigned long long)(clock64() - t0));
+        }
+    }
+    d4g_wave_sync();
+}
+// ids of a finished rebuild (one wave, tasks one after the other, in queue order): an earlier code with the same lengths is
+// reused.  A code met for the first time in the round is given its default header's id here; the header itself is
+// registered from the code's record when it stands, else queued (F.treeCand[0], F.misc[4]) to be built after the step's
+// last batch.
+D4F_TASK void d4f_tree_publish(int slotIdx, long long* stats) {
+    D4FLds& F = d4fLds;
+    D4F_CTX;
+    D4FTreeScr& T = F.scr.tree[slotIdx];
+    const int lane = threadIdx.x & 63;
+    const uint32_t* lw = (const uint32_t*)T.lens;
+    const unsigned long long h = T.codeH;
+    int found = T.found;
+    uint32_t k = 0;
+    if (found < 0) {   // (a slot before this one may have inserted the code; k: the first empty place)
+        found = d4f_code_probe(T, h, k);
+        if (stats && threadIdx.x == 0 && found >= 0) atomicAdd((unsigned long long*)&stats[71], 1ull);
+    }
+    if (stats && threadIdx.x == 0 && found >= 0) atomicAdd((unsigned long long*)&stats[70], 1ull);
     int code = found;
+    bool refused = false;                       // no id left for the code: the round is given up, no header is built for it
     const int nCodeNow = __shfl(F.nCode, 0);   // (every lane reads before lane 0 writes)
     if (code < 0) {
         code = nCodeNow;
-        if (code >= F.capC) { if (lane == 0) F.fallback = 1; code = 0; }
+        if (code >= F.capC) { if (lane == 0) F.fallback = 1; code = 0; refused = true; }
         else {
             D4FCode& cd = G.code[code];
             for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) ((uint32_t*)cd.lens)[i] = lw[i];
             if (lane == 0) {
-                cd.nLit = T.nLit; cd.nDist = T.nDist; cd.type = D4G_DYNAMIC; cd.err = T.err;
+                cd.nLit = T.nLit; cd.nDist = T.nDist; cd.type = D4G_DYNAMIC; cd.err = T.err; cd.defStands = 0;
                 F.nCode = code + 1;
                 F.codeH[code] = h;
                 F.defHdr[code] = -1;
@@ -1599,19 +1672,32 @@ D4F_TASK void d4f_tree_publish(int slotIdx) {
     const int nHdrNow = __shfl(F.nHdr, 0);
     if (defNow < 0) {   // the code's default header (rewriteHeader()) — a function of the lengths
         int hid = nHdrNow;
-        if (hid >= F.capH) { if (lane == 0) F.fallback = 1; hid = 0; }
-        else {
-            D4FPairs& pb = G.pairs[1 + code];
-            for (int i = lane; i < T.nPairs; i += 64) pb.pairs[i] = T.pairs[i];
-            D4FHdr& hd = G.hdr[hid];
-            if (lane < 32) hd.clLen[lane] = lane < 19 ? T.clLen[lane] : 0;
-            if (lane < 10) hd.flags[lane] = 0;
+        if (hid >= F.capH) {
+            if (lane == 0) F.fallback = 1;
+            hid = 0;
+            if (stats && threadIdx.x == 0) atomicAdd((unsigned long long*)&stats[72], 1ull);
+        } else {
+            const long long t0 = stats ? clock64() : 0;
+            const D4FCode& cd = G.code[code];
+            const int stands = found >= 0 ? __shfl(cd.defStands, 0) : 0;
+            if (stands) {   // built in an earlier round of the launch: the pairs are still in G.pairs[1 + code]
+                D4FHdr& hd = G.hdr[hid];
+                if (lane < 32) hd.clLen[lane] = lane < 19 ? cd.defClLen[lane] : 0;
+                if (lane < 10) hd.flags[lane] = 0;
+                if (lane == 0) {
+                    const int bits = cd.defBits;
+                    hd.nCl = cd.defNCl; hd.bits = bits; hd.base = 1 + code;
+                    F.hdrBits[hid] = bits;
+                }
+            }
             if (lane == 0) {
-                pb.nPairs = T.nPairs;
-                hd.nCl = T.nCl; hd.bits = T.hdrBits; hd.base = 1 + code;
-                F.hdrBits[hid] = T.hdrBits;
+                if (!stands && !refused) F.treeCand[0][F.misc[4]++] = (code << 16) | hid;
                 F.nHdr = hid + 1;
                 F.defHdr[code] = (int16_t)hid;
+                if (stats && stands && threadIdx.x == 0) {
+                    atomicAdd((unsigned long long*)&stats[66], 1ull);
+                    atomicAdd((unsigned long long*)&stats[67], (unsigned long long)(clock64() - t0));
+                }
             }
         }
     }
@@ -2117,6 +2203,7 @@ D4F_TASK bool d4f_round_setup(const D4GOp* ops0, const D4GOp* ops1, int nOps0, i
         __syncthreads();
         for (int i = threadIdx.x; i < D4F_MAXC; i += blockDim.x) { F.eState[i] = 0; F.eEq[i] = 0; F.bbState[i] = 0; F.hsState[i] = 0; }
         for (int i = threadIdx.x; i < 256; i += blockDim.x) F.codeHash[i] = 0;
+        for (int i = threadIdx.x; i < D4F_MAXC; i += blockDim.x) G.code[i].defStands = 0;   // (no default header outlives its code)
         if (threadIdx.x == 0) F.nCode = 2;
         __syncthreads();
     }
@@ -2183,7 +2270,7 @@ D4F_TASK bool d4f_round_setup(const D4GOp* ops0, const D4GOp* ops1, int nOps0, i
             ((uint32_t*)cd.lens)[lane] = w0;
             if (lane < 16) ((uint32_t*)cd.lens)[64 + lane] = w1;
             if (lane == 0) {
-                cd.nLit = nLit0; cd.nDist = nDist0; cd.type = curType; cd.err = 0;
+                cd.nLit = nLit0; cd.nDist = nDist0; cd.type = curType; cd.err = 0; cd.defStands = 0;
                 F.nCode = code + 1;
                 F.codeH[code] = h;
                 F.codeHash[k] = (uint8_t)(code + 1);
@@ -2317,10 +2404,17 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
     int rounds = 0, info = 0;
     // optional accounting (D4G_FUSED_STATS): [0,8) tasks per kind, [8,16) steps per kind, [16,24) cycles per kind, 24 advance,
     // 25 set-up, 26 selection, 27 rounds, 28 steps, 29 cycles in total, 30 / 31 / 32 masks / codes / headers made,
-    // 62 header-search candidates whose code-length tree took the depth limiter
+    // 62 header-search candidates whose code-length tree took the depth limiter; 64 / 65 default headers built and the
+    // building waves' cycles, 66 / 67 default headers registered again from a code's record and cycles, 68 / 69 header
+    // sub-steps of the tree step and cycles, 70 built trees whose code was in the table already, 71 those of them whose code
+    // a slot before them in the same batch had inserted, 72 default headers refused an id (D4FParams.caps)
     const bool prof = P.stats != nullptr && threadIdx.x == 0;
     auto acc = [&](int k, long long v) { if (prof) atomicAdd((unsigned long long*)&P.stats[k], (unsigned long long)v); };
     const long long tKernel = prof ? clock64() : 0;
+    // the code table starts empty (d4f_block_init): no code has a default header from this launch yet.  (Here and not in
+    // d4f_block_init: the table is the control workgroup's alone, a cluster launch's helpers must not write to it.)
+    for (int i = threadIdx.x; i < D4F_MAXC; i += blockDim.x) F.G.code[i].defStands = 0;
+    __syncthreads();
     for (;;) {
         long long tp = prof ? clock64() : 0;
         if (!d4f_round_setup(P.ops[0], P.ops[1], P.nOps[0], P.nOps[1])) { info |= D4F_INFO_FALLBACK; break; }
@@ -2430,6 +2524,7 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
                         else F.treeCand[1][na++] = (m << 16) | from;
                     }
                     F.misc[3] = nu;
+                    F.misc[4] = 0;   // codes of this step whose default header is to be built (listed in treeCand[0], which is free from here on)
                 }
                 __syncthreads();
                 const int nu = F.misc[3];
@@ -2448,13 +2543,27 @@ __device__ __forceinline__ void d4f_block_rounds(const D4FParams& P) {
                     if (prof) { acc(33, clock64() - tq); tq = clock64(); }
                     __syncthreads();
                     if (prof) { acc(34, clock64() - tq); tq = clock64(); }
-                    if (ts < nts && t0 + ts < nu && !distWave) d4f_tree_header(ts);
+                    // both trees stand: the first wave sums the token bits while the second looks the lengths up in the code table
+                    if (ts < nts && t0 + ts < nu) {
+                        if (distWave) d4f_tree_probe(ts); else d4f_tree_bits(ts);
+                    }
                     __syncthreads();
                     if (prof) { acc(35, clock64() - tq); tq = clock64(); }
                     if (wave == 0)
-                        for (int t = 0; t < nts && t0 + t < nu; t++) d4f_tree_publish(t);
+                        for (int t = 0; t < nts && t0 + t < nu; t++) d4f_tree_publish(t, P.stats);
                     __syncthreads();
                     if (prof) { acc(36, clock64() - tq); acc(37, 1); }
+                }
+                // the default headers of the step's new codes, one wave each (the tree slots are done with the scratch)
+                const int nDef = F.misc[4];
+                if (nDef > 0) {
+                    const long long tq = prof ? clock64() : 0;
+                    const int nhw = nw < 8 ? nw : 8;
+                    for (int d0 = 0; d0 < nDef; d0 += nhw) {
+                        if (wave < nhw && d0 + wave < nDef) d4f_def_header(wave, F.treeCand[0][d0 + wave], P.stats);
+                        __syncthreads();
+                    }
+                    if (prof) { acc(68, 1); acc(69, clock64() - tq); }
                 }
                 if (threadIdx.x == 0) {   // in queue order: a mask copied from an earlier one of this queue finds it finished
                     for (int k = 0; k < nq - nu; k++) {

@@ -335,7 +335,7 @@ struct Engine {  // per-process device objects shared by all batches
         build_hdr_tables(tab, tab + 64);
         dHdrTables.alloc(128);
         rt_h2d(dHdrTables, tab, 128);
-        dOpStats.alloc_zero(64);
+        dOpStats.alloc_zero(D4F_NSTATS);
         {
             std::vector<uint32_t> t(1024 + 32);
             for (uint32_t i = 0; i < 256; i++) {

@@ -1439,7 +1439,18 @@ int d4g_debug_fused_stats(long long* out64) {
         engine().init();
         rt_sync_all();
         rt_d2h(out64, engine().dOpStats, 64 * 8);
-        rt_memset(engine().dOpStats, 0, 64 * 8);
+        rt_memset(engine().dOpStats, 0, D4F_NSTATS * 8);
+        rt_sync();
+        return D4G_OK;
+    });
+}
+// the same with the counters past the first 64 (the tree step's header accounting): out holds D4F_NSTATS (80) entries
+int d4g_debug_fused_stats_all(long long* out80) {
+    return api(nullptr, [&] {
+        engine().init();
+        rt_sync_all();
+        rt_d2h(out80, engine().dOpStats, D4F_NSTATS * 8);
+        rt_memset(engine().dOpStats, 0, D4F_NSTATS * 8);
         rt_sync();
         return D4G_OK;
     });

@@ -22,7 +22,61 @@ __global__ void k_tree(const uint32_t* histG, uint8_t* lensG, long long* ticks, 
     for (int i = lane; i < D4G_NLIT; i += 64) lensG[i] = lens[i];
     if (lane == 0) { ticks[0] = t1 - t0; ticks[1] = err; }
 }
+// The code-length tree of a default header (19 leaves, limit 7): the wave-wide heap the fused search builds it with
+// (mode 0) against one lane with the tree in registers, d4g_cl_tree_regs, which the header search trusts (mode 1; a tree
+// deeper than 7 would go on to the one-lane limiter, d4g_build_tree, as in d4g_cl_lengths: err reports it).
+__global__ void k_cl_tree(const uint32_t* freqG, uint8_t* lensG, long long* ticks, int reps, int mode) {
+    __shared__ alignas(16) unsigned char mem[256];
+    __shared__ uint32_t freq[20];
+    __shared__ uint8_t lens[20];
+    const int lane = threadIdx.x & 63;
+    if (lane < 20) { freq[lane] = lane < 19 ? freqG[lane] : 0; lens[lane] = 0; }
+    __syncthreads();
+    TreeMem<uint32_t, uint8_t, 20> tm; tm.carve(mem, 1);
+    long long t0 = clock64();
+    int err = 0;
+    for (int r = 0; r < reps; r++) {
+        if (mode == 0) {
+            if (lane < 19) lens[lane] = 0;
+            d4g_wave_sync();
+            err |= d4g_build_tree_wave64<1>(tm, 19, 7, [&](int i) { return (unsigned)freq[i]; }, [&](int v, int len) { lens[v] = (uint8_t)len; });
+            d4g_wave_sync();
+        } else if (lane == 0) {
+            uint32_t f[19];
+#pragma unroll
+            for (int s = 0; s < 19; s++) f[s] = freq[s];
+            D4GClLens len;
+            len.lo = 0; len.hi = 0;
+            const bool deep = d4g_cl_tree_regs([&](int s) { return f[s]; }, len);
+            err |= deep ? 1 : 0;
+#pragma unroll
+            for (int s = 0; s < 19; s++) lens[s] = (uint8_t)len.get(s);
+        }
+        __syncthreads();
+    }
+    long long t1 = clock64();
+    if (lane < 19) lensG[lane] = lens[lane];
+    if (lane == 0) { ticks[0] = t1 - t0; ticks[1] = err; }
+}
 int main() {
+    {   // counts of a text block's default header: the lengths 5..12 carry most, the repeat codes a few
+        const uint32_t f[19] = {3, 0, 0, 1, 2, 6, 11, 14, 12, 9, 7, 4, 2, 0, 0, 0, 5, 3, 4};
+        uint32_t* df; uint8_t* dl; long long* dt;
+        hipMalloc(&df, 4 * 19); hipMalloc(&dl, 32); hipMalloc(&dt, 64);
+        hipMemcpy(df, f, 4 * 19, hipMemcpyHostToDevice);
+        for (int mode = 0; mode < 2; mode++)
+            for (int rep = 0; rep < 2; rep++) {
+                const int reps = 200;
+                hipLaunchKernelGGL(k_cl_tree, dim3(1), dim3(64), 0, 0, df, dl, dt, reps, mode);
+                hipDeviceSynchronize();
+                long long t[2]; hipMemcpy(t, dt, 16, hipMemcpyDeviceToHost);
+                uint8_t l[19]; hipMemcpy(l, dl, 19, hipMemcpyDeviceToHost);
+                unsigned ck = 0; for (int i = 0; i < 19; i++) ck = ck * 31 + l[i];
+                printf("code-length tree, %s: %.0f cycles per tree, err %lld, lens checksum %08x\n", mode ? "one lane in registers" : "wave-wide heap",
+                       (double)t[0] / reps, t[1], ck);
+            }
+        hipFree(df); hipFree(dl); hipFree(dt);
+    }
     std::vector<uint32_t> h(D4G_NLIT, 0);
     // 55 used literals with a text-like distribution + 256 + a few length symbols
     unsigned s = 12345;
