@@ -101,7 +101,7 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_batch_copy_output", "d4g_batch_copy_decoded", "d4g_batch_checksums", "d4g_batch_parse", "d4g_batch_stats", "d4g_batch_destroy", "d4g_optimise_streams",
            "d4g_size_bits_fallback", "d4g_inflate", "d4g_free", "d4g_batch_create_encode", "d4g_batch_run_encode", "d4g_deflate_streams",
            "d4g_compress", "d4g_recompress_streams", "d4g_batch_run_recompress", "d4g_batch_recompress_result", "d4g_zopfli_streams",
-           "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
+           "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_debug_pack_header", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
            "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
            "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
            "d4g_debug_device_blocks", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name",
@@ -179,6 +179,8 @@ def load_library(path=None):
     L.d4g_debug_zopfli_code_lengths.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
     L.d4g_debug_cl_tree_lengths.restype = ctypes.c_int
     L.d4g_debug_cl_tree_lengths.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    # (d4g_debug_pack_header, a test hook, gets its prototype where the tests call it — tests/abi_calls.py: a build of the
+    # library from before the hook existed, as an A/B series loads through D4G_LIB, has no such symbol to declare)
     L.d4g_compress.restype = ctypes.c_int
     L.d4g_compress.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]

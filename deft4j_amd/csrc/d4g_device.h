@@ -123,6 +123,19 @@ D4G_DEV int wg_max_i32(int v, long long* red) {
     return (int)red[16];
 }
 
+// The memos' and the fused tables' position-keyed hashes: the sum over positions i of mix(i, word at i) names a set of
+// words, and changes by mix(i, new) - mix(i, old) when one word does.  Two independent mixes: one finds, one confirms.
+D4G_DEV unsigned long long d4g_mix1(unsigned long long i, unsigned long long w) {
+    unsigned long long x = (w + 1) * 0x9e3779b97f4a7c15ULL + (i + 1) * 0xbf58476d1ce4e5b9ULL;
+    x ^= x >> 29; x *= 0x94d049bb133111ebULL; x ^= x >> 32;
+    return x;
+}
+D4G_DEV unsigned long long d4g_mix2(unsigned long long i, unsigned long long w) {
+    unsigned long long y = (w + 0x632be59bd9b4e019ULL) * ((i + 7) * 0xd6e8feb86659fd93ULL | 1ULL);
+    y ^= y >> 31; y *= 0xff51afd7ed558ccdULL; y ^= y >> 33;
+    return y;
+}
+
 // ---------------------------------------------------------------------------------------
 // Huffman tree with exact JDK PriorityQueue tie-breaking and the reference's depth limiter.
 // Reproduces HuffmanTree(freq, limit).getTable().codeLen — B/huffman/HuffmanTree.java:36-128
@@ -1057,20 +1070,6 @@ __device__ void d4g_pack_kinds(int v, int r, int flags, Rep rep, Lit lit) {
     }
     lits += r;
     if (lits) lit(lits);
-}
-
-// Runs of the concatenated code lengths (lit then dist; runs may span the boundary — A.4).
-// len(i) reads combined length i.  Calls body(value, runLength) per run.
-template <typename LenFn, typename Body>
-__device__ void d4g_for_runs(int n, LenFn len, Body body) {
-    int last = len(0), run = 1;
-    for (int i = 1; i <= n; i++) {
-        if (i < n && len(i) == last) { run++; }
-        else {
-            body(last, run);
-            if (i < n) { last = len(i); run = 1; }
-        }
-    }
 }
 
 // pair encode/decode (see d4g_types.h)

@@ -284,16 +284,6 @@ __shared__ D4FLds d4fLds;
 // ---------------------------------------------------------------------------------------
 // small helpers
 // ---------------------------------------------------------------------------------------
-D4G_DEV unsigned long long d4f_mix1(unsigned long long i, unsigned long long w) {
-    unsigned long long x = (w + 1) * 0x9e3779b97f4a7c15ULL + (i + 1) * 0xbf58476d1ce4e5b9ULL;
-    x ^= x >> 29; x *= 0x94d049bb133111ebULL; x ^= x >> 32;
-    return x;
-}
-D4G_DEV unsigned long long d4f_mix2(unsigned long long i, unsigned long long w) {
-    unsigned long long y = (w + 0x632be59bd9b4e019ULL) * ((i + 7) * 0xd6e8feb86659fd93ULL | 1ULL);
-    y ^= y >> 31; y *= 0xff51afd7ed558ccdULL; y ^= y >> 33;
-    return y;
-}
 D4G_DEV uint64_t* d4f_mask(const D4GCtx& c, const D4GBlock& b, int id) { return mask_ptr(c, b, id); }
 D4G_DEV uint64_t* d4f_eset(const D4GCtx& c, const D4GBlock& b, int code, int prune) { return mask_ptr(c, b, D4F_MAXM + 2 * code + (prune ? 1 : 0)); }
 D4G_DEV long long d4f_slot_size(const D4FSlot& s) {
@@ -975,7 +965,7 @@ D4F_TASK void d4f_apply_task(int idx) {
                 if (w < nWords) {
                     const uint64_t o = mw[j], n = o | ew[j];
                     O[w] = n;
-                    if (n != o) { h1 += d4f_mix1(w, n) - d4f_mix1(w, o); h2 += d4f_mix2(w, n) - d4f_mix2(w, o); }
+                    if (n != o) { h1 += d4g_mix1(w, n) - d4g_mix1(w, o); h2 += d4g_mix2(w, n) - d4g_mix2(w, o); }
                 }
             }
             h1 = (unsigned long long)wave_sum_i64((long long)h1) + F.maskH1[m];
@@ -1024,7 +1014,7 @@ D4F_TASK void d4f_apply_task(int idx) {
         for (int w = lane; w < nWords; w += 64) {
             const uint64_t o = M[w], n = o | E[w];
             O[w] = n;
-            if (n != o) { h1 += d4f_mix1(w, n) - d4f_mix1(w, o); h2 += d4f_mix2(w, n) - d4f_mix2(w, o); }
+            if (n != o) { h1 += d4g_mix1(w, n) - d4g_mix1(w, o); h2 += d4g_mix2(w, n) - d4g_mix2(w, o); }
         }
         h1 = (unsigned long long)wave_sum_i64((long long)h1) + F.maskH1[m];
         h2 = (unsigned long long)wave_sum_i64((long long)h2) + F.maskH2[m];
@@ -1213,7 +1203,7 @@ D4F_TASK void d4f_least_task(int idx) {
                 const uint64_t o = mw[j], n = o | bw[j];
                 O[w] = n;
                 cnt += __popcll(n & ~o);
-                if (n != o) { h1 += d4f_mix1(w, n) - d4f_mix1(w, o); h2 += d4f_mix2(w, n) - d4f_mix2(w, o); }
+                if (n != o) { h1 += d4g_mix1(w, n) - d4g_mix1(w, o); h2 += d4g_mix2(w, n) - d4g_mix2(w, o); }
             }
         }
         cnt = wave_sum_i32(cnt);
@@ -1311,7 +1301,7 @@ D4F_TASK void d4f_least_task(int idx) {
         const uint64_t o = M[w], n = o | bm[w];
         O[w] = n;
         cnt += __popcll(n & ~o);
-        if (n != o) { h1 += d4f_mix1(w, n) - d4f_mix1(w, o); h2 += d4f_mix2(w, n) - d4f_mix2(w, o); }
+        if (n != o) { h1 += d4g_mix1(w, n) - d4g_mix1(w, o); h2 += d4g_mix2(w, n) - d4g_mix2(w, o); }
     }
     cnt = wave_sum_i32(cnt);
     h1 = (unsigned long long)wave_sum_i64((long long)h1) + F.maskH1[m];
@@ -1323,9 +1313,9 @@ D4F_TASK void d4f_least_task(int idx) {
 }
 
 // ---------------------------------------------------------------------------------------
-// Header pieces by one wave (the workgroup forms are in d4g_ops.h)
+// Header pieces by one wave: the forms of d4g_header.h on a task's scratch
 // ---------------------------------------------------------------------------------------
-// code-length code of clFreq — Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134
+// code-length code of clFreq — Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134: the fused executor's code-length-tree step
 D4G_DEV int d4f_wave_cl_tree(unsigned char* treeMem, const uint32_t* clFreq, uint8_t* clLen) {
     TreeMem<uint32_t, uint8_t, 20> tm;
     tm.carve(treeMem, 1);
@@ -1336,117 +1326,22 @@ D4G_DEV int d4f_wave_cl_tree(unsigned char* treeMem, const uint32_t* clFreq, uin
     d4g_wave_sync();
     return err;
 }
-// trailing zero code-length-code lengths in transmit order — removeDynHeaderTrailingZeroLenCodelens, :335-364
-D4G_DEV int d4f_wave_trim(const uint8_t* clLen, int nCl) {
-    const int lane = threadIdx.x & 63;
-    const bool nz = lane < nCl && lane < 19 && clLen[D4G_CL_ORDER[lane]] != 0;
-    const unsigned long long m = d4g_ballot(nz);
-    return m ? 64 - __clzll((long long)m) : nCl;
-}
-// rewriteHeader with the default flags — DeflateBlockHuffman.java:484-577 (wg_rewrite_header's wave part): pairs,
-// code-length code, size; nCl trimmed.  lens = litLen[288] + distLen[32].
+// rewriteHeader with the default flags — DeflateBlockHuffman.java:484-577: pairs, code-length code, size; nCl trimmed.
+// lens = litLen[288] + distLen[32].
 __device__ __forceinline__ int d4f_wave_default_header(const uint8_t* lens, int nLit, int nDist, uint16_t* pairs, uint32_t* clFreq, uint8_t* clLen,
                                                         unsigned char* treeMem, int& nPairsOut, int& nClOut, int& bitsOut) {
-    const int lane = threadIdx.x & 63;
-    const int flags = F_DEFAULT;
-    if (lane < 20) clFreq[lane] = 0;
-    d4g_wave_sync();
-    const int n = nLit + nDist;
-    auto len = [&](int i) { return i < nLit ? (int)lens[i] : (int)lens[D4G_NLIT + i - nLit]; };
-    constexpr int NCH = (D4G_NLIT + D4G_NDIST) / 64;
-    unsigned long long sm[NCH];
-    int v[NCH];
-#pragma unroll
-    for (int ch = 0; ch < NCH; ch++) {
-        int i = ch * 64 + lane;
-        v[ch] = i < n ? len(i) : -1;
-        int pv = (i > 0 && i < n) ? len(i - 1) : -2;
-        sm[ch] = d4g_ballot(i < n && v[ch] != pv);
-    }
-    int base = 0;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ch++) {
-        int i = ch * 64 + lane;
-        bool start = (sm[ch] >> lane) & 1;
-        int cnt = 0, run = 0;
-        if (start) {
-            int nx = -1;
-            unsigned long long m = lane == 63 ? 0ULL : (sm[ch] >> (lane + 1));
-            if (m) nx = i + __ffsll((long long)m);
-#pragma unroll
-            for (int c2 = ch + 1; c2 < NCH; c2++)
-                if (nx < 0 && sm[c2]) nx = c2 * 64 + __ffsll((long long)sm[c2]) - 1;
-            if (nx < 0) nx = n;
-            run = nx - i;
-            d4g_pack_run(v[ch], run, flags, [&](int, int, int) { cnt++; });
-        }
-        int incl = cnt;
-        for (int d = 1; d < 64; d <<= 1) {
-            int o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        int off = base + incl - cnt;
-        if (start)
-            d4g_pack_run(v[ch], run, flags, [&](int sym, int r, int value) {
-                pairs[off++] = pair_encode(sym, r, value);
-                atomicAdd(&clFreq[sym], 1u);
-            });
-        base += __shfl(incl, 63);
-    }
-    d4g_wave_sync();
-    const int err = d4f_wave_cl_tree(treeMem, clFreq, clLen);
-    int hbl = 0;
-    if (lane < 19) hbl = (int)clFreq[lane] * (clLen[lane] + (lane >= 16 ? pair_extra_bits(lane) : 0));
-    int hb = 5 + 5 + 4 + 19 * 3 + wave_sum_i32(hbl);
-    const int nCl = d4f_wave_trim(clLen, 19);
-    hb -= 3 * (19 - nCl);
-    nPairsOut = base; nClOut = nCl; bitsOut = hb;
-    return err;
+    d4g_wave_clear_cl_freq(clFreq);
+    return d4g_wave_pack_header(nLit + nDist, [&](int i) { return i < nLit ? (int)lens[i] : (int)lens[D4G_NLIT + i - nLit]; }, F_DEFAULT, pairs, clFreq, clLen,
+                                [&](const uint32_t* f, uint8_t* l) { return d4f_wave_cl_tree(treeMem, f, l); }, nPairsOut, nClOut, bitsOut);
 }
-// replaceRLERunsWithLiteralsIfSmaller — :321-332: returns the bits saved
-D4G_DEV int d4f_wave_replace_runs(uint16_t* pairs, int nPairs, const uint8_t* clLen, bool prune) {
-    const int lane = threadIdx.x & 63;
-    int saved = 0;
-    for (int i = lane; i < nPairs; i += 64) {
-        uint16_t p = pairs[i];
-        if ((p & 31) >= 16 && !(p & D4G_PAIR_EXPANDED)) {
-            int sym, run, value;
-            pair_decode(p, sym, run, value);
-            int g = pair_replace_gain(sym, run, value, prune, [&](int s) { return (int)clLen[s]; });
-            if (g >= 0) { pairs[i] = p | D4G_PAIR_EXPANDED; saved += g; }
-        }
-    }
-    saved = wave_sum_i32(saved);
-    d4g_wave_sync();
-    return saved;
-}
-// recodeHeader — :579-629 (numCodelenLens deliberately not reset): new code-length code for the pairs as they stand
+// recodeHeader — :579-629: new code-length code for the pairs as they stand
 D4G_DEV int d4f_wave_recode_header(D4FHdrScr& H) {
-    const int lane = threadIdx.x & 63;
-    if (lane < 20) H.clFreq[lane] = 0;
+    int nCl, hb;
+    d4g_wave_clear_cl_freq(H.clFreq);
+    const int err = d4g_wave_recode_header(H.pairs, H.nPairs, H.clFreq, H.clLen, H.nCl,
+                                           [&](const uint32_t* f, uint8_t* l) { return d4f_wave_cl_tree(H.tree, f, l); }, nCl, hb);
     d4g_wave_sync();
-    const int np = H.nPairs;
-    for (int i = lane; i < np; i += 64) {
-        int sym, run, value;
-        uint16_t p = H.pairs[i];
-        pair_decode(p, sym, run, value);
-        if (p & D4G_PAIR_EXPANDED) atomicAdd(&H.clFreq[value], (unsigned)run);
-        else atomicAdd(&H.clFreq[sym], 1u);
-    }
-    d4g_wave_sync();
-    const int err = d4f_wave_cl_tree(H.tree, H.clFreq, H.clLen);
-    const int nCl = d4f_wave_trim(H.clLen, H.nCl);
-    int hbl = 0;
-    for (int i = lane; i < np; i += 64) {
-        int sym, run, value;
-        uint16_t p = H.pairs[i];
-        pair_decode(p, sym, run, value);
-        if (p & D4G_PAIR_EXPANDED) hbl += run * H.clLen[value];
-        else hbl += H.clLen[sym] + (sym >= 16 ? pair_extra_bits(sym) : 0);
-    }
-    const int hb = 5 + 5 + 4 + 3 * nCl + wave_sum_i32(hbl);
-    d4g_wave_sync();
-    if (lane == 0) { H.nCl = nCl; H.bits = hb; }
+    if ((threadIdx.x & 63) == 0) { H.nCl = nCl; H.bits = hb; }
     d4g_wave_sync();
     return err;
 }
@@ -1469,13 +1364,13 @@ D4F_TASK void d4f_hdr_task(int idx) {
     d4g_wave_sync();
     int err = 0;
     if (op == D4F_H_OPT) {
-        const int n = d4f_wave_trim(H.clLen, H.nCl);
-        const int saved = d4f_wave_replace_runs(H.pairs, nPairs, H.clLen, false);
+        const int n = d4g_wave_trim(H.clLen, H.nCl);
+        const int saved = d4g_wave_replace_runs(H.pairs, nPairs, H.clLen, false);
         if (lane == 0) { H.bits -= 3 * (H.nCl - n) + saved; H.nCl = n; }
     } else if (op == D4F_H_POST) {
         err = d4f_wave_recode_header(H);
     } else {
-        (void)d4f_wave_replace_runs(H.pairs, nPairs, H.clLen, true);   // (the bits are summed again by recodeHeader)
+        (void)d4g_wave_replace_runs(H.pairs, nPairs, H.clLen, true);   // (the bits are summed again by recodeHeader)
         err = d4f_wave_recode_header(H);
     }
     d4g_wave_sync();
@@ -1588,7 +1483,7 @@ D4F_TASK void d4f_tree_probe(int slotIdx) {
     const int lane = threadIdx.x & 63;
     unsigned long long h = 0;
     const uint32_t* lw = (const uint32_t*)T.lens;
-    for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) h += d4f_mix1(i, lw[i]);
+    for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) h += d4g_mix1(i, lw[i]);
     h = (unsigned long long)wave_sum_i64((long long)h) + (unsigned long long)T.nLit * 0x100000001b3ULL + ((unsigned long long)T.nDist << 48);
     if (h == 0) h = 1;
     uint32_t k;
@@ -1707,7 +1602,8 @@ D4F_TASK void d4f_tree_publish(int slotIdx, long long* stats) {
 }
 
 // ---------------------------------------------------------------------------------------
-// Header search of one code (one wave): the 56 optimiseBlockDynBlock candidates — see d4g_exec_hdr_search
+// Header search of one code (one wave): the 56 optimiseBlockDynBlock candidates (d4g_hdr_candidate_body, d4g_ops.h) on the
+// run list of d4g_wave_hs_runs (d4g_header.h)
 // ---------------------------------------------------------------------------------------
 // Returns the number of candidates whose code-length tree needed the depth limiter.
 D4F_TASK int d4f_hs_task(int slotIdx, int code) {
@@ -1722,48 +1618,8 @@ D4F_TASK int d4f_hs_task(int slotIdx, int code) {
     for (int i = lane; i < (D4G_NLIT + D4G_NDIST) / 4; i += 64) ((uint32_t*)H.lens)[i] = ((const uint32_t*)cd.lens)[i];
     d4g_wave_sync();
     for (int i = lane; i < D4G_NLIT + D4G_NDIST; i += 64) comb[i] = i >= n ? 0 : i < nLit ? H.lens[i] : H.lens[D4G_NLIT + i - nLit];
-    if (lane < 20) H.baseFreq[lane] = 0;
     d4g_wave_sync();
-    {
-        constexpr int NCH = (D4G_NLIT + D4G_NDIST) / 64;
-        unsigned long long sm[NCH];
-        int v[NCH];
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            int i = ch * 64 + lane;
-            v[ch] = i < n ? (int)comb[i] : -1;
-            int pv = (i > 0 && i < n) ? (int)comb[i - 1] : -2;
-            sm[ch] = d4g_ballot(i < n && v[ch] != pv);
-        }
-        int ncx = 0;
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            int i = ch * 64 + lane;
-            bool start = (sm[ch] >> lane) & 1;
-            int run = 0;
-            if (start) {
-                int nx = -1;
-                unsigned long long m = lane == 63 ? 0ULL : (sm[ch] >> (lane + 1));
-                if (m) nx = i + __ffsll((long long)m);
-#pragma unroll
-                for (int c2 = ch + 1; c2 < NCH; c2++)
-                    if (nx < 0 && sm[c2]) nx = c2 * 64 + __ffsll((long long)sm[c2]) - 1;
-                if (nx < 0) nx = n;
-                run = nx - i;
-            }
-            bool simple = start && (v[ch] != 0 ? run <= 3 : run <= 2);
-            bool cx = start && !simple;
-            if (simple) atomicAdd(&H.baseFreq[v[ch]], (unsigned)run);
-            unsigned long long cm = d4g_ballot(cx);
-            if (cx) {
-                int idx = ncx + __popcll(cm & ((1ULL << lane) - 1));
-                H.runV[idx] = (uint8_t)v[ch];
-                H.runL[idx] = (uint16_t)run;
-            }
-            ncx += __popcll(cm);
-        }
-        if (lane == 0) H.nRuns = ncx;
-    }
+    d4g_wave_hs_runs(H, comb, n);
     d4g_wave_sync();
     long long key = D4G_KEY_NONE;
     bool fellBack = false;
@@ -1877,7 +1733,7 @@ D4F_TASK void d4f_cl_work() {
                 if (O && w < nWords) {
                     const uint64_t o = mw[j], n = o | xw[j];
                     O[w] = n;
-                    if (n != o) { h1Lane += d4f_mix1(w, n) - d4f_mix1(w, o); h2Lane += d4f_mix2(w, n) - d4f_mix2(w, o); }
+                    if (n != o) { h1Lane += d4g_mix1(w, n) - d4g_mix1(w, o); h2Lane += d4g_mix2(w, n) - d4g_mix2(w, o); }
                 }
             }
             d4f_wave_for_bits(d, rf + (size_t)w0 * 64, W.queue, [&](const uint4& rv) {
@@ -1932,7 +1788,7 @@ D4F_TASK void d4f_cl_work() {
                         const uint64_t o = mw[j], n = o | xw[j];
                         O[w] = n;
                         cntLane += __popcll(n & ~o);
-                        if (n != o) { h1Lane += d4f_mix1(w, n) - d4f_mix1(w, o); h2Lane += d4f_mix2(w, n) - d4f_mix2(w, o); }
+                        if (n != o) { h1Lane += d4g_mix1(w, n) - d4g_mix1(w, o); h2Lane += d4g_mix2(w, n) - d4g_mix2(w, o); }
                     }
                 }
                 // what the already expanded records of the bin contributed to the static row (they were moved earlier)
@@ -2244,7 +2100,7 @@ D4F_TASK bool d4f_round_setup(const D4GOp* ops0, const D4GOp* ops1, int nOps0, i
         const uint32_t* cw = (const uint32_t*)cur->litLen;
         const uint32_t w0 = cw[lane], w1 = lane < 16 ? cw[64 + lane] : 0u;
         const int nLit0 = cur->nLit, nDist0 = cur->nDist;
-        unsigned long long h = d4f_mix1(lane, w0) + (lane < 16 ? d4f_mix1(64 + lane, w1) : 0ull);
+        unsigned long long h = d4g_mix1(lane, w0) + (lane < 16 ? d4g_mix1(64 + lane, w1) : 0ull);
         h = (unsigned long long)wave_sum_i64((long long)h) + (unsigned long long)nLit0 * 0x100000001b3ULL + ((unsigned long long)nDist0 << 48) +
             (curType == D4G_DYNAMIC ? 0ull : 0x9e3779b97f4a7c15ULL);
         if (h == 0) h = 1;

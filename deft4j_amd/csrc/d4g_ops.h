@@ -1,11 +1,11 @@
 // d4g_ops.h — workgroup-cooperative operations on one candidate state held in LDS, and
-// the kernels that execute the candidate-search program.  See d4g_device.h for the pieces.
+// the kernels that execute the candidate-search program.  See d4g_device.h for the pieces and d4g_header.h for the
+// header operations' one-wave forms.
 #pragma once
-#include "d4g_device.h"
+#include "d4g_header.h"
 
 #ifdef D4G_PROFILE_OPS
 __device__ unsigned long long d4g_dbg_pass[4];  // computed replace passes: lookup cycles, loop cycles, count, records
-__device__ unsigned long long d4g_dbg_hdr[4];   // profile builds: header rewrite sections (RLE, code-length tree, tail), count
 #endif
 
 // Header-search memo.  The 56 header candidates of a state depend only on its code lengths, and most of a block's
@@ -237,23 +237,13 @@ __device__ __forceinline__ int wg_passmemo_lookup(D4GLds* L, const D4GCtx& c, co
     D4GState* S = &L->st;
     entry = nullptr;
     if (!c.passMemo || b.passMemo < 0) return 0;
-    auto mix1 = [](unsigned long long i, unsigned long long w) {
-        unsigned long long x = (w + 1) * 0x9e3779b97f4a7c15ULL + (i + 1) * 0xbf58476d1ce4e5b9ULL;
-        x ^= x >> 29; x *= 0x94d049bb133111ebULL; x ^= x >> 32;
-        return x;
-    };
-    auto mix2 = [](unsigned long long i, unsigned long long w) {
-        unsigned long long y = (w + 0x632be59bd9b4e019ULL) * ((i + 7) * 0xd6e8feb86659fd93ULL | 1ULL);
-        y ^= y >> 31; y *= 0xff51afd7ed558ccdULL; y ^= y >> 33;
-        return y;
-    };
     unsigned long long a1 = 0, a2 = 0;
     const uint32_t* lw = (const uint32_t*)S->litLen;   // litLen[288] + distLen[32], contiguous
-    for (int i = threadIdx.x; i < (D4G_NLIT + D4G_NDIST) / 4; i += blockDim.x) { a1 += mix1(i, lw[i]); a2 += mix2(i, lw[i]); }
+    for (int i = threadIdx.x; i < (D4G_NLIT + D4G_NDIST) / 4; i += blockDim.x) { a1 += d4g_mix1(i, lw[i]); a2 += d4g_mix2(i, lw[i]); }
     for (int w = threadIdx.x; w < (int)b.maskWords; w += blockDim.x) {
         unsigned long long m = d4g_ld_agent(maskIn + w);
-        a1 += mix1(1000 + w, m);
-        a2 += mix2(1000 + w, m);
+        a1 += d4g_mix1(1000 + w, m);
+        a2 += d4g_mix2(1000 + w, m);
     }
     long long s1, s2;
     wg_sum2_i64((long long)a1, (long long)a2, L->red, s1, s2);
@@ -727,54 +717,36 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
 // ---------------------------------------------------------------------------------------
 // Header operations on the LDS state
 // ---------------------------------------------------------------------------------------
-// code-length-code tree from L->clFreq — Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134
-__device__ __forceinline__ void t0_build_cl_tree(D4GLds* L) {
-    D4GState* S = &L->st;
+// code-length code of clFreq — Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134 — by one lane: what
+// w0_build_cl_tree runs under D4G_SERIAL_TREES
+D4G_DEV int t0_build_cl_tree(unsigned char* treeMem, const uint32_t* clFreq, uint8_t* clLen) {
     TreeMem<uint32_t, uint8_t, 20> tm;
-    tm.carve(L->treeCl, 1);
-    for (int i = 0; i < 19; i++) S->clLen[i] = 0;
-    int err = d4g_build_tree(tm, 1, 0, 19, 7, [&](int i) { return (unsigned)L->clFreq[i]; },
-                             [&](int v, int len) { S->clLen[v] = (uint8_t)len; });
-    if (err) S->flags |= 0x100;
+    tm.carve(treeMem, 1);
+    for (int i = 0; i < 19; i++) clLen[i] = 0;
+    return d4g_build_tree(tm, 1, 0, 19, 7, [&](int i) { return (unsigned)clFreq[i]; }, [&](int v, int len) { clLen[v] = (uint8_t)len; });
 }
 
-// the same by all lanes of wave 0
-__device__ __forceinline__ void w0_build_cl_tree(D4GLds* L) {
-    D4GState* S = &L->st;
+// the same by all lanes of wave 0: the level executor's code-length-tree step for the forms of d4g_header.h
+D4G_DEV int w0_build_cl_tree(unsigned char* treeMem, const uint32_t* clFreq, uint8_t* clLen) {
+    int err = 0;
 #ifndef D4G_SERIAL_TREES
     TreeMem<uint32_t, uint8_t, 20> tm;
-    tm.carve(L->treeCl, 1);
-    const int lane = threadIdx.x & 63;
-    if (lane < 19) S->clLen[lane] = 0;
-    int err = d4g_build_tree_wave<1>(tm, 19, 7, [&](int i) { return (unsigned)L->clFreq[i]; },
-                                     [&](int v, int len) { S->clLen[v] = (uint8_t)len; });
-    if (err && lane == 0) S->flags |= 0x100;
+    tm.carve(treeMem, 1);
+    if ((threadIdx.x & 63) < 19) clLen[threadIdx.x & 63] = 0;
+    err = d4g_build_tree_wave<1>(tm, 19, 7, [&](int i) { return (unsigned)clFreq[i]; }, [&](int v, int len) { clLen[v] = (uint8_t)len; });
 #else
-    if ((threadIdx.x & 63) == 0) t0_build_cl_tree(L);
+    if ((threadIdx.x & 63) == 0) err = t0_build_cl_tree(treeMem, clFreq, clLen);
 #endif
     d4g_wave_sync();
+    return err;
 }
 
-// removeTrailingHeaderCodes — DeflateBlockHuffman.java:366-370 (thread 0)
-__device__ __forceinline__ void t0_remove_trailing_header_codes(D4GState* S) {
-    if (S->type != D4G_DYNAMIC) return;
-    int n = trim_codelens(S->nCl, [&](int s) { return (int)S->clLen[s]; });
-    long long saved = 3LL * (S->nCl - n);
-    S->nCl = n;
-    S->sizeBits -= saved;
-    S->hdrBits -= saved;
-}
-
-// removeTrailingHeaderCodes by all lanes of wave 0: trim_codelens drops trailing zero lengths (in code-length
-// order) one at a time while a non-zero one exists, i.e. it keeps everything up to the last non-zero length.
+// removeTrailingHeaderCodes — DeflateBlockHuffman.java:366-370, by all lanes of wave 0
 __device__ __forceinline__ void w0_remove_trailing_header_codes(D4GState* S) {
     if (S->type != D4G_DYNAMIC) return;
-    const int lane = threadIdx.x & 63;
     const int nCl = S->nCl;
-    bool nz = lane < nCl && lane < 19 && S->clLen[D4G_CL_ORDER[lane]] != 0;
-    unsigned long long m = d4g_ballot(nz);
-    int n = m ? 64 - __clzll((long long)m) : nCl;
-    if (lane == 0) {
+    const int n = d4g_wave_trim(S->clLen, nCl);
+    if ((threadIdx.x & 63) == 0) {
         long long saved = 3LL * (nCl - n);
         S->nCl = n;
         S->sizeBits -= saved;
@@ -782,120 +754,44 @@ __device__ __forceinline__ void w0_remove_trailing_header_codes(D4GState* S) {
     }
 }
 
-// rewriteHeader — DeflateBlockHuffman.java:484-577 (HuffmanTable.packCodeLengths :100-186 inside).  All threads.
-// Wave 0 finds the runs of the concatenated code lengths with ballots; the lane at each run start packs
-// that run (the pair count first, then the pairs at their prefix-summed position).  Thread 0 finishes with
-// the code-length code and the header size.
+// rewriteHeader — DeflateBlockHuffman.java:484-577.  All threads call; wave 0 works (d4g_wave_pack_header).
 // (forced inline: inside a kernel the compiler then knows L is LDS and drops the generic-pointer checks)
 __device__ __forceinline__ void wg_rewrite_header(D4GLds* L, int flags) {
     D4GState* S = &L->st;
     __syncthreads();
-#ifdef D4G_PROFILE_OPS
-    long long r0 = d4g_clock_drained(), r1 = 0, r2 = 0;
-#endif
     if (S->type != D4G_DYNAMIC) return;
     if (threadIdx.x < 20) L->clFreq[threadIdx.x] = 0;
     __syncthreads();
     if (threadIdx.x < 64) {
         D4G_SETPRIO(3);   // the workgroup's other waves wait for this one
-        const int lane = threadIdx.x;
-        const int nLit = S->nLit, n = nLit + S->nDist;
-        auto len = [&](int i) { return i < nLit ? (int)S->litLen[i] : (int)S->distLen[i - nLit]; };
-        constexpr int NCH = (D4G_NLIT + D4G_NDIST) / 64;  // 5 chunks of 64 code lengths
-        unsigned long long sm[NCH];
-        int v[NCH];
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            int i = ch * 64 + lane;
-            v[ch] = i < n ? len(i) : -1;
-            int pv = (i > 0 && i < n) ? len(i - 1) : -2;
-            sm[ch] = d4g_ballot(i < n && v[ch] != pv);   // runs may span the literal/distance boundary — A.4
-        }
-        int base = 0;
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            int i = ch * 64 + lane;
-            bool start = (sm[ch] >> lane) & 1;
-            int cnt = 0, run = 0;
-            if (start) {
-                int nx = -1;
-                unsigned long long m = lane == 63 ? 0ULL : (sm[ch] >> (lane + 1));
-                if (m) nx = i + __ffsll((long long)m);
-#pragma unroll
-                for (int c2 = ch + 1; c2 < NCH; c2++)
-                    if (nx < 0 && sm[c2]) nx = c2 * 64 + __ffsll((long long)sm[c2]) - 1;
-                if (nx < 0) nx = n;
-                run = nx - i;
-                d4g_pack_run(v[ch], run, flags, [&](int, int, int) { cnt++; });
-            }
-            int incl = cnt;
-            for (int d = 1; d < 64; d <<= 1) {
-                int o = __shfl_up(incl, d);
-                if (lane >= d) incl += o;
-            }
-            int off = base + incl - cnt;
-            if (start)
-                d4g_pack_run(v[ch], run, flags, [&](int sym, int r, int value) {
-                    S->pairs[off++] = pair_encode(sym, r, value);
-                    atomicAdd(&L->clFreq[sym], 1u);
-                });
-            base += __shfl(incl, 63);
-        }
-        if (lane == 0) S->nPairs = base;
-#ifdef D4G_PROFILE_OPS
-        r1 = d4g_clock_drained();
-#endif
-        // code-length code (Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134) and the header's size
-        w0_build_cl_tree(L);
-#ifdef D4G_PROFILE_OPS
-        r2 = d4g_clock_drained();
-#endif
-        int hbl = 0;
-        if (lane < 19) hbl = (int)L->clFreq[lane] * (S->clLen[lane] + (lane >= 16 ? pair_extra_bits(lane) : 0));
-        long long hb = 5 + 5 + 4 + 19 * 3 + wave_sum_i32(hbl);
-        if (lane == 0) {
+        int nCl, hb;
+        const int nLit = S->nLit;
+        const int err = d4g_wave_pack_header(nLit + S->nDist, [&](int i) { return i < nLit ? (int)S->litLen[i] : (int)S->distLen[i - nLit]; },
+                                             flags, S->pairs, L->clFreq, S->clLen,
+                                             [&](const uint32_t* f, uint8_t* l) { return w0_build_cl_tree(L->treeCl, f, l); }, S->nPairs, nCl, hb);
+        if (threadIdx.x == 0) {
+            if (err) S->flags |= 0x100;
+            S->nCl = nCl;
             S->sizeBits += hb - S->hdrBits;
             S->hdrBits = hb;
-            S->nCl = 19;
         }
-        d4g_wave_sync();
-        w0_remove_trailing_header_codes(S);
         D4G_SETPRIO(D4G_BASE_PRIO);
-#ifdef D4G_PROFILE_OPS
-        if (lane == 0) {
-            atomicAdd(&d4g_dbg_hdr[0], (unsigned long long)(r1 - r0));
-            atomicAdd(&d4g_dbg_hdr[1], (unsigned long long)(r2 - r1));
-            atomicAdd(&d4g_dbg_hdr[2], (unsigned long long)(d4g_clock_drained() - r2));
-            atomicAdd(&d4g_dbg_hdr[3], 1ULL);
-        }
-#endif
     }
     __syncthreads();
 }
 
-// replaceRLERunsWithLiteralsIfSmaller — DeflateBlockHuffman.java:321-332.  All threads.
+// replaceRLERunsWithLiteralsIfSmaller — DeflateBlockHuffman.java:321-332.  All threads call; wave 0 works.
 __device__ __forceinline__ void wg_replace_rle_runs(D4GLds* L, bool prune) {
     D4GState* S = &L->st;
-    long long saved = 0;
     __syncthreads();
-    if (S->type == D4G_DYNAMIC) {
-        for (int i = threadIdx.x; i < S->nPairs; i += blockDim.x) {
-            uint16_t p = S->pairs[i];
-            if ((p & 31) >= 16 && !(p & D4G_PAIR_EXPANDED)) {
-                int sym, run, value;
-                pair_decode(p, sym, run, value);
-                int g = pair_replace_gain(sym, run, value, prune, [&](int s) { return (int)S->clLen[s]; });
-                if (g >= 0) { S->pairs[i] = p | D4G_PAIR_EXPANDED; saved += g; }
-            }
-        }
+    if (S->type == D4G_DYNAMIC && threadIdx.x < 64) {
+        const int saved = d4g_wave_replace_runs(S->pairs, S->nPairs, S->clLen, prune);
+        if (threadIdx.x == 0) { S->sizeBits -= saved; S->hdrBits -= saved; }
     }
-    saved = wg_sum_i64(saved, L->red);
-    if (threadIdx.x == 0) { S->sizeBits -= saved; S->hdrBits -= saved; }
     __syncthreads();
 }
 
-// recodeHeader — DeflateBlockHuffman.java:579-629 (numCodelenLens deliberately not reset).  Wave 0: the pairs are
-// counted and priced 64 at a time, the code-length tree is built by the wave.
+// recodeHeader — DeflateBlockHuffman.java:579-629.  All threads call; wave 0 works (d4g_wave_recode_header).
 __device__ __forceinline__ void wg_recode_header(D4GLds* L) {
     D4GState* S = &L->st;
     __syncthreads();
@@ -903,32 +799,11 @@ __device__ __forceinline__ void wg_recode_header(D4GLds* L) {
     if (threadIdx.x < 20) L->clFreq[threadIdx.x] = 0;
     __syncthreads();
     if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        const int np = S->nPairs;
-        for (int i = lane; i < np; i += 64) {
-            int sym, run, value;
-            uint16_t p = S->pairs[i];
-            pair_decode(p, sym, run, value);
-            if (p & D4G_PAIR_EXPANDED) atomicAdd(&L->clFreq[value], (unsigned)run);
-            else atomicAdd(&L->clFreq[sym], 1u);
-        }
-        d4g_wave_sync();
-        w0_build_cl_tree(L);
-        // trim from the current count (trim_codelens: keep everything up to the last non-zero length)
-        const int nCl0 = S->nCl;
-        bool nz = lane < nCl0 && lane < 19 && S->clLen[D4G_CL_ORDER[lane]] != 0;
-        unsigned long long m = d4g_ballot(nz);
-        const int nCl = m ? 64 - __clzll((long long)m) : nCl0;
-        int hbl = 0;
-        for (int i = lane; i < np; i += 64) {
-            int sym, run, value;
-            uint16_t p = S->pairs[i];
-            pair_decode(p, sym, run, value);
-            if (p & D4G_PAIR_EXPANDED) hbl += run * S->clLen[value];
-            else hbl += S->clLen[sym] + (sym >= 16 ? pair_extra_bits(sym) : 0);
-        }
-        long long hb = 5 + 5 + 4 + 3LL * nCl + wave_sum_i32(hbl);
-        if (lane == 0) {
+        int nCl, hb;
+        const int err = d4g_wave_recode_header(S->pairs, S->nPairs, L->clFreq, S->clLen, S->nCl,
+                                               [&](const uint32_t* f, uint8_t* l) { return w0_build_cl_tree(L->treeCl, f, l); }, nCl, hb);
+        if (threadIdx.x == 0) {
+            if (err) S->flags |= 0x100;
             S->nCl = nCl;
             S->sizeBits += hb - S->hdrBits;
             S->hdrBits = hb;
@@ -977,13 +852,8 @@ __device__ __forceinline__ void wg_recode_huffman(D4GLds* L, D4GRecodeMemo* memo
     if (memoTab) {
         unsigned long long a1 = 0, a2 = 0;
         for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) {
-            unsigned long long w = (unsigned long long)S->hist[i] + 1;
-            unsigned long long x = w * 0x9e3779b97f4a7c15ULL + (unsigned long long)(i + 1) * 0xbf58476d1ce4e5b9ULL;
-            x ^= x >> 29; x *= 0x94d049bb133111ebULL; x ^= x >> 32;
-            unsigned long long y = (w + 0x632be59bd9b4e019ULL) * ((unsigned long long)(i + 7) * 0xd6e8feb86659fd93ULL | 1ULL);
-            y ^= y >> 31; y *= 0xff51afd7ed558ccdULL; y ^= y >> 33;
-            a1 += x;
-            a2 += y;
+            a1 += d4g_mix1(i, S->hist[i]);
+            a2 += d4g_mix2(i, (unsigned long long)S->hist[i] + 1);   // (the second hash has always taken the count plus one)
         }
         long long s1, s2;
         wg_sum2_i64((long long)a1, (long long)a2, L->red, s1, s2);
@@ -1342,18 +1212,7 @@ __global__ void __launch_bounds__(256) D4G_WAVES_PER_SIMD(D4G_STATE_WAVES) k_exe
 // 19 symbol counts and both code-length-code tables in registers; its trees are built in registers
 // (d4g_cl_tree_regs).  Only a tree deeper than 7 (the limiter) goes through LDS, one lane at a time.
 // ---------------------------------------------------------------------------------------
-// the limiter's code-length tree: 16-bit queue entries (weight < 1024, node id < 64), depths in the queue's memory
-typedef TreeMem<uint16_t, uint8_t, 20, 6, true> D4GHdrTree;
-struct D4GHdrLds {
-    alignas(16) uint8_t lens[D4G_NLIT + D4G_NDIST];
-    uint8_t runV[D4G_MAXPAIRS];
-    uint16_t runL[D4G_MAXPAIRS];
-    int nRuns;              // runs whose packing depends on the flags (the others are summed in baseFreq)
-    uint32_t baseFreq[20];  // code-length symbols contributed by the runs every candidate packs as plain literals
-    alignas(16) unsigned char tree[D4GHdrTree::bytes(1)];   // the one tree deeper than 7 being rebuilt
-    uint16_t fbFreq[19];
-    uint8_t fbLen[19];
-};
+// (the runs and the limiter's tree area: D4GHdrLds, d4g_header.h)
 
 // count += cnt for the wave-uniform symbol v < 16 of counts packed two per register
 D4G_DEV void d4g_cl_count(uint32_t (&f2)[8], int v, uint32_t cnt) {
@@ -1530,13 +1389,8 @@ __device__ void d4g_exec_hdr_search(D4GHdrLds& H, uint8_t* comb, const D4GCtx& c
     unsigned long long h1 = 0, h2 = 0;
     if (c.hsMemo) {
         for (int i = lane; i < n; i += 64) {
-            unsigned long long w = (unsigned long long)comb[i] + 1;
-            unsigned long long x = w * 0x9e3779b97f4a7c15ULL + (unsigned long long)(i + 1) * 0xbf58476d1ce4e5b9ULL;
-            x ^= x >> 29; x *= 0x94d049bb133111ebULL; x ^= x >> 32;
-            unsigned long long y = (w + 0x632be59bd9b4e019ULL) * ((unsigned long long)(i + 7) * 0xd6e8feb86659fd93ULL | 1ULL);
-            y ^= y >> 31; y *= 0xff51afd7ed558ccdULL; y ^= y >> 33;
-            h1 += x;
-            h2 += y;
+            h1 += d4g_mix1(i, comb[i]);
+            h2 += d4g_mix2(i, (unsigned long long)comb[i] + 1);   // (as in wg_recode_huffman)
         }
         h1 = (unsigned long long)wave_sum_i64((long long)h1) + (unsigned long long)nLit * 0x100000001b3ULL;
         h2 = (unsigned long long)wave_sum_i64((long long)h2) ^ ((unsigned long long)n << 40);
@@ -1587,52 +1441,8 @@ __device__ void d4g_exec_hdr_search(D4GHdrLds& H, uint8_t* comb, const D4GCtx& c
             return;
         }
     }
-    // Runs of the combined code lengths, found with ballots.  HuffmanTable.pack turns a run of up to three equal
-    // non-zero lengths (up to two zeros) into plain literals whatever the flags: those only add to the symbol
-    // counts, once for all 56 candidates.  The other runs are listed for the candidates' own packing (their
-    // order does not matter: candidates only count symbols and sum savings).
-    if (lane < 20) H.baseFreq[lane] = 0;
-    __syncthreads();
-    {
-        constexpr int NCH = (D4G_NLIT + D4G_NDIST) / 64;
-        unsigned long long sm[NCH];
-        int v[NCH];
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            int i = ch * 64 + lane;
-            v[ch] = i < n ? (int)comb[i] : -1;
-            int pv = (i > 0 && i < n) ? (int)comb[i - 1] : -2;
-            sm[ch] = d4g_ballot(i < n && v[ch] != pv);
-        }
-        int ncx = 0;
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            int i = ch * 64 + lane;
-            bool start = (sm[ch] >> lane) & 1;
-            int run = 0;
-            if (start) {
-                int nx = -1;
-                unsigned long long m = lane == 63 ? 0ULL : (sm[ch] >> (lane + 1));
-                if (m) nx = i + __ffsll((long long)m);
-#pragma unroll
-                for (int c2 = ch + 1; c2 < NCH; c2++)
-                    if (nx < 0 && sm[c2]) nx = c2 * 64 + __ffsll((long long)sm[c2]) - 1;
-                if (nx < 0) nx = n;
-                run = nx - i;
-            }
-            bool simple = start && (v[ch] != 0 ? run <= 3 : run <= 2);
-            bool cx = start && !simple;
-            if (simple) atomicAdd(&H.baseFreq[v[ch]], (unsigned)run);
-            unsigned long long cm = d4g_ballot(cx);
-            if (cx) {
-                int idx = ncx + __popcll(cm & ((1ULL << lane) - 1));
-                H.runV[idx] = (uint8_t)v[ch];
-                H.runL[idx] = (uint16_t)run;
-            }
-            ncx += __popcll(cm);
-        }
-        if (lane == 0) H.nRuns = ncx;
-    }
+    // the run list the 56 candidates pack from
+    d4g_wave_hs_runs(H, comb, n);
     __syncthreads();
 #ifdef D4G_PROFILE_OPS
     long long hs1 = d4g_clock_drained();

@@ -827,6 +827,50 @@ int d4g_debug_cl_tree_lengths(const uint32_t* freq, int n, uint32_t* lengths, in
     });
 }
 
+// rewriteHeader(flags) of one set of code lengths by one wave (d4g_wave_pack_header with the fused executor's tree step)
+__global__ void __launch_bounds__(64) k_debug_pack_header(const uint8_t* lens320, int nLit, int nDist, int flags, uint16_t* pairs, uint8_t* clLen19,
+                                                          int32_t* out4) {
+    __shared__ __attribute__((aligned(16))) uint8_t lens[D4G_NLIT + D4G_NDIST];
+    __shared__ uint16_t prs[D4G_MAXPAIRS];   // (a pair stands for at least one of the at most 320 lengths)
+    __shared__ uint32_t clFreq[20];
+    __shared__ uint8_t clLen[32];
+    __shared__ __attribute__((aligned(16))) unsigned char tree[TreeMem<uint32_t, uint8_t, 20>::bytes(1)];
+    const int lane = threadIdx.x & 63;
+    for (int i = lane; i < D4G_NLIT + D4G_NDIST; i += 64) lens[i] = lens320[i];
+    __syncthreads();
+    int nPairs, nCl, bits;
+    d4g_wave_clear_cl_freq(clFreq);
+    const int err = d4g_wave_pack_header(nLit + nDist, [&](int i) { return i < nLit ? (int)lens[i] : (int)lens[D4G_NLIT + i - nLit]; }, flags, prs, clFreq, clLen,
+                                         [&](const uint32_t* f, uint8_t* l) { return d4f_wave_cl_tree(tree, f, l); }, nPairs, nCl, bits);
+    __syncthreads();
+    for (int i = lane; i < nPairs; i += 64) pairs[i] = prs[i];
+    if (lane < 19) clLen19[lane] = clLen[lane];
+    if (lane == 0) { out4[0] = nPairs; out4[1] = nCl; out4[2] = bits; out4[3] = err; }
+}
+
+int d4g_debug_pack_header(const uint8_t* lens320, int nLit, int nDist, int flags, uint16_t* pairs, int32_t* nPairs, uint8_t* clLen19, int32_t* nCl,
+                          int32_t* bits) {
+    if (!lens320 || !pairs || !nPairs || !clLen19 || !nCl || !bits || nLit < 1 || nLit > D4G_NLIT || nDist < 1 || nDist > D4G_NDIST || flags < 0 ||
+        flags > 255)
+        return fail(D4G_ERR_ARG, "bad argument");
+    return api(nullptr, [&] {
+        RtScratch tmp;
+        uint8_t* dL = tmp.alloc<uint8_t>(D4G_NLIT + D4G_NDIST);
+        uint16_t* dP = tmp.alloc<uint16_t>(D4G_MAXPAIRS);
+        uint8_t* dC = tmp.alloc<uint8_t>(19);
+        int32_t* dO = tmp.alloc<int32_t>(4);
+        rt_h2d(dL, lens320, D4G_NLIT + D4G_NDIST);
+        RT_LAUNCH(k_debug_pack_header, 1, 64, dL, nLit, nDist, flags, dP, dC, dO);
+        int32_t o[4];
+        rt_d2h(o, dO, sizeof(o));
+        rt_d2h(pairs, dP, (size_t)o[0] * 2);
+        rt_d2h(clLen19, dC, 19);
+        tmp.release();
+        *nPairs = o[0]; *nCl = o[1]; *bits = o[2];
+        return o[3] ? fail(D4G_ERR_RUNTIME, "the code-length tree could not be built") : D4G_OK;
+    });
+}
+
 void d4g_free(void* p) { free(p); }
 
 }  // extern "C"
@@ -1469,7 +1513,6 @@ int d4g_debug_opstats(long long* out64) {
     return api(nullptr, [&] {
         rt_d2h(out64, engine().dOpStats, 64 * 8);
         (void)hipMemcpyFromSymbol(out64 + 56, HIP_SYMBOL(d4g_dbg_counters), 7 * 8);
-        (void)hipMemcpyFromSymbol(out64 + 28, HIP_SYMBOL(d4g_dbg_hdr), 4 * 8);
         (void)hipMemcpyFromSymbol(out64 + 16, HIP_SYMBOL(d4g_dbg_tree), 3 * 8);
         (void)hipMemcpyFromSymbol(out64 + 34, HIP_SYMBOL(d4g_dbg_pass), 4 * 8);
         return D4G_OK;

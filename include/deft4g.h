@@ -196,6 +196,12 @@ int d4g_debug_zopfli_code_lengths(const uint32_t* freq, int n, int maxbits, uint
 /* Test hook (tests/ only): the header search's 19-symbol code-length trees (limit 7) of n histograms freq[h * 19 + s]:
  * lengths[h * 19 + s], and limited[h] = 1 where the tree was deeper than 7 and went through the depth limiter. */
 int d4g_debug_cl_tree_lengths(const uint32_t* freq, int n, uint32_t* lengths, int32_t* limited);
+/* Test hook (tests/ only): rewriteHeader(flags) of the code lengths lens320 = literal/length[288] + distance[32], of which the
+ * first nLit and nDist count, packed by one wave as both search executors pack them: the RLE pairs (up to 320, encoded as
+ * in d4g_types.h), their count, the 19 code-length-code lengths, nCl after trimming and the header's size in bits.
+ * flags: bit 0 ohh, 1 use8, 2 use7, 3 alt8, 4 noRep, 5 noZRep, 6 noZRep2, 7 noRepZeros. */
+int d4g_debug_pack_header(const uint8_t* lens320, int nLit, int nDist, int flags, uint16_t* pairs, int32_t* nPairs, uint8_t* clLen19, int32_t* nCl,
+                          int32_t* bits);
 
 #define D4G_MODE_NONE 0
 #define D4G_MODE_CHEAP 1

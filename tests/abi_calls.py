@@ -71,6 +71,25 @@ def check_one_shot_entry_points(L, O, streams, merge):
     return kinds
 
 
+def pack_header_fn(L):
+    """d4g_debug_pack_header with its prototype (include/deft4g.h)"""
+    f = L.d4g_debug_pack_header
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p]
+    return f
+
+
+def pack_header_call(L, null=False):
+    """d4g_debug_pack_header on 257 + 1 lengths of 8 under the default flags (null: every pointer NULL) -> rc"""
+    if null:
+        return pack_header_fn(L)(None, 257, 1, 7, None, None, None, None, None)
+    lens = (ctypes.c_uint8 * 320)(*([8] * 320))
+    pairs, cl = (ctypes.c_uint16 * 320)(), (ctypes.c_uint8 * 19)()
+    n, ncl, bits = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    return pack_header_fn(L)(lens, 257, 1, 7, pairs, ctypes.byref(n), cl, ctypes.byref(ncl), ctypes.byref(bits))
+
+
 class Slots:
     """Poisoned result arrays of a one-shot call with n streams: the call must define every slot it is given."""
 

@@ -112,6 +112,7 @@ def test_device_entry_points_refuse_before_init(lib):
     assert refused(lambda: lib.d4g_debug_zopfli_table(b"abc", 3, 0, u16, u16, None)) == -1
     assert refused(lambda: lib.d4g_debug_zopfli_code_lengths(u32, 4, 15, u32)) == -1
     assert refused(lambda: lib.d4g_debug_cl_tree_lengths(u32, 1, u32, i32)) == -1
+    assert refused(lambda: abi_calls.pack_header_call(lib)) == -1
     assert refused(lambda: lib.d4g_debug_fused_stats((ctypes.c_int64 * 64)())) == -1
     assert refused(lambda: lib.d4g_batch_run(None, 1)) == -1
     assert refused(lambda: lib.d4g_batch_run_encode(None, 0, 0)) == -1

@@ -433,6 +433,8 @@ def test_single_faults_keep_their_codes_and_messages(sim):
     refused(L.d4g_debug_zopfli_table(None, 0, 0, None, None, None), ARG, b"null argument")
     refused(L.d4g_debug_zopfli_code_lengths(None, 0, 0, None), ARG, b"bad argument")
     refused(L.d4g_debug_cl_tree_lengths(None, 0, None, None), ARG, b"bad argument")
+    refused(abi_calls.pack_header_call(L, null=True), ARG, b"bad argument")
+    assert abi_calls.pack_header_call(L) == 0
     refused(L.d4g_batch_run(None, 1), ARG, b"null batch")
     refused(L.d4g_batch_parse(None), ARG, b"null batch")
     refused(L.d4g_batch_run_encode(None, 0, 0), ARG, b"not an encoder batch")
