@@ -43,7 +43,7 @@ class d4g_stats(ctypes.Structure):
                 ("recover_streams", ctypes.c_int64), ("recover_bytes", ctypes.c_int64), ("ms_recover", ctypes.c_double),
                 ("ms_recover_kernels", ctypes.c_double),
                 ("fused_fallbacks_mid", ctypes.c_int64), ("fused_relaunches", ctypes.c_int64), ("cluster_fallbacks", ctypes.c_int64),
-                ("scan_kept", ctypes.c_int64)]
+                ("scan_kept", ctypes.c_int64), ("dict_streams", ctypes.c_int64), ("dict_bytes", ctypes.c_int64)]
 
 
 class d4g_encoder_spec(ctypes.Structure):
@@ -62,7 +62,7 @@ class d4g_block_info(ctypes.Structure):
 class d4g_found_stream(ctypes.Structure):
     _fields_ = [("file", ctypes.c_int32), ("kind", ctypes.c_int32)] + \
                [(n, ctypes.c_int64) for n in ("offset", "payload_offset", "payload_len", "total_len", "decoded_len", "size_bits")] + \
-               [("crc32", ctypes.c_uint32), ("adler32", ctypes.c_uint32), ("n_blocks", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+               [("crc32", ctypes.c_uint32), ("adler32", ctypes.c_uint32), ("n_blocks", ctypes.c_int32), ("dictionary", ctypes.c_int32)]
 
 
 class d4g_find_options(ctypes.Structure):
@@ -105,7 +105,8 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
            "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
            "d4g_debug_device_blocks", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name",
-           "d4g_find_streams", "d4g_batch_recover", "d4g_batch_copy_recovered", "d4g_recover_streams"]
+           "d4g_find_streams", "d4g_batch_recover", "d4g_batch_copy_recovered", "d4g_recover_streams",
+           "d4g_batch_create_dict", "d4g_batch_create_dict_on", "d4g_inflate_dict", "d4g_find_streams_dict"]
 
 
 def load_library(path=None):
@@ -233,6 +234,17 @@ def load_library(path=None):
     L.d4g_recover_streams.restype = ctypes.c_int
     L.d4g_recover_streams.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p),
                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(d4g_parse_error)]
+    if hasattr(L, "d4g_batch_create_dict"):   # (preset dictionaries: a build from before them, loaded through D4G_LIB, has no such symbols)
+        dict_args = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]
+        L.d4g_batch_create_dict.restype = ctypes.c_void_p
+        L.d4g_batch_create_dict.argtypes = L.d4g_batch_create.argtypes + dict_args
+        L.d4g_batch_create_dict_on.restype = ctypes.c_void_p
+        L.d4g_batch_create_dict_on.argtypes = L.d4g_batch_create_on.argtypes + dict_args
+        L.d4g_inflate_dict.restype = ctypes.c_int
+        L.d4g_inflate_dict.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p),
+                                       ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]
+        L.d4g_find_streams_dict.restype = ctypes.c_int
+        L.d4g_find_streams_dict.argtypes = L.d4g_find_streams.argtypes[:4] + dict_args[:3] + L.d4g_find_streams.argtypes[4:]
     if path is None:
         _lib = L
     return L
@@ -302,21 +314,56 @@ def _parse_error_dict(e):
     return d
 
 
-class Batch:
-    """A list of independent raw DEFLATE streams resident in HBM (d4g_batch_*)."""
+def _dictionary_args(n, dictionaries, dictionary_of):
+    """The preset-dictionary arguments of Batch and its kin -> (dictionaries as a list of bytes, index per stream with -1 for
+    none).  `dictionaries` is one bytes object, applied to all n streams, or a list that goes with `dictionary_of`: per stream
+    an index into it, or None."""
+    if isinstance(dictionaries, (bytes, bytearray, memoryview)):
+        if dictionary_of is not None:
+            raise ValueError("dictionary_of goes with a list of dictionaries")
+        return [bytes(dictionaries)], [0] * n
+    dicts = [bytes(d) for d in dictionaries]
+    if dictionary_of is None:
+        raise ValueError("a list of dictionaries needs dictionary_of: per stream an index into it, or None")
+    if len(dictionary_of) != n:
+        raise ValueError("dictionary_of has one entry per stream")
+    return dicts, [-1 if k is None else int(k) for k in dictionary_of]
 
-    def __init__(self, streams, lib=None, context=None):
+
+def _dictionary_arrays(dicts):
+    nd = len(dicts)
+    return (ctypes.c_char_p * max(1, nd))(*dicts), (ctypes.c_size_t * max(1, nd))(*[len(d) for d in dicts])
+
+
+class Batch:
+    """A list of independent raw DEFLATE streams resident in HBM (d4g_batch_*).  dictionaries / dictionary_of: the preset
+    dictionaries the streams were written against (zlib's zdict=, d4g_batch_create_dict) — one bytes object for all
+    streams, or a list and per stream an index into it or None."""
+
+    def __init__(self, streams, lib=None, context=None, dictionaries=None, dictionary_of=None):
         self.L = lib or _need()
         self.n = len(streams)
         self._keep = [bytes(s) for s in streams]
         arr = (ctypes.c_char_p * self.n)(*self._keep)
         lens = (ctypes.c_size_t * self.n)(*[len(s) for s in self._keep])
-        if context is None:
+        what = "d4g_batch_create: "
+        if dictionaries is not None:
+            dicts, of = _dictionary_args(self.n, dictionaries, dictionary_of)
+            darr, dlens = _dictionary_arrays(dicts)
+            ofarr = (ctypes.c_int32 * max(1, self.n))(*of)
+            what = "d4g_batch_create_dict: "
+            if context is None:
+                self.h = self.L.d4g_batch_create_dict(self.n, arr, lens, len(dicts), darr, dlens, ofarr)
+            else:
+                self.h = self.L.d4g_batch_create_dict_on(context, self.n, arr, lens, len(dicts), darr, dlens, ofarr)
+        elif dictionary_of is not None:
+            raise ValueError("dictionary_of without dictionaries")
+        elif context is None:
             self.h = self.L.d4g_batch_create(self.n, arr, lens)
         else:   # d4g_batch_create_on: the batch lives on that context (device) whichever thread calls with it
             self.h = self.L.d4g_batch_create_on(context, self.n, arr, lens)
         if not self.h:
-            raise RuntimeError("d4g_batch_create: " + self.L.d4g_last_error().decode())
+            raise RuntimeError(what + self.L.d4g_last_error().decode())
 
     def run(self, merge_blocks=True):
         rc = self.L.d4g_batch_run(self.h, 1 if merge_blocks else 0)
@@ -553,9 +600,16 @@ def verify_streams(a, b, lib=None):
     return [{"verdict": v[i], "first_mismatch": f[i]} for i in range(n)]
 
 
-def diagnose_streams(streams, lib=None):
+def diagnose_streams(streams, lib=None, dictionaries=None, dictionary_of=None):
     """d4g_diagnose_streams: parse every raw DEFLATE stream and say where and why it fails -> list of the dicts of
-    Batch.parse_error (reason PARSE_OK for the streams that parse)."""
+    Batch.parse_error (reason PARSE_OK for the streams that parse).  With preset dictionaries (as Batch takes them) the same
+    through a batch of its own."""
+    if dictionaries is not None:
+        b = Batch(streams, lib=lib, dictionaries=dictionaries, dictionary_of=dictionary_of).parse()
+        try:
+            return [b.parse_error(i) for i in range(b.n)]
+        finally:
+            b.close()
     L = lib or _need()
     n = len(streams)
     keep = [bytes(s) for s in streams]
@@ -568,10 +622,16 @@ def diagnose_streams(streams, lib=None):
     return [_parse_error_dict(out[i]) for i in range(n)]
 
 
-def recover_streams(streams, lib=None):
+def recover_streams(streams, lib=None, dictionaries=None, dictionary_of=None):
     """d4g_recover_streams: inflate every raw DEFLATE stream as far as it goes -> list of (bytes, the dict of Batch.parse_error);
     a stream that parses gives all its bytes and reason PARSE_OK, one that does not the decoded_offset bytes before its first
-    failure."""
+    failure.  With preset dictionaries (as Batch takes them) the same through a batch of its own."""
+    if dictionaries is not None:
+        b = Batch(streams, lib=lib, dictionaries=dictionaries, dictionary_of=dictionary_of).parse()
+        try:
+            return [(b.recovered(i), b.parse_error(i)) for i in range(b.n)]
+        finally:
+            b.close()
     L = lib or _need()
     n = len(streams)
     keep = [bytes(s) for s in streams]
@@ -590,11 +650,36 @@ def recover_streams(streams, lib=None):
     return res
 
 
-def find_streams(files, kinds=0, min_decoded=0, lib=None, stats=False):
+def inflate(data, dictionary=None, lib=None):
+    """d4g_inflate / d4g_inflate_dict: the decoded bytes of one raw DEFLATE stream, optionally written against a preset
+    dictionary -> (bytes or None when it does not parse, bytes consumed)."""
+    L = lib or _need()
+    data = bytes(data)
+    out = ctypes.c_void_p()
+    ol = ctypes.c_size_t()
+    co = ctypes.c_size_t()
+    st = ctypes.c_int32()
+    if dictionary is None:
+        rc = L.d4g_inflate(data, len(data), ctypes.byref(out), ctypes.byref(ol), ctypes.byref(co), ctypes.byref(st))
+    else:
+        d = bytes(dictionary)
+        rc = L.d4g_inflate_dict(data, len(data), d, len(d), ctypes.byref(out), ctypes.byref(ol), ctypes.byref(co), ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError("d4g_inflate: " + L.d4g_last_error().decode())
+    if st.value < 0:
+        return None, co.value
+    res = ctypes.string_at(out.value, ol.value)
+    L.d4g_free(out)
+    return res, co.value
+
+
+def find_streams(files, kinds=0, min_decoded=0, lib=None, stats=False, dictionaries=None):
     """d4g_find_streams: the zlib and gzip streams embedded in files whose layout is not known (include/deft4g.h states what
     counts as one).  kinds: OR of 1 << FOUND_ZLIB / 1 << FOUND_GZIP, 0 = both.  -> one list per file, in offset order, of
     dict(file, kind, kind_name, offset, payload_offset, payload_len, total_len, decoded_len, size_bits, crc32, adler32,
-    n_blocks); with stats=True also the dict of d4g_find_stats."""
+    n_blocks); with stats=True also the dict of d4g_find_stats.  dictionaries: a list of preset dictionaries
+    (d4g_find_streams_dict) — zlib headers with FDICT whose DICTID is the Adler-32 of one of them are streams too, and every
+    dict then has a "dictionary" key: the index of the stream's dictionary, or None."""
     L = lib or _need()
     n = len(files)
     keep = [bytes(f) for f in files]
@@ -604,12 +689,19 @@ def find_streams(files, kinds=0, min_decoded=0, lib=None, stats=False):
     found = ctypes.POINTER(d4g_found_stream)()
     nf = ctypes.c_size_t()
     st = d4g_find_stats()
-    rc = L.d4g_find_streams(n, arr, lens, ctypes.byref(opt), ctypes.byref(found), ctypes.byref(nf), ctypes.byref(st))
+    if dictionaries is None:
+        rc = L.d4g_find_streams(n, arr, lens, ctypes.byref(opt), ctypes.byref(found), ctypes.byref(nf), ctypes.byref(st))
+    else:
+        dicts = [bytes(d) for d in dictionaries]
+        darr, dlens = _dictionary_arrays(dicts)
+        rc = L.d4g_find_streams_dict(n, arr, lens, ctypes.byref(opt), len(dicts), darr, dlens, ctypes.byref(found), ctypes.byref(nf), ctypes.byref(st))
     if rc != 0:
         raise RuntimeError("d4g_find_streams: " + L.d4g_last_error().decode())
     res = [[] for _ in range(n)]
     for k in range(nf.value):
-        d = {name: getattr(found[k], name) for name, _ in d4g_found_stream._fields_ if name != "reserved"}
+        d = {name: getattr(found[k], name) for name, _ in d4g_found_stream._fields_ if name != "dictionary"}
+        if dictionaries is not None:
+            d["dictionary"] = found[k].dictionary - 1 if found[k].dictionary > 0 else None
         d["kind_name"] = FOUND_KIND_NAMES.get(d["kind"], "unknown")
         res[d["file"]].append(d)
     if nf.value:
@@ -737,29 +829,19 @@ class DeflateStream:
         self._data = None
         self._batch = None
         self._parsed = None
+        self._dictionary = None
 
     def getName(self):
         return self.name
 
-    def parse(self, data):
-        """-> bool.  `consumed` gives the bytes DeflateStream.parse(InputStream) reads (K/GZFile.java:84 relies on it)."""
+    def parse(self, data, dictionary=None):
+        """-> bool.  `consumed` gives the bytes DeflateStream.parse(InputStream) reads (K/GZFile.java:84 relies on it).
+        dictionary: the preset dictionary the stream was written against; optimise() and printBlockInfo() then use it too."""
         self._data = bytes(data)
+        self._dictionary = None if dictionary is None else bytes(dictionary)
         self.close()
-        L = self._lib or _need()
-        out = ctypes.c_void_p()
-        ol = ctypes.c_size_t()
-        co = ctypes.c_size_t()
-        st = ctypes.c_int32()
-        rc = L.d4g_inflate(self._data, len(self._data), ctypes.byref(out), ctypes.byref(ol), ctypes.byref(co), ctypes.byref(st))
-        if rc != 0:
-            raise RuntimeError(L.d4g_last_error().decode())
-        self.consumed = co.value
-        if st.value < 0:
-            self._parsed = None
-            return False
-        self._parsed = ctypes.string_at(out.value, ol.value)
-        L.d4g_free(out)
-        return True
+        self._parsed, self.consumed = inflate(self._data, self._dictionary, self._lib)
+        return self._parsed is not None
 
     def getUncompressedData(self):
         return self._parsed
@@ -771,7 +853,7 @@ class DeflateStream:
         if b is None:
             if self._parsed is None:
                 raise RuntimeError("printBlockInfo() on a stream that did not parse")
-            b, own = Batch([self._data], lib=self._lib).parse(), True
+            b, own = Batch([self._data], lib=self._lib, dictionaries=self._dictionary).parse(), True
         try:
             info = b.block_info(0, final=not own)
         finally:
@@ -785,12 +867,19 @@ class DeflateStream:
         if self._batch is not None:
             r = self._batch.result(0)
             return r["size_bits_in"] - r["saved_bits"]
+        if self._dictionary is not None:   # (getSizeBitsFallback knows no dictionary)
+            b = Batch([self._data], lib=self._lib, dictionaries=self._dictionary).parse()
+            try:
+                r = b.result(0)
+                return r["size_bits_in"] if r["status"] >= 0 else len(self._data) * 8
+            finally:
+                b.close()
         return Deft.getSizeBitsFallback(self._data, self._lib)
 
     def optimise(self, mergeBlocks=True):
         """-> bits saved (DeflateStream.optimise(boolean), :496)."""
         self.close()
-        self._batch = Batch([self._data], lib=self._lib).run(mergeBlocks)
+        self._batch = Batch([self._data], lib=self._lib, dictionaries=self._dictionary).run(mergeBlocks)
         return self._batch.result(0)["saved_bits"]
 
     def asBytes(self):
@@ -802,7 +891,7 @@ class DeflateStream:
         if self._parsed is None:
             raise RuntimeError("asBytes() on a stream that did not parse")
         out = bytearray(self._data[:self.consumed])
-        rem = Deft.getSizeBitsFallback(self._data, self._lib) % 8
+        rem = self.getSizeBits() % 8
         if rem and out:
             out[-1] &= (1 << rem) - 1
         return bytes(out)

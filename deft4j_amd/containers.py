@@ -90,24 +90,42 @@ class GZFile:
 
 
 class ZLibFile:
+    """dictionaries: the preset dictionaries a stream with FDICT may name (the reference refuses FDICT, K/ZLibFile.java:76-79,
+    and so does this class without them).  The stream's DICTID — the Adler-32 of its dictionary — picks one, the first that
+    matches; `dictionary` is its index (None: no FDICT).  The DICTID bytes are kept and written back."""
     file_type = "ZLib"                        # K/ZLibFile.java:98
 
+    def __init__(self, dictionaries=None):
+        self.dictionaries = None if dictionaries is None else [bytes(d) for d in dictionaries]
+        self.dictionary = None
+        self.dictid = b""
+
     def read(self, data):                     # K/ZLibFile.java:60-95
+        import zlib as _z
         d = bytes(data)
         if len(d) < 2:
             return False
         self.cmf, self.flg = d[0], d[1]
-        if (self.cmf & 0xf) != 8 or ((self.cmf << 8) + self.flg) % 31 != 0 or (self.flg & 0x20):
+        self.dictionary, self.dictid = None, b""
+        if (self.cmf & 0xf) != 8 or ((self.cmf << 8) + self.flg) % 31 != 0:
             return False
-        self.payload = d[2:]
+        if self.flg & 0x20:
+            if len(d) < 6 or not self.dictionaries:
+                return False
+            ids = [struct.pack(">I", _z.adler32(x) & 0xffffffff) for x in self.dictionaries]
+            if d[2:6] not in ids:
+                return False
+            self.dictid = d[2:6]
+            self.dictionary = ids.index(self.dictid)
+        self.payload = d[2 + len(self.dictid):]
         self.name = DEFAULT_NAME
         return True
 
     def payload_offset(self):
-        return 2
+        return 2 + len(self.dictid)
 
     def write(self, deflate, crc32, adler32, isize):   # K/ZLibFile.java:33-57 (Adler-32 big-endian)
-        return bytes([self.cmf, self.flg]) + deflate + struct.pack(">I", adler32 & 0xffffffff)
+        return bytes([self.cmf, self.flg]) + self.dictid + deflate + struct.pack(">I", adler32 & 0xffffffff)
 
 
 class PNGFile:
@@ -370,11 +388,14 @@ class EmbeddedFile:
         self.min_decoded = min_decoded
         self.relocations = []
 
-    def read(self, data, lib=None):
+    def read(self, data, lib=None, dictionaries=None):
         from . import find_streams
         self.data = bytes(data)
-        self.found = find_streams([self.data], min_decoded=self.min_decoded, lib=lib)[0]
+        self.found = find_streams([self.data], min_decoded=self.min_decoded, lib=lib, dictionaries=dictionaries)[0]
         return bool(self.found)
+
+    def stream_dictionaries(self):
+        return [f.get("dictionary") for f in self.found]
 
     def stream_payloads(self):
         return [("%s stream at %d" % (f["kind_name"], f["offset"]), self.data[f["payload_offset"]:f["payload_offset"] + f["payload_len"]])
@@ -399,8 +420,9 @@ class EmbeddedFile:
 _MULTI = (PNGFile, ZipFile, EmbeddedFile)     # containers with a list of streams (stream_payloads)
 
 
-def detect(data):
-    """K/ContainerUtil.java:64-86 by magic bytes (PNG, zip, gzip, zlib); anything else must be given explicitly."""
+def detect(data, dictionaries=None):
+    """K/ContainerUtil.java:64-86 by magic bytes (PNG, zip, gzip, zlib); anything else must be given explicitly.
+    dictionaries: the preset dictionaries a zlib stream with FDICT may name."""
     if bytes(data[:8]) == PNGFile.SIG:
         return PNGFile()
     if bytes(data[:4]) == b"PK\x03\x04":
@@ -409,13 +431,13 @@ def detect(data):
     if d == b"\x1f\x8b":
         return GZFile()
     if len(d) == 2 and (d[0] & 0xf) == 8 and ((d[0] << 8) + d[1]) % 31 == 0:
-        return ZLibFile()
+        return ZLibFile(dictionaries)
     return None
 
 
-def _read_files(files, formats, lib=None):
+def _read_files(files, formats, lib=None, dictionaries=None):
     """-> (container per file or None when unreadable, the deflate payloads of all files in order, (file index, stream
-    name) per payload)"""
+    name) per payload, the keyword arguments that give a Batch of the payloads their preset dictionaries)"""
     conts = []
     for i, f in enumerate(files):
         c = formats[i] if formats and formats[i] is not None else None
@@ -424,10 +446,10 @@ def _read_files(files, formats, lib=None):
         if c == "embedded":
             c = EmbeddedFile()
         if c is None:
-            c = detect(f)
-        ok = c is not None and (c.read(f, lib=lib) if isinstance(c, EmbeddedFile) else c.read(f))
+            c = detect(f, dictionaries)
+        ok = c is not None and (c.read(f, lib=lib, dictionaries=dictionaries) if isinstance(c, EmbeddedFile) else c.read(f))
         conts.append(c if ok else None)
-    payloads, owner = [], []
+    payloads, owner, dict_of = [], [], []
     for i, c in enumerate(conts):
         if c is None:
             continue
@@ -435,20 +457,25 @@ def _read_files(files, formats, lib=None):
         for name, pl in sp:
             payloads.append(pl)
             owner.append((i, name))
-    return conts, payloads, owner
+        if isinstance(c, EmbeddedFile):
+            dict_of += c.stream_dictionaries()
+        else:
+            dict_of += [getattr(c, "dictionary", None)] * len(sp)
+    with_dicts = {} if dictionaries is None else dict(dictionaries=[bytes(d) for d in dictionaries], dictionary_of=dict_of)
+    return conts, payloads, owner, with_dicts
 
 
-def explain_failures(files, formats=None, lib=None):
+def explain_failures(files, formats=None, lib=None, dictionaries=None):
     """Where the reference prints "Failed to parse deflate stream data": the containers are read as optimise_files reads
     them, every stream of every file is parsed in one batch, and for each stream that does not parse the answer is
     dict(file, stream, name, error) — file index, stream index within the file, stream name, and the dict of
     Batch.parse_error (reason, reason_name, block, block_bit_pos, bit_pos, decoded_offset, value).  Files that cannot be
     read as a container have no streams and are not listed."""
-    _, payloads, owner = _read_files(files, formats, lib)
+    _, payloads, owner, with_dicts = _read_files(files, formats, lib, dictionaries)
     out = []
     if not payloads:
         return out
-    batch = Batch(payloads, lib=lib).parse()
+    batch = Batch(payloads, lib=lib, **with_dicts).parse()
     try:
         first = {}
         for q, (i, name) in enumerate(owner):
@@ -460,18 +487,18 @@ def explain_failures(files, formats=None, lib=None):
     return out
 
 
-def recover_files(files, formats=None, lib=None):
+def recover_files(files, formats=None, lib=None, dictionaries=None):
     """What can be saved of damaged files: the containers are read as optimise_files and explain_failures read them (a file
     they refuse has no streams: its list is empty), every stream of every file is parsed in one batch, and per file the answer
     is a list of dict(stream, name, data, complete, error) — stream index within the file, stream name, the decoded bytes
     (all of them where the stream parsed: complete=True, error=None; else the bytes before its first failure and the dict of
     Batch.parse_error, whose decoded_offset is len(data)).  Later intact members of a multi-member file are not pieced on;
     find_streams locates those."""
-    _, payloads, owner = _read_files(files, formats, lib)
+    _, payloads, owner, with_dicts = _read_files(files, formats, lib, dictionaries)
     out = [[] for _ in files]
     if not payloads:
         return out
-    batch = Batch(payloads, lib=lib).parse()
+    batch = Batch(payloads, lib=lib, **with_dicts).parse()
     try:
         for q, (i, name) in enumerate(owner):
             ok = batch.result(q)["status"] >= 0
@@ -482,7 +509,7 @@ def recover_files(files, formats=None, lib=None):
     return out
 
 
-def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, verify=False):
+def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, verify=False, dictionaries=None):
     """files: list of bytes.  formats: optional list of container instances / None (auto-detect) / "raw" /
     "embedded" (EmbeddedFile: zlib and gzip streams wherever they lie in the file).
     mode: RecompressMode ordinal of `deft4j optimise --mode` (0 NONE, 1 CHEAP, 2 ZOPFLI, 3 ZOPFLI_EXTENSIVE, 4 ZOPFLI_VERY_EXTENSIVE; M/CMDUtil.java:44-50,76-105): above NONE every
@@ -490,11 +517,14 @@ def optimise_files(files, merge_blocks=True, formats=None, lib=None, mode=0, ver
     Returns [(output bytes or None when unreadable, transcript lines)] — the lines M/CMDUtil.java:64-74 and
     K/DeflateFilesContainer.java:31-40 print.  Every deflate stream of every file goes to the GPU in one batch.
     verify: before any file is assembled, every rewritten stream is parsed again on the device and its decoded bytes compared
-    with the original's (Batch.verify); a stream that fails raises RuntimeError naming file, stream, block and offset."""
-    conts, payloads, owner = _read_files(files, formats, lib)
+    with the original's (Batch.verify); a stream that fails raises RuntimeError naming file, stream, block and offset.
+    dictionaries: a list of preset dictionaries.  A zlib file with FDICT (and, in an EmbeddedFile, a zlib header with FDICT)
+    whose DICTID names one of them is read and optimised against it; explain_failures and recover_files take the same.  The
+    encoders take no dictionary: mode > 0 with such a stream raises RuntimeError with the library's message."""
+    conts, payloads, owner, with_dicts = _read_files(files, formats, lib, dictionaries)
     batch = None
     if payloads:
-        batch = Batch(payloads, lib=lib)
+        batch = Batch(payloads, lib=lib, **with_dicts)
         batch.run_recompress(mode, merge_blocks) if mode > 0 else batch.run(merge_blocks)
         if verify:
             from . import VERDICT_NAMES

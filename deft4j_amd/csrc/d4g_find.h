@@ -9,7 +9,10 @@
 
 #define D4G_FOUND_KIND_ZLIB 1   // = D4G_FOUND_ZLIB / D4G_FOUND_GZIP of the C ABI
 #define D4G_FOUND_KIND_GZIP 2
+// kind: D4G_FOUND_KIND_* in the low byte; a zlib header with FDICT carries 1 + the index of its preset dictionary above it
 struct D4GFindCand { int32_t file, kind; long long offset, payload; };
+#define D4G_FIND_KIND(k) ((k) & 0xff)
+#define D4G_FIND_DICT(k) (((k) >> 8) - 1)   // -1: none
 struct D4GScanTile { int32_t stream; int32_t pad; long long byteStart; };   // one workgroup's bytes of a file
 #define D4G_FIND_TILE 2048
 #define D4G_FIND_LOCAL 64   // candidates a workgroup collects before it touches the global list (random bytes give about one per tile)
@@ -37,8 +40,10 @@ D4G_DEV long long d4g_gzip_payload(const uint8_t* data, long long len, long long
 // workgroup and take one global atomic per tile (an atomic per hit on one counter is far slower); a tile with more than
 // D4G_FIND_LOCAL of them sends the rest straight to the global list.  The count may pass `cap`: the host then runs the
 // kernel again with a list that holds them all.
+// dictIds: the Adler-32 of each of the caller's nDict preset dictionaries (d4g_find_streams_dict): a zlib header with FDICT
+// whose DICTID is one of them is a candidate too, the first match in list order, its payload 4 bytes further on.
 __global__ void __launch_bounds__(256) k_find_wrappers(const D4GStreamDesc* files, const D4GScanTile* tiles, int kinds, D4GFindCand* cands,
-                                                       unsigned* nCands, unsigned cap) {
+                                                       unsigned* nCands, unsigned cap, const uint32_t* dictIds, int nDict) {
     alignas(16) __shared__ uint8_t buf[D4G_FIND_TILE + 16];
     __shared__ D4GFindCand lc[D4G_FIND_LOCAL];
     __shared__ unsigned lcount, gbase;
@@ -58,6 +63,15 @@ __global__ void __launch_bounds__(256) k_find_wrappers(const D4GStreamDesc* file
             !(c1 & 0x20)) {
             c.kind = D4G_FOUND_KIND_ZLIB;
             c.payload = o + 2;
+        } else if (nDict && (kinds & (1 << D4G_FOUND_KIND_ZLIB)) && o + 6 <= sd.len && (c0 & 15) == 8 && (c0 >> 4) <= 7 &&
+                   ((c0 << 8) + c1) % 31 == 0) {   // FDICT: DICTID, big-endian, right after FLG
+            const uint32_t id = ((uint32_t)buf[b + 2] << 24) | ((uint32_t)buf[b + 3] << 16) | ((uint32_t)buf[b + 4] << 8) | (uint32_t)buf[b + 5];
+            for (int d = 0; d < nDict; d++)
+                if (dictIds[d] == id) {
+                    c.kind = D4G_FOUND_KIND_ZLIB | ((d + 1) << 8);
+                    c.payload = o + 6;
+                    break;
+                }
         } else if ((kinds & (1 << D4G_FOUND_KIND_GZIP)) && o + 10 <= sd.len && c0 == 0x1f && c1 == 0x8b && buf[b + 2] == 8 && !(buf[b + 3] & 0xe0)) {
             c.kind = D4G_FOUND_KIND_GZIP;
             c.payload = d4g_gzip_payload(sd.data, sd.len, o, buf[b + 3]);   // (rare: the optional fields are read where they lie)

@@ -63,6 +63,8 @@ struct HStream {
     std::vector<HBlock> blocks;
     i64 consumed = 0, sizeBitsIn = 0, saved = 0;
     i64 inOff = 0, inLen = 0;
+    const uint8_t* dict = nullptr;   // preset dictionary: its tail in device memory (the batch's dDict, or that of the batch this one works for)
+    i64 dictLen = 0;                 // bytes of that tail (<= 32768), 0: none
     i64 tokBase = 0, uBase = 0, nTok = 0, nU = 0, refBase = 0, nRef = 0;
     i64 outWordBase = 0, outBits = 0;
     int arena[2] = {-1, -1};
@@ -99,7 +101,7 @@ struct Batch {
         i64 maxSlots = 0;
     };
     struct MergeReq { int stream; int arena; };
-    struct ChainStart { int32_t stream; i64 bit; };   // walk_chains: a block chain begins at this bit of this stream
+    struct ChainStart { int32_t stream; i64 bit; i64 dictLen = 0; };   // walk_chains: a block chain begins at this bit of this stream; bytes of preset dictionary before it
     struct BlockMap {   // scan_inputs: the dynamic headers the scan found and the probe confirmed
         std::vector<std::vector<std::pair<i64, int>>> byStream;   // per stream, sorted: bit position -> index in pout
         std::vector<D4GProbeOut> pout;
@@ -110,6 +112,8 @@ struct Batch {
     std::vector<HStream> streams;
     d4g_stats stats;
     RtBuf<uint8_t> dIn;
+    RtBuf<uint8_t> dDict;            // preset dictionaries: the last 32 KiB of each, once per batch (allocated only when there is one)
+    std::vector<i64> dictOff, dictTail;   // per dictionary: where its tail starts in dDict, and its length
     RtBuf<uint8_t> dU;               // decoded bytes of every stream
     RtBuf<D4GStreamDesc> dStreams;
     RtBuf<uint32_t> dOut;
@@ -164,6 +168,9 @@ struct Batch {
     void check_device_errors();
     // d4g_host_parse.h
     void create(size_t n, const uint8_t* const* in, const size_t* len, bool fromDevice = false);
+    void set_dictionaries(size_t nDict, const uint8_t* const* dict, const size_t* dictLen, const int32_t* dictOf);
+    D4GStreamDesc stream_desc(size_t i) const;
+    bool has_dictionary() const { return stats.dict_streams > 0; }
     void parse_probe();
     void scan_inputs(BlockMap& M);
     void walk_chains(const std::vector<ChainStart>& starts, const BlockMap& M, std::vector<PStream>& out, int maxBlocks);

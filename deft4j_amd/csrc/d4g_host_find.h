@@ -16,7 +16,7 @@ struct FindRun {
     double msKernels = 0;
 
     // k_find_wrappers over every file -> the candidates in (file, offset) order
-    std::vector<D4GFindCand> wrappers(Batch& F, int kinds) {
+    std::vector<D4GFindCand> wrappers(Batch& F, int kinds, const std::vector<uint32_t>& dictIds) {
         std::vector<D4GScanTile> tiles;
         i64 total = 0;
         for (size_t i = 0; i < F.streams.size(); i++) {
@@ -28,11 +28,12 @@ struct FindRun {
         RtScratch tmp;
         D4GScanTile* dTiles = tmp.upload(tiles);
         unsigned* dN = tmp.alloc<unsigned>(1);
+        const uint32_t* dIds = dictIds.empty() ? nullptr : tmp.upload(dictIds);
         unsigned cap = (unsigned)std::max<i64>(4096, total / 256), nc = 0;
         for (int attempt = 0; attempt < 2; attempt++) {
             D4GFindCand* dC = tmp.alloc<D4GFindCand>((size_t)cap);
             rt_memset(dN, 0, 4);
-            RT_LAUNCH(k_find_wrappers, tiles.size(), 256, F.dStreams, dTiles, kinds, dC, dN, cap);
+            RT_LAUNCH(k_find_wrappers, tiles.size(), 256, F.dStreams, dTiles, kinds, dC, dN, cap, dIds, (int)dictIds.size());
             st.kernel_launches++;
             rt_d2h(&nc, dN, 4);
             if (nc <= cap) {
@@ -69,9 +70,10 @@ struct FindRun {
             const D4GFindCand& c = cands[group[k]];
             G.streams[k].inOff = F.streams[c.file].inOff;
             G.streams[k].inLen = F.streams[c.file].inLen;
+            if (const int d = D4G_FIND_DICT(c.kind); d >= 0 && F.dictTail[d]) { G.streams[k].dict = F.dDict + F.dictOff[d]; G.streams[k].dictLen = F.dictTail[d]; }
             G.ps[k] = chains[group[k]];
             for (Batch::PBlock& pb : G.ps[k].blocks) pb.firstBatch = -1;   // (the scan's chunk records went back with the scan)
-            checks[k] = {G.dIn + G.streams[k].inOff + G.ps[k].consumed, c.kind, 0};
+            checks[k] = {G.dIn + G.streams[k].inOff + G.ps[k].consumed, D4G_FIND_KIND(c.kind), 0};
         }
         G.build_blocks(false, false);
         RtScratch tmp;
@@ -91,13 +93,30 @@ struct FindRun {
         return v;
     }
 
-    void run(size_t n, const uint8_t* const* file, const size_t* len, int kinds, i64 minDecoded) {
+    // RFC 1950's Adler-32 of a whole dictionary: its DICTID
+    static uint32_t adler32(const uint8_t* p, size_t n) {
+        uint32_t a = 1, b = 0;
+        while (n) {
+            const size_t k = std::min<size_t>(n, 5552);   // (the sums stay below 2^32 for this many bytes)
+            for (size_t i = 0; i < k; i++) { a += p[i]; b += a; }
+            a %= 65521; b %= 65521;
+            p += k; n -= k;
+        }
+        return (b << 16) | a;
+    }
+
+    void run(size_t n, const uint8_t* const* file, const size_t* len, int kinds, i64 minDecoded, size_t nDict = 0, const uint8_t* const* dict = nullptr,
+             const size_t* dictLen = nullptr) {
         const double t0 = now_ms();
         memset(&st, 0, sizeof(st));
         if (kinds == 0) kinds = (1 << D4G_FOUND_KIND_ZLIB) | (1 << D4G_FOUND_KIND_GZIP);
         engine().init();
         Batch F;
         F.create(n, file, len);
+        std::vector<uint32_t> dictIds(nDict);
+        for (size_t d = 0; d < nDict; d++) dictIds[d] = adler32(dict[d], dictLen[d]);
+        if (nDict) F.set_dictionaries(nDict, dict, dictLen, nullptr);   // (the tails: a candidate names its dictionary)
+        auto dict_len_of = [&](const D4GFindCand& c) { return D4G_FIND_DICT(c.kind) >= 0 ? F.dictTail[D4G_FIND_DICT(c.kind)] : (i64)0; };
         st.bytes_scanned = F.stats.bytes_in;
         // 1. every file's dynamic-header map (once), the wrapper candidates, and their trial parse: the first block of
         //    every candidate, then the whole chain of the survivors
@@ -105,16 +124,16 @@ struct FindRun {
         e0.record();
         Batch::BlockMap M;
         F.scan_inputs(M);
-        const std::vector<D4GFindCand> all = wrappers(F, kinds);
+        const std::vector<D4GFindCand> all = wrappers(F, kinds, dictIds);
         st.header_candidates = (i64)all.size();
         std::vector<Batch::ChainStart> starts(all.size());
-        for (size_t k = 0; k < all.size(); k++) starts[k] = {all[k].file, all[k].payload * 8};
+        for (size_t k = 0; k < all.size(); k++) starts[k] = {all[k].file, all[k].payload * 8, dict_len_of(all[k])};
         std::vector<Batch::PStream> first;
         F.walk_chains(starts, M, first, 1);
         std::vector<D4GFindCand> cands;
         starts.clear();
         for (size_t k = 0; k < all.size(); k++)
-            if (first[k].status == 0) { cands.push_back(all[k]); starts.push_back({all[k].file, all[k].payload * 8}); }
+            if (first[k].status == 0) { cands.push_back(all[k]); starts.push_back({all[k].file, all[k].payload * 8, dict_len_of(all[k])}); }
         st.first_block_ok = (i64)cands.size();
         std::vector<Batch::PStream> chains;
         F.walk_chains(starts, M, chains, 0);
@@ -127,7 +146,7 @@ struct FindRun {
         for (size_t k = 0; k < cands.size(); k++) {
             if (chains[k].status != 0) continue;
             st.parsed++;
-            const i64 trailer = cands[k].kind == D4G_FOUND_KIND_ZLIB ? 4 : 8;
+            const i64 trailer = D4G_FIND_KIND(cands[k].kind) == D4G_FOUND_KIND_ZLIB ? 4 : 8;
             if (chains[k].consumed + trailer > F.streams[cands[k].file].inLen || chains[k].nU < minDecoded) continue;
             todo.push_back(k);
         }
@@ -154,9 +173,9 @@ struct FindRun {
                 if (c.offset < reportedEnd[c.file]) continue;
                 d4g_found_stream f;
                 memset(&f, 0, sizeof(f));
-                f.file = c.file; f.kind = c.kind; f.offset = c.offset; f.payload_offset = c.payload;
+                f.file = c.file; f.kind = D4G_FIND_KIND(c.kind); f.dictionary = D4G_FIND_DICT(c.kind) + 1; f.offset = c.offset; f.payload_offset = c.payload;
                 f.payload_len = P.consumed - c.payload;
-                f.total_len = P.consumed + (c.kind == D4G_FOUND_KIND_ZLIB ? 4 : 8) - c.offset;
+                f.total_len = P.consumed + (f.kind == D4G_FOUND_KIND_ZLIB ? 4 : 8) - c.offset;
                 f.decoded_len = P.nU; f.size_bits = P.sizeBits;
                 f.crc32 = v[q].crc32; f.adler32 = v[q].adler32;
                 f.n_blocks = (int32_t)P.blocks.size();

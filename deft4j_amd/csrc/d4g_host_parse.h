@@ -27,6 +27,45 @@ inline void Batch::create(size_t n, const uint8_t* const* in, const size_t* len,
     stats.ms_upload = now_ms() - t0;
 }
 
+// Preset dictionaries (d4g_batch_create_dict): the last 32 KiB of each goes to the device once, however many streams name
+// it; a stream's descriptor points at its dictionary's tail.  dictOf == nullptr names none (d4g_find_streams_dict picks
+// per candidate).  A dictionary of length 0 is no dictionary; without any, nothing is allocated.  The caller has checked
+// the arguments.
+inline void Batch::set_dictionaries(size_t nDict, const uint8_t* const* dict, const size_t* dictLen, const int32_t* dictOf) {
+    dictOff.assign(nDict, 0);
+    dictTail.assign(nDict, 0);
+    i64 off = 0;
+    for (size_t d = 0; d < nDict; d++) {
+        dictTail[d] = (i64)std::min<size_t>(dictLen[d], D4G_WIN);
+        dictOff[d] = off;
+        off += (dictTail[d] + 15) & ~15LL;
+    }
+    if (!off) return;
+    dDict.alloc_zero((size_t)off);
+    for (size_t d = 0; d < nDict; d++)
+        if (dictTail[d]) rt_h2d(dDict + dictOff[d], dict[d] + (dictLen[d] - (size_t)dictTail[d]), (size_t)dictTail[d]);
+    rt_sync();
+    stats.dict_bytes = 0;
+    for (size_t d = 0; d < nDict; d++) stats.dict_bytes += dictTail[d];
+    for (size_t i = 0; dictOf && i < streams.size(); i++) {
+        if (dictOf[i] < 0 || !dictTail[dictOf[i]]) continue;
+        streams[i].dict = dDict + dictOff[dictOf[i]];
+        streams[i].dictLen = dictTail[dictOf[i]];
+        stats.dict_streams++;
+    }
+}
+// stream i as the kernels see it before its decoded bytes have a place
+inline D4GStreamDesc Batch::stream_desc(size_t i) const {
+    D4GStreamDesc d;
+    d.data = dIn ? dIn + streams[i].inOff : nullptr;
+    d.len = streams[i].inLen;
+    d.uBase = 0;
+    d.uLen = 0;
+    d.dict = streams[i].dict;
+    d.dictLen = streams[i].dictLen;
+    return d;
+}
+
 // ---- parse: header scan -> block probes -> chain -> emit -> pointer jumping ----
 // hit records that come back with the hit count, in one read: up to 45 KB whatever the count turns out to be, the price
 // of not waiting for the count first (a batch of config 2 has about 340 hits)
@@ -93,10 +132,7 @@ inline void Batch::scan_inputs(BlockMap& M) {
     uint32_t* tileStart = (uint32_t*)(sd.data() + n);
     i64 totalBytes = 0, nTiles = 0;
     for (size_t i = 0; i < n; i++) {
-        sd[i].data = dIn + streams[i].inOff;
-        sd[i].len = streams[i].inLen;
-        sd[i].uBase = 0;
-        sd[i].uLen = 0;
+        sd[i] = stream_desc(i);
         tileStart[i] = (uint32_t)nTiles;
         nTiles += (streams[i].inLen + D4G_SCAN_TILE - 1) / D4G_SCAN_TILE;
         if (nTiles > 0x7fffffffLL) throw std::runtime_error("batch holds 2^31 or more scan tiles: split it");
@@ -131,7 +167,7 @@ inline void Batch::walk_chains(const std::vector<ChainStart>& starts, const Bloc
     dExOut.alloc(n, 16);
     auto accept = [&](size_t i, i64 bitPos, const D4GProbeOut& o, bool fromScan) {
         PStream& P = out[i];
-        if (o.status != 0 || o.needHist > upos[i]) {
+        if (o.status != 0 || o.needHist > upos[i] + starts[i].dictLen) {
             P.status = -1; done[i] = 1;
             P.failBlock = (i64)P.blocks.size(); P.failBit = bitPos; P.failU = upos[i];
             return;
@@ -195,7 +231,7 @@ inline void Batch::parse_probe() {
     BlockMap M;
     scan_inputs(M);
     std::vector<ChainStart> starts(n);
-    for (size_t i = 0; i < n; i++) starts[i] = {(int32_t)i, 0};
+    for (size_t i = 0; i < n; i++) starts[i] = {(int32_t)i, 0, streams[i].dictLen};
     walk_chains(starts, M, ps, 0);
     e1.record();
     msParseKernels += rt_elapsed_ms(e0, e1);
@@ -304,6 +340,8 @@ inline void Batch::recover() {
         const PStream& P = ps[owner[k]];
         G.streams[k].inOff = streams[owner[k]].inOff;
         G.streams[k].inLen = streams[owner[k]].inLen;
+        G.streams[k].dict = streams[owner[k]].dict;   // (this batch's dDict outlives the side batch)
+        G.streams[k].dictLen = streams[owner[k]].dictLen;
         PStream& Q = G.ps[k];
         Q.blocks = P.accepted;
         for (PBlock& pb : Q.blocks) { pb.firstBatch = -1; Q.nTok += pb.nTok; Q.nU += pb.uLen; }   // (the scan's chunk records went back with the parse)
@@ -377,8 +415,7 @@ inline void Batch::layout_blocks(bool merge, bool needSlots, Layout& LY) {
         s.tokBase = tokTot;
         s.refBase = refTot;
         s.uBase = P.uBaseFixed >= 0 ? P.uBaseFixed : uTot;
-        sd[si].data = dIn ? dIn + s.inOff : nullptr;
-        sd[si].len = s.inLen;
+        sd[si] = stream_desc(si);
         sd[si].uBase = s.uBase;
         sd[si].uLen = P.nU;
         tokTot += P.nTok;
@@ -574,7 +611,10 @@ inline void Batch::copy_block_local(const std::vector<D4GTokRange>& allRanges, c
     uint16_t* dSym = tmp.alloc<uint16_t>((size_t)uTotal, 64);
     const size_t slots = R.slotOrd.size();
     uint16_t* dTailA = slots ? tmp.alloc<uint16_t>(slots * D4G_WIN) : nullptr;
-    RT_LAUNCH(k_seg_symbols, R.segs.size(), seg_threads(), dStreams, dSegs, dAll, dTok, dU, dSym, dTailA, dBad);
+    bool anyDict = false;   // (a side batch borrows its streams' dictionaries: ask the streams, not dDict)
+    for (const HStream& s : streams) anyDict |= s.dictLen > 0;
+    if (anyDict) RT_LAUNCH(k_seg_symbols<true>, R.segs.size(), seg_threads(), dStreams, dSegs, dAll, dTok, dU, dSym, dTailA, dBad);
+    else RT_LAUNCH(k_seg_symbols<false>, R.segs.size(), seg_threads(), dStreams, dSegs, dAll, dTok, dU, dSym, dTailA, dBad);
     stats.kernel_launches++;
     stats.copy_segments += (i64)R.segs.size();
     // windows: rounds of the scan are sized from the segment counts, nothing is read back
@@ -650,7 +690,7 @@ inline void Batch::copy_doubling(const CopyRoute& R, int32_t* dBad, RtScratch& t
     std::vector<D4GStreamDesc> sd;
     if (!R.segs.empty()) {
         sd.resize(n);
-        for (size_t i = 0; i < n; i++) sd[i] = {dIn ? dIn + streams[i].inOff : nullptr, streams[i].inLen, streams[i].uBase, R.doubling[i] ? ps[i].nU : 0};
+        for (size_t i = 0; i < n; i++) { sd[i] = stream_desc(i); sd[i].uBase = streams[i].uBase; sd[i].uLen = R.doubling[i] ? ps[i].nU : 0; }
         dStreamsD = tmp.upload(sd);
     }
     i64 maxDoubling = 0, totalU = 0;

@@ -135,6 +135,8 @@ struct VerifyItem {
     const uint8_t* want = nullptr;    // expected decoded bytes (device)
     i64 wantLen = 0;
     i64 wantBits = -1;                // >= 0: the parse must read exactly `len` bytes and this many bits
+    const uint8_t* dict = nullptr;    // the preset dictionary the stream was written against (its tail, device), as in HStream
+    i64 dictLen = 0;
     int verdict = VERIFY_SKIPPED;
     i64 first = -1;
     std::vector<Batch::PBlock> blocks;   // the stream's block list as parsed (empty when it does not parse)
@@ -150,6 +152,7 @@ inline void verify_items(std::vector<VerifyItem>& items, bool bytesOnHost, Verif
     for (size_t i = 0; i < n; i++) { p[i] = items[i].bytes; l[i] = items[i].len; }
     Batch V;
     V.create(n, p.data(), l.data(), !bytesOnHost);
+    for (size_t i = 0; i < n; i++) { V.streams[i].dict = items[i].dict; V.streams[i].dictLen = items[i].dictLen; }
     engine().init();
     V.parse_probe();
     V.build_blocks(false, false);

@@ -30,6 +30,11 @@ struct D4GStreamDesc {
     long long len;
     long long uBase;       // start of this stream's region in U / src
     long long uLen;
+    // preset dictionary (inflateSetDictionary): the last dictLen <= 32768 bytes of it, in device memory, shared by every stream
+    // of the batch that names it.  A distance d at decoded position p is valid iff d <= p + dictLen, and position q < 0 reads
+    // dict[dictLen + q].  nullptr / 0: no dictionary.
+    const uint8_t* dict;
+    long long dictLen;
 };
 
 struct D4GProbeIn {
@@ -866,7 +871,7 @@ __device__ __forceinline__ void d4g_parse_block(const D4GStreamDesc& sd, long lo
                 used += dcl + deb;
                 if (used > avail) { fl = 2; break; }
                 if constexpr (FAR) {
-                    if (dist > (int)uAt + (int)u) { farPos = pos; farDist = dist; farU = u; break; }
+                    if (dist > (int)uAt + (int)u + (int)sd.dictLen) { farPos = pos; farDist = dist; farU = u; break; }   // (a preset dictionary lies before byte 0)
                 }
                 if constexpr (CAP) {
                     if (u + (unsigned)len > room) break;
@@ -1192,6 +1197,7 @@ __global__ void __launch_bounds__(256) k_fill_src(const D4GStreamDesc* streams, 
     const D4GStreamDesc sd = streams[r.stream];
     uint32_t* s = src + sd.uBase;
     uint8_t* u = U + sd.uBase;
+    const uint32_t dictLen = (uint32_t)sd.dictLen;
     long long stride = (long long)G * blockDim.x;
     long long t0 = (long long)(blockIdx.x % G) * blockDim.x + threadIdx.x;
     if (r.stored) {
@@ -1204,9 +1210,15 @@ __global__ void __launch_bounds__(256) k_fill_src(const D4GStreamDesc* streams, 
         int dist = tok_dist(a), val = tok_val(a);
         if (dist == 0) {
             if (val < 256) { u[pos] = (uint8_t)val; s[pos] = pos | D4G_SRC_FINAL; }
-        } else if ((uint32_t)dist > pos) {
+        } else if ((uint32_t)dist > pos + dictLen) {
             badDist[r.stream] = 1;  // reference: readSlice walks off the first block (NullPointerException)
             for (int k = 0; k < val; k++) s[pos + k] = (pos + k) | D4G_SRC_FINAL;
+        } else if ((uint32_t)dist > pos) {
+            // the copy begins in the preset dictionary: those bytes are known now and become literals; what follows (the copy
+            // may run on into the stream's own bytes, and overlap itself) points back as any copy does
+            const int inDict = (int)((uint32_t)dist - pos) < val ? (int)((uint32_t)dist - pos) : val;
+            for (int k = 0; k < inDict; k++) { u[pos + k] = sd.dict[dictLen + pos + k - (uint32_t)dist]; s[pos + k] = (pos + k) | D4G_SRC_FINAL; }
+            for (int k = inDict; k < val; k++) s[pos + k] = pos + k - dist;
         } else {
             for (int k = 0; k < val; k++) s[pos + k] = pos + k - dist;
         }
@@ -1357,6 +1369,9 @@ struct D4GSegLds {
 // is final), or a pointer to its source inside the group; pointer doubling in LDS then resolves the group in at most
 // log2(4096) rounds whatever the tokens are — a run of tokens that each depend on the one before (PNG rows at distance
 // 3-4, long runs) costs rounds, not one round per token.
+// DICT: some stream of the batch has a preset dictionary.  A batch without one runs the instantiation that knows of none: the
+// code of the default path is what it was before dictionaries.
+template <bool DICT>
 __global__ void __launch_bounds__(1024) k_seg_symbols(const D4GStreamDesc* streams, const D4GSegment* segs, const D4GTokRange* ranges,
                                                                       const uint2* tok, const uint8_t* U, uint16_t* sym, uint16_t* tails,
                                                                       int32_t* badDist) {
@@ -1366,7 +1381,15 @@ __global__ void __launch_bounds__(1024) k_seg_symbols(const D4GStreamDesc* strea
     const D4GStreamDesc sd = streams[sg.stream];
     uint16_t* out = sym + sd.uBase + sg.uStart;
     const uint32_t segStart = (uint32_t)sg.uStart;
-    for (int i = tid; i < D4G_WIN; i += NL) L.ring[i] = (uint16_t)(D4G_SYM_MARK | (uint32_t)i);
+    // The window before the segment is unknown: markers.  Before a stream's first segment lies its preset dictionary, if it has
+    // one: those bytes are known, the window's last dictLen symbols; the markers left in front of them are the positions too far back.
+    const uint32_t dictLen = DICT ? (uint32_t)sd.dictLen : 0u;
+    if constexpr (DICT) {
+        const int known = sg.win < 0 ? D4G_WIN - (int)dictLen : D4G_WIN;   // window symbols from here on are dictionary bytes
+        for (int i = tid; i < D4G_WIN; i += NL) L.ring[i] = i >= known ? (uint16_t)sd.dict[i - known] : (uint16_t)(D4G_SYM_MARK | (uint32_t)i);
+    } else {
+        for (int i = tid; i < D4G_WIN; i += NL) L.ring[i] = (uint16_t)(D4G_SYM_MARK | (uint32_t)i);
+    }
     if (tid == 0) { L.n = D4G_SEG_GROUP_TOKENS; L.anyPtr[0] = 0; L.anyPtr[1] = 0; L.anyPtr[2] = 0; }
     __syncthreads();
     int rr = 0;   // doubling rounds so far (workgroup-uniform): round r raises anyPtr[r % 3]
@@ -1429,7 +1452,7 @@ __global__ void __launch_bounds__(1024) k_seg_symbols(const D4GStreamDesc* strea
                     const uint32_t dist = in ? (uint32_t)tok_dist(a) : 0u;
                     const uint32_t back = L.ring[(j[k] + D4G_WIN - dist) % D4G_SEG_RING];   // (final if it lies before the group, unused otherwise)
                     if (!dist) e[k] = a & 0xffu;
-                    else if (dist > segStart + j[k]) { e[k] = 0; bad = true; }   // before the start of the stream
+                    else if (dist > segStart + j[k] + dictLen) { e[k] = 0; bad = true; }   // before the start of the stream (and of its dictionary)
                     else if (j[k] - gs >= dist) e[k] = D4G_SYM_PTR | (j[k] - dist - gs);
                     else e[k] = back;
                 }

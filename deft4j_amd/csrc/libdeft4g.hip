@@ -153,6 +153,22 @@ std::unique_ptr<d4g_batch> make_batch(size_t n, const uint8_t* const* in, const 
     b->impl.create(n, in, in_len);
     return b;
 }
+// the dictionary arguments of the _dict entry points: empty when they are in order, else why not
+std::string dict_refusal(size_t n, size_t n_dict, const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of) {
+    if (n_dict && (!dict || !dict_len)) return "null argument";
+    for (size_t d = 0; d < n_dict; d++)
+        if (!dict[d] && dict_len[d]) return "dictionary " + std::to_string(d) + " is NULL but has a length";
+    for (size_t i = 0; dict_of && n_dict && i < n; i++)
+        if (dict_of[i] < -1 || dict_of[i] >= (int64_t)n_dict) return "dict_of[" + std::to_string(i) + "] names no dictionary";
+    return "";
+}
+// d4g_batch_create_dict: the arguments have passed dict_refusal
+std::unique_ptr<d4g_batch> make_batch_dict(size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict, const uint8_t* const* dict,
+                                           const size_t* dict_len, const int32_t* dict_of) {
+    std::unique_ptr<d4g_batch> b = make_batch(n, in, in_len);
+    if (n_dict && dict_of) b->impl.set_dictionaries(n_dict, dict, dict_len, dict_of);
+    return b;
+}
 static_assert(sizeof(LzSpec) == sizeof(d4g_encoder_spec), "spec layout");
 static_assert(sizeof(LzSpecL) == sizeof(d4g_encoder_spec_level), "spec layout");
 template <class Spec>   // LzSpec or LzSpecL
@@ -165,8 +181,9 @@ std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, con
     return e;
 }
 // one stream, parsed (and decoded): d4g_size_bits_fallback, d4g_inflate
-std::unique_ptr<d4g_batch> parse_one(const uint8_t* in, size_t len, bool decode) {
-    std::unique_ptr<d4g_batch> b = make_batch(1, &in, &len);
+std::unique_ptr<d4g_batch> parse_one(const uint8_t* in, size_t len, bool decode, const uint8_t* dict = nullptr, size_t dict_len = 0) {
+    const int32_t first = 0;
+    std::unique_ptr<d4g_batch> b = make_batch_dict(1, &in, &len, dict_len ? 1 : 0, &dict, &dict_len, &first);
     engine().init();
     b->impl.parse_probe();
     if (decode) b->impl.build_blocks(false, false);
@@ -261,6 +278,7 @@ int batch_verify(d4g_batch& b, const char* what, bool failOnNegative) {
         it.len = (size_t)((f.outBits + 7) / 8);
         it.want = b.impl.dU + s.uBase;
         it.wantLen = s.nU;
+        it.dict = s.dict; it.dictLen = s.dictLen;   // the written stream is parsed against the dictionary the input was
         it.wantBits = s.sizeBitsIn - s.saved - (i < b.recompSaved.size() ? b.recompSaved[i] : 0);   // what d4g_batch_stream_result lets the caller compute
         items.push_back(it);
         index.push_back(i);
@@ -413,6 +431,18 @@ d4g_batch* d4g_batch_create(size_t n, const uint8_t* const* in, const size_t* in
     d4g_batch* b = nullptr;
     api(nullptr, [&] {
         b = make_batch(n, in, in_len).release();
+        return D4G_OK;
+    });
+    return b;
+}
+
+d4g_batch* d4g_batch_create_dict(size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict, const uint8_t* const* dict,
+                                 const size_t* dict_len, const int32_t* dict_of) {
+    d4g_batch* b = nullptr;
+    api(nullptr, [&] {
+        const std::string why = dict_refusal(n, n_dict, dict, dict_len, dict_of);
+        if (!why.empty()) return fail(D4G_ERR_ARG, why);
+        b = make_batch_dict(n, in, in_len, n_dict, dict, dict_len, dict_of).release();
         return D4G_OK;
     });
     return b;
@@ -626,6 +656,16 @@ int d4g_optimise_streams_sharded(size_t n, const uint8_t* const* in, const size_
     }));
 }
 
+d4g_batch* d4g_batch_create_dict_on(int context, size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict,
+                                    const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of) {
+    if (context < 0 || context >= RT_MAX_CTX || !rtp_ctx_ready(context)) { fail(D4G_ERR_ARG, "no such context (d4g_init_devices)"); return nullptr; }
+    const int keep = g_tlsCtx;
+    g_tlsCtx = context;
+    d4g_batch* b = d4g_batch_create_dict(n, in, in_len, n_dict, dict, dict_len, dict_of);
+    g_tlsCtx = keep;
+    return b;
+}
+
 int d4g_size_bits_fallback(const uint8_t* in, size_t len, int64_t* bits) {
     if (!in || !bits) return fail(D4G_ERR_ARG, "null argument");
     return api(nullptr, [&] {
@@ -637,10 +677,16 @@ int d4g_size_bits_fallback(const uint8_t* in, size_t len, int64_t* bits) {
 }
 
 int d4g_inflate(const uint8_t* in, size_t len, uint8_t** out, size_t* out_len, size_t* consumed, int32_t* status) {
+    return d4g_inflate_dict(in, len, nullptr, 0, out, out_len, consumed, status);
+}
+
+int d4g_inflate_dict(const uint8_t* in, size_t len, const uint8_t* dict, size_t dict_len, uint8_t** out, size_t* out_len, size_t* consumed,
+                     int32_t* status) {
     if (!in || !out || !out_len || !status) return fail(D4G_ERR_ARG, "null argument");
+    if (!dict && dict_len) return fail(D4G_ERR_ARG, "the dictionary is NULL but has a length");
     Outputs o(1, out, out_len);
     return o.commit(api(nullptr, [&] {
-        std::unique_ptr<d4g_batch> b = parse_one(in, len, true);
+        std::unique_ptr<d4g_batch> b = parse_one(in, len, true, dict, dict_len);
         const Batch::PStream& p = b->impl.ps[0];
         if (consumed) *consumed = (size_t)p.consumed;
         *status = p.status != 0 ? D4G_STREAM_PARSE_ERROR : D4G_STREAM_UNCHANGED;
@@ -655,6 +701,11 @@ int d4g_inflate(const uint8_t* in, size_t len, uint8_t** out, size_t* out_len, s
 static_assert(D4G_FOUND_KIND_ZLIB == D4G_FOUND_ZLIB && D4G_FOUND_KIND_GZIP == D4G_FOUND_GZIP, "kind values");
 int d4g_find_streams(size_t n, const uint8_t* const* file, const size_t* file_len, const d4g_find_options* opt, d4g_found_stream** found,
                      size_t* n_found, d4g_find_stats* stats) {
+    return d4g_find_streams_dict(n, file, file_len, opt, 0, nullptr, nullptr, found, n_found, stats);
+}
+
+int d4g_find_streams_dict(size_t n, const uint8_t* const* file, const size_t* file_len, const d4g_find_options* opt, size_t n_dict,
+                          const uint8_t* const* dict, const size_t* dict_len, d4g_found_stream** found, size_t* n_found, d4g_find_stats* stats) {
     if (!found || !n_found || (n && (!file || !file_len))) return fail(D4G_ERR_ARG, "null argument");
     const int known = (1 << D4G_FOUND_ZLIB) | (1 << D4G_FOUND_GZIP);
     if (opt && ((opt->kinds & ~known) || opt->min_decoded < 0)) return fail(D4G_ERR_ARG, "bad find options");
@@ -663,9 +714,12 @@ int d4g_find_streams(size_t n, const uint8_t* const* file, const size_t* file_le
         if (file_len[i] && !file[i]) return fail(D4G_ERR_ARG, "null argument");
         if (file_len[i] >= ((size_t)1 << 31)) return fail(D4G_ERR_ARG, "a file of 2 GiB or more");
     }
+    if (n_dict >= 0x7fffff) return fail(D4G_ERR_ARG, "too many dictionaries");
+    const std::string why = dict_refusal(0, n_dict, dict, dict_len, nullptr);
+    if (!why.empty()) return fail(D4G_ERR_ARG, why);
     return api(nullptr, [&] {
         FindRun R;
-        R.run(n, file, file_len, opt ? opt->kinds : 0, opt ? opt->min_decoded : 0);
+        R.run(n, file, file_len, opt ? opt->kinds : 0, opt ? opt->min_decoded : 0, n_dict, dict, dict_len);
         d4g_found_stream* out = nullptr;
         if (!R.found.empty()) {
             out = (d4g_found_stream*)malloc(R.found.size() * sizeof(d4g_found_stream));
@@ -1139,6 +1193,8 @@ int recompress_batch(d4g_batch& b, int mode, int iter, bool merge) {
     std::string why;
     if (mode != D4G_MODE_NONE && !mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
     Batch& A = b.impl;
+    if (mode != D4G_MODE_NONE && A.has_dictionary())
+        return fail(D4G_ERR_ARG, "the batch holds streams with a preset dictionary and the encoders take no dictionary: only mode NONE runs on it");
     const size_t n = A.streams.size();
     double t0 = now_ms();
     // container.optimise(mergeBlocks) — CMDUtil.java:70.  In a Zopfli mode only the parse happens here: the search of the originals

@@ -93,6 +93,9 @@ typedef struct d4g_stats {
     /* header scan: scan_candidates = bit positions with a plausible prolog and a complete code-length code; scan_kept = those
      * whose coded code lengths also give complete codes, which is what the probe is run on */
     int64_t scan_kept;
+    /* preset dictionaries (d4g_batch_create_dict): streams of the batch that have one (of non-zero length), and the bytes of
+     * dictionary tails uploaded — each dictionary once, its last 32 768 bytes at most, however many streams name it */
+    int64_t dict_streams, dict_bytes;
 } d4g_stats;
 
 /* Select the HIP device (one process per GPU) and create the library's stream.
@@ -115,6 +118,24 @@ const char* d4g_last_error(void);
  * (parse -> optimise -> [mergeBlocks] -> write) with inputs and outputs resident in HBM. */
 d4g_batch* d4g_batch_create(size_t n, const uint8_t* const* in, const size_t* in_len);
 d4g_batch* d4g_batch_create_on(int context, size_t n, const uint8_t* const* in, const size_t* in_len);
+/* ---- preset dictionaries: streams written with deflateSetDictionary / Deflater.setDictionary / zdict= ----
+ * The rule is zlib's inflateSetDictionary on a raw stream.  Let L = min(dict_len, 32768): only the dictionary's last L bytes
+ * count.  At decoded position p a distance d is valid iff d <= p + L, and the byte at q = p - d < 0 is dict_tail[L + q]; a
+ * copy may begin in the dictionary and run on into the stream's own bytes, overlapping itself like any copy.  The dictionary
+ * is not part of the decoded bytes: decoded_len, CRC-32, Adler-32, ISIZE, decoded_offset, d4g_block_info.decoded_len and
+ * bytes_decoded do not count it.  A dictionary of length 0, or none, is d4g_batch_create exactly: the same kernels, the same
+ * device blocks.
+ * dict_of[i] = index of stream i's dictionary, -1: none; dict_of NULL or n_dict 0: d4g_batch_create.  Every dictionary's tail
+ * is uploaded once per batch.  Refused (NULL, D4G_ERR_ARG in d4g_last_error's sense): a dict_of value outside -1..n_dict-1, a
+ * NULL dictionary with a length.
+ * Everything a batch can be asked works on such a batch — parse, run with and without mergeBlocks, outputs, decoded bytes,
+ * checksums, block info, parse errors (DISTANCE_TOO_FAR by the rule above), recovery, and verification, which parses the
+ * written stream again with the same dictionary — except d4g_batch_run_recompress with a mode above NONE: the LZ77 and Zopfli
+ * encoders take no dictionary, so a batch that holds any dictionary stream is refused there with D4G_ERR_ARG. */
+d4g_batch* d4g_batch_create_dict(size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict, const uint8_t* const* dict,
+                                 const size_t* dict_len, const int32_t* dict_of);
+d4g_batch* d4g_batch_create_dict_on(int context, size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict,
+                                    const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of);
 int d4g_batch_run(d4g_batch* b, int merge_blocks);
 /* status: D4G_STREAM_*; saved_bits = DeflateStream.optimise(mergeBlocks) (B/deflate/DeflateStream.java:496);
  * out_len = bytes DeflateStream.asBytes() (:652) would return; consumed = input bytes parse() read
@@ -291,6 +312,7 @@ int d4g_batch_block_info(d4g_batch* b, size_t i, int which /* 0 = input as parse
  *   LITLEN_SYMBOL     no literal/length code matches, or symbol 286 / 287      first bit of the token      the symbol, -1: no code
  *   DIST_SYMBOL       no distance code matches, or symbol 30 / 31              first bit of the token      the symbol, -1: no code
  *   DISTANCE_TOO_FAR  a back-reference reaches before the first decoded byte   first bit of the token      the distance
+ *                     (a stream with a preset dictionary: before the dictionary's last 32 768 bytes)
  * block = blocks parsed before the failing one, block_bit_pos = its first header bit, decoded_offset = bytes of the whole
  * stream decoded before the failing element.  Whether a stream parses is decided by the parser alone; the diagnosis runs
  * only when asked (the first question about a batch diagnoses all its failed streams in one kernel launch and keeps the
@@ -341,8 +363,12 @@ int d4g_recover_streams(size_t n, const uint8_t* const* in, const size_t* in_len
  * parsed, decoded and checked against their own trailer there, so a reported stream is wrong only when a 32-bit checksum
  * matches by accident.  What counts as a stream:
  *   zlib at offset o: o + 2 <= len; CMF = file[o], FLG = file[o+1]; (CMF & 15) == 8; (CMF >> 4) <= 7;
- *     (CMF * 256 + FLG) % 31 == 0; (FLG & 0x20) == 0 (no preset dictionary).  The payload starts at o + 2.  The trailer is
+ *     (CMF * 256 + FLG) % 31 == 0; (FLG & 0x20) == 0.  The payload starts at o + 2.  The trailer is
  *     the 4 bytes right after the consumed payload, inside the file, big-endian, equal to the Adler-32 of the decoded bytes.
+ *     With FDICT set ((FLG & 0x20) != 0) the header is a stream only for d4g_find_streams_dict, and only when o + 6 <= len and
+ *     the four bytes after FLG (DICTID, big-endian) equal the Adler-32 of one of the caller's dictionaries, the first in list
+ *     order: the payload then starts at o + 6, is parsed with that dictionary, total_len counts the 6 header bytes and
+ *     `dictionary` reports 1 + the dictionary's index.  gzip has no dictionaries.
  *   gzip at offset o: the header bytes are 1f 8b 08 and FLG = file[o+3] has (FLG & 0xE0) == 0.  The 10 fixed header bytes
  *     are followed, in RFC 1952 order, by FEXTRA (XLEN, little-endian 16 bits, plus that many bytes), FNAME
  *     (zero-terminated), FCOMMENT (zero-terminated) and FHCRC (2 bytes, skipped and not checked — as
@@ -350,7 +376,8 @@ int d4g_recover_streams(size_t n, const uint8_t* const* in, const size_t* in_len
  *     after the payload: CRC-32, little-endian, equal to that of the decoded bytes, then ISIZE, little-endian, equal to
  *     decoded_len mod 2^32.
  *   payload: it parses by the library's own parser rule, exactly as d4g_inflate would on file[payload_offset:], through a
- *     block with BFINAL set; no back-reference reaches before payload_offset; decoded_len >= min_decoded (default 0).
+ *     block with BFINAL set; no back-reference reaches before payload_offset (with FDICT: before the dictionary's last
+ *     32 768 bytes, which lie in front of it); decoded_len >= min_decoded (default 0).
  *     Raw DEFLATE without a wrapper is not searched for: nothing confirms it.
  *   overlap: within a file, in ascending offset, a confirmed stream is reported iff offset >= the end (offset + total_len)
  *     of the last reported stream.  So a wrapper that lies inside another stream's compressed bytes, or inside its header
@@ -367,7 +394,7 @@ typedef struct d4g_found_stream {
     int64_t total_len;           /* header + payload + trailer */
     int64_t decoded_len, size_bits;   /* size_bits = DeflateStream.getSizeBits */
     uint32_t crc32, adler32;     /* of the decoded bytes, both always filled */
-    int32_t n_blocks, reserved;
+    int32_t n_blocks, dictionary; /* dictionary: 0 none, else 1 + index of the preset dictionary (d4g_find_streams_dict) */
 } d4g_found_stream;
 typedef struct d4g_find_options { int32_t kinds /* OR of (1 << D4G_FOUND_*), 0 = all */, reserved; int64_t min_decoded; } d4g_find_options;
 typedef struct d4g_find_stats {
@@ -378,6 +405,9 @@ typedef struct d4g_find_stats {
 } d4g_find_stats;
 int d4g_find_streams(size_t n, const uint8_t* const* file, const size_t* file_len, const d4g_find_options* opt /* NULL: defaults */,
                      d4g_found_stream** found /* d4g_free */, size_t* n_found, d4g_find_stats* stats /* may be NULL */);
+/* d4g_find_streams plus zlib headers with FDICT whose DICTID names one of n_dict dictionaries; n_dict == 0: d4g_find_streams */
+int d4g_find_streams_dict(size_t n, const uint8_t* const* file, const size_t* file_len, const d4g_find_options* opt, size_t n_dict,
+                          const uint8_t* const* dict, const size_t* dict_len, d4g_found_stream** found, size_t* n_found, d4g_find_stats* stats);
 
 /* ---- one-shot wrappers ----
  * Deft.optimiseDeflateStream for n streams: out[i]/out_len[i] are set only when status[i] ==
@@ -394,6 +424,9 @@ int d4g_size_bits_fallback(const uint8_t* in, size_t len, int64_t* bits);
 /* DeflateStream.parse + getUncompressedData; *consumed = bytes read.  Returns D4G_ERR_ARG-style <0 only on
  * library failure; *status receives D4G_STREAM_PARSE_ERROR for a malformed stream. */
 int d4g_inflate(const uint8_t* in, size_t len, uint8_t** out, size_t* out_len, size_t* consumed, int32_t* status);
+/* the same against a preset dictionary (d4g_batch_create_dict states the rule); dict_len 0: d4g_inflate */
+int d4g_inflate_dict(const uint8_t* in, size_t len, const uint8_t* dict, size_t dict_len, uint8_t** out, size_t* out_len, size_t* consumed,
+                     int32_t* status);
 void d4g_free(void* p);
 
 #ifdef __cplusplus
