@@ -18,9 +18,9 @@
 
 // The emulator's deliberate algorithm swaps.  Each wave collective costs the emulator a fiber switch per lane, so where a
 // wave-wide builder has a one-lane equivalent with the same result, the emulator runs the one-lane form to keep test time
-// down: the search's Huffman trees (d4f_wave_tree, w0_build_cl_tree, the literal/length and distance trees of
-// wg_recode_huffman) and Zopfli's package-merge (zf_dynamic_lengths).  The GPU always runs the wave-wide builders;
-// -DD4G_SIM_WAVE_HEAP (tests/hostsim/build.sh waveheap) runs them in the emulator too.
+// down: the search's Huffman trees (d4g_wave_tree, d4g_rebuild.h) and Zopfli's package-merge (zf_pm, d4g_zopfli.h), the two
+// places that test the switch.  The GPU always runs the wave-wide builders; -DD4G_SIM_WAVE_HEAP (tests/hostsim/build.sh
+// waveheap) runs them in the emulator too.
 #if defined(D4G_HOSTSIM) && !defined(D4G_SIM_WAVE_HEAP)
 #define D4G_SERIAL_TREES
 #endif

@@ -165,8 +165,8 @@ D4G_DEV int d4f_qoff(int q) {
 enum { D4F_H_OPT = 1, D4F_H_POST = 2, D4F_H_PRUNE = 3 };
 
 // scratch of one Huffman-rebuild task (one wave): the three trees are built one after the other in the same memory
-typedef TreeMem<uint64_t, uint16_t, D4G_NLIT, 16, true> D4FLitTree;    // (depth scratch of the limiter path overlays the queue)
-typedef TreeMem<uint64_t, uint16_t, D4G_NDIST, 16, true> D4FDistTree;
+typedef D4GFusedTrees::Lit D4FLitTree;
+typedef D4GFusedTrees::Dist D4FDistTree;
 struct D4FTreeScr {
     alignas(16) unsigned char tree[(D4FLitTree::bytes(1) + 15) & ~15];       // literal/length tree, then the code-length tree
     alignas(16) unsigned char treeD[(D4FDistTree::bytes(1) + 15) & ~15];     // distance tree (built beside the literal/length tree)
@@ -294,17 +294,6 @@ D4G_DEV void d4f_push(int q, int v) {
     int k = atomicAdd(&F.qn[q], 1);
     if (k < d4f_qcap(q)) F.qAll[d4f_qoff(q) + k] = (uint16_t)v;
     else F.fallback = 1;
-}
-// a wave's tree (all lanes call): the wave-wide JDK heap on the GPU; the emulator runs the one-lane form unless asked
-template <int NREG, typename TM, typename FreqFn, typename OutFn>
-__device__ __forceinline__ int d4f_wave_tree(TM& tm, int numSymbols, int limit, FreqFn freq, OutFn out) {
-#ifndef D4G_SERIAL_TREES
-    return d4g_build_tree_wave64<NREG>(tm, numSymbols, limit, freq, out);
-#else
-    int err = 0;
-    if ((threadIdx.x & 63) == 0) err = d4g_build_tree(tm, 1, 0, numSymbols, limit, freq, out);
-    return __shfl(err, 0);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1315,31 +1304,20 @@ D4F_TASK void d4f_least_task(int idx) {
 // ---------------------------------------------------------------------------------------
 // Header pieces by one wave: the forms of d4g_header.h on a task's scratch
 // ---------------------------------------------------------------------------------------
-// code-length code of clFreq — Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134: the fused executor's code-length-tree step
-D4G_DEV int d4f_wave_cl_tree(unsigned char* treeMem, const uint32_t* clFreq, uint8_t* clLen) {
-    TreeMem<uint32_t, uint8_t, 20> tm;
-    tm.carve(treeMem, 1);
-    const int lane = threadIdx.x & 63;
-    if (lane < 19) clLen[lane] = 0;
-    d4g_wave_sync();
-    int err = d4f_wave_tree<1>(tm, 19, 7, [&](int i) { return (unsigned)clFreq[i]; }, [&](int v, int len) { clLen[v] = (uint8_t)len; });
-    d4g_wave_sync();
-    return err;
-}
 // rewriteHeader with the default flags — DeflateBlockHuffman.java:484-577: pairs, code-length code, size; nCl trimmed.
 // lens = litLen[288] + distLen[32].
 __device__ __forceinline__ int d4f_wave_default_header(const uint8_t* lens, int nLit, int nDist, uint16_t* pairs, uint32_t* clFreq, uint8_t* clLen,
                                                         unsigned char* treeMem, int& nPairsOut, int& nClOut, int& bitsOut) {
     d4g_wave_clear_cl_freq(clFreq);
     return d4g_wave_pack_header(nLit + nDist, [&](int i) { return i < nLit ? (int)lens[i] : (int)lens[D4G_NLIT + i - nLit]; }, F_DEFAULT, pairs, clFreq, clLen,
-                                [&](const uint32_t* f, uint8_t* l) { return d4f_wave_cl_tree(treeMem, f, l); }, nPairsOut, nClOut, bitsOut);
+                                [&](const uint32_t* f, uint8_t* l) { return d4g_wave_cl_tree<D4GFusedTrees>(treeMem, f, l); }, nPairsOut, nClOut, bitsOut);
 }
 // recodeHeader — :579-629: new code-length code for the pairs as they stand
 D4G_DEV int d4f_wave_recode_header(D4FHdrScr& H) {
     int nCl, hb;
     d4g_wave_clear_cl_freq(H.clFreq);
     const int err = d4g_wave_recode_header(H.pairs, H.nPairs, H.clFreq, H.clLen, H.nCl,
-                                           [&](const uint32_t* f, uint8_t* l) { return d4f_wave_cl_tree(H.tree, f, l); }, nCl, hb);
+                                           [&](const uint32_t* f, uint8_t* l) { return d4g_wave_cl_tree<D4GFusedTrees>(H.tree, f, l); }, nCl, hb);
     d4g_wave_sync();
     if ((threadIdx.x & 63) == 0) { H.nCl = nCl; H.bits = hb; }
     d4g_wave_sync();
@@ -1404,13 +1382,9 @@ D4F_TASK void d4f_tree_lit(int slotIdx, int m) {      // the slot's first wave: 
     for (int i = lane; i < D4G_NLIT; i += 64) T.hist[i] = G.hist[(size_t)m * D4G_HIST + i];
     for (int i = lane; i < D4G_NLIT / 4; i += 64) ((uint32_t*)T.lens)[i] = 0;
     d4g_wave_sync();
-    int ml = 0;
-    for (int i = lane; i < 286; i += 64) if (T.hist[i]) ml = i + 1 > ml ? i + 1 : ml;
-    const int lastLit = wave_max_i32(ml);
-    D4FLitTree tm;
-    tm.carve(T.tree, 1);
-    const int err = d4f_wave_tree<(D4G_NLIT + 63) / 64>(tm, lastLit, 15, [&](int i) { return T.hist[i]; }, [&](int v, int len) { T.lens[v] = (uint8_t)len; });
-    if (lane == 0) { T.nLit = lastLit; T.err = err; T.m = m; }
+    int nLit;
+    const int err = d4g_wave_lit_tree<D4GFusedTrees>(T.hist, T.lens, T.tree, nLit);
+    if (lane == 0) { T.nLit = nLit; T.err = err; T.m = m; }
     d4g_wave_sync();
 }
 D4F_TASK void d4f_tree_dist(int slotIdx, int m) {     // the slot's second wave: distance tree
@@ -1420,20 +1394,8 @@ D4F_TASK void d4f_tree_dist(int slotIdx, int m) {     // the slot's second wave:
     const int lane = threadIdx.x & 63;
     if (lane < D4G_NDIST) { T.hist[D4G_NLIT + lane] = G.hist[(size_t)m * D4G_HIST + D4G_NLIT + lane]; T.lens[D4G_NLIT + lane] = 0; }
     d4g_wave_sync();
-    int md = 0;
-    if (lane < 30 && T.hist[D4G_NLIT + lane]) md = lane + 1;
-    const int lastDist = wave_max_i32(md);
-    const bool used = lane < lastDist && T.hist[D4G_NLIT + lane] != 0;
-    const int nz = __popcll(d4g_ballot(used));
-    int nDist, err = 0;
-    if (lastDist == 0) nDist = 1;                                  // handleZero: new HuffmanTable(1)
-    else if (nz <= 1) { nDist = lastDist; if (lane == 0) T.lens[D4G_NLIT + lastDist - 1] = 1; }   // handleOne: one used distance code, length 1
-    else {
-        D4FDistTree tm;
-        tm.carve(T.treeD, 1);
-        err = d4f_wave_tree<1>(tm, lastDist, 15, [&](int i) { return T.hist[D4G_NLIT + i]; }, [&](int v, int len) { T.lens[D4G_NLIT + v] = (uint8_t)len; });
-        nDist = lastDist;
-    }
+    int nDist;
+    const int err = d4g_wave_dist_tree<D4GFusedTrees>(T.hist + D4G_NLIT, T.lens + D4G_NLIT, T.treeD, nDist);
     if (lane == 0) { T.nDist = nDist; T.pad = err; }
     d4g_wave_sync();
 }
@@ -1443,13 +1405,7 @@ D4F_TASK void d4f_tree_bits(int slotIdx) {            // wave A again, once both
     const int lane = threadIdx.x & 63;
     // Σ token bits from the histogram — recodeToHuffmanInternal, :759-770
     long long v = 0;
-    for (int i = lane; i < D4G_HIST; i += 64) {
-        const unsigned h = T.hist[i];
-        if (h) {
-            if (i < D4G_NLIT) v += (long long)h * (T.lens[i] + (i >= 257 ? d4g_lsym_ebits(i) : 0));
-            else v += (long long)h * (T.lens[i] + d4g_dsym_ebits(i - D4G_NLIT));
-        }
-    }
+    for (int i = lane; i < D4G_HIST; i += 64) v += d4g_slot_token_bits(i, T.hist[i], T.lens, T.lens + D4G_NLIT);
     v = wave_sum_i64(v);
     if (lane == 0) { T.err |= T.pad; T.litlen = v; }
     d4g_wave_sync();

@@ -190,6 +190,7 @@ struct Batch {
     void ensure_level_tables();
     D4FParams fused_params(int maxRounds, D4GRoundResult* results, int32_t* info);
     void count_state_launch(const int32_t* blk, size_t n);
+    std::pair<std::vector<size_t>, std::vector<size_t>> split_for_fused(const std::vector<int>& act) const;
     std::vector<D4GRoundResult> run_round(const std::vector<int>& act);
     bool run_cluster(int blk, D4GRoundResult* out);
     std::vector<std::vector<D4GRoundResult>> run_fused(const std::vector<int>& act, int maxRounds);

@@ -36,21 +36,32 @@ inline void Batch::count_state_launch(const int32_t* blk, size_t n) {
     for (size_t i = 0; i < n; i++) { stats.state_tokens_per_round += hBlocks[blk[i]].tokCount; stats.state_bytes_per_round += hBlocks[blk[i]].uLen; }
 }
 
+// the elements of v at the positions pos
+template <typename T>
+static std::vector<T> picked(const std::vector<T>& v, const std::vector<size_t>& pos) {
+    std::vector<T> out;
+    out.reserve(pos.size());
+    for (size_t p : pos) out.push_back(v[p]);
+    return out;
+}
+// The positions of `act` whose blocks the fused executor takes, one workgroup each, and the others.  Blocks of up to 16384
+// back-references always; longer ones when there are many of them, which still fill the device one workgroup each (a few
+// long blocks are left to an executor that gives each the whole device).
+inline std::pair<std::vector<size_t>, std::vector<size_t>> Batch::split_for_fused(const std::vector<int>& act) const {
+    std::pair<std::vector<size_t>, std::vector<size_t>> pos;
+    size_t nLong = 0;
+    for (int k : act) nLong += hBlocks[k].refCount > (1LL << 14);
+    for (size_t i = 0; i < act.size(); i++) (hBlocks[act[i]].refCount <= fused_max_refs(nLong) ? pos.first : pos.second).push_back(i);
+    return pos;
+}
+
 // One optimiseBlock call per block of `act`: the fused and cluster executors take the blocks they can hold, the level
 // executor the rest.
 inline std::vector<D4GRoundResult> Batch::run_round(const std::vector<int>& act) {
     if (!exec_fused()) return run_round_levels(act);
     std::vector<D4GRoundResult> res(act.size());
-    std::vector<int> small, big;
-    std::vector<size_t> smallPos, bigPos;
-    // Blocks of up to 16384 back-references: one workgroup each (fused).  Longer ones: when there are many of them they
-    // still fill the device one workgroup each; a few long blocks get the whole device one after the other (cluster).
-    size_t nLong = 0;
-    for (int k : act) nLong += hBlocks[k].refCount > (1LL << 14);
-    for (size_t i = 0; i < act.size(); i++) {
-        if (hBlocks[act[i]].refCount <= fused_max_refs(nLong)) { small.push_back(act[i]); smallPos.push_back(i); }
-        else { big.push_back(act[i]); bigPos.push_back(i); }
-    }
+    auto [smallPos, bigPos] = split_for_fused(act);
+    std::vector<int> small = picked(act, smallPos), big = picked(act, bigPos);
     if (!small.empty()) {
         std::vector<std::vector<D4GRoundResult>> ch = run_fused(small, 1);
         for (size_t i = 0; i < small.size(); i++) res[smallPos[i]] = ch[i].at(0);
@@ -300,21 +311,14 @@ inline void Batch::phase1() {
         }
     }
     if (exec_fused()) {   // all rounds of a block inside one workgroup; blocks the fused executor does not take follow below
-        std::vector<int> fa, rest;
-        std::vector<std::pair<int, int>> fo, ro;
-        size_t nLong = 0;
-        for (int k : act) nLong += hBlocks[k].refCount > (1LL << 14);
-        for (size_t i = 0; i < act.size(); i++) {
-            if (hBlocks[act[i]].refCount <= fused_max_refs(nLong)) { fa.push_back(act[i]); fo.push_back(owner[i]); }
-            else { rest.push_back(act[i]); ro.push_back(owner[i]); }
-        }
-        if (!fa.empty()) {
-            std::vector<std::vector<D4GRoundResult>> ch = run_fused(fa, 1 << 20);
-            for (size_t i = 0; i < fa.size(); i++) streams[fo[i].first].blocks[fo[i].second].chain = ch[i];
+        const auto [fusedPos, restPos] = split_for_fused(act);
+        if (!fusedPos.empty()) {
+            std::vector<std::vector<D4GRoundResult>> ch = run_fused(picked(act, fusedPos), 1 << 20);
+            for (size_t i = 0; i < fusedPos.size(); i++) streams[owner[fusedPos[i]].first].blocks[owner[fusedPos[i]].second].chain = ch[i];
             stats.rounds++;
         }
-        act.swap(rest);
-        owner.swap(ro);
+        act = picked(act, restPos);
+        owner = picked(owner, restPos);
     }
     // fixpoint rounds: every block follows its own chain of strictly improving Huffman states
     while (!act.empty()) {

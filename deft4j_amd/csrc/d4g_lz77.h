@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "d4g_device.h"
+#include "d4g_sort.h"
 
 #define LZ_SORT_BLOCK 32768
 #define LZ_CHUNK 2048          // positions per parse chunk (one wave)
@@ -91,7 +92,7 @@ D4G_DEV int lz_block_inserted(long long len, int blk) {   // positions of sort b
 // ---------------------------------------------------------------------------------------------------------------------
 // k_lz_sort: stable counting sort of one sort block's positions by hash.
 // ---------------------------------------------------------------------------------------------------------------------
-#define LZ_SORT_THREADS 512
+#define LZ_SORT_THREADS D4G_SORT_THREADS
 __global__ void __launch_bounds__(LZ_SORT_THREADS) k_lz_sort(const LzStream* streams, const LzSortJob* jobs, uint16_t* S16, uint16_t* rank16,
                                                              uint16_t* bstart) {
     __shared__ uint16_t tbl[32768];          // counts, then bucket cursors
@@ -99,87 +100,9 @@ __global__ void __launch_bounds__(LZ_SORT_THREADS) k_lz_sort(const LzStream* str
     const LzSortJob job = jobs[blockIdx.x];
     const LzStream st = streams[job.stream];
     const long long p0 = (long long)job.blk * LZ_SORT_BLOCK;
-    const int nIns = lz_block_inserted(st.len, job.blk);
-    const int tid = threadIdx.x, lane = tid & 63;
     const uint8_t* d = st.data + p0;
-    unsigned* tw = (unsigned*)tbl;
-    for (int i = tid; i < 16384; i += LZ_SORT_THREADS) tw[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < nIns; i += LZ_SORT_THREADS) {
-        unsigned h = lz_hash3(d[i], d[i + 1], d[i + 2]);
-        atomicAdd(tw + (h >> 1), 1u << ((h & 1) * 16));   // two 16-bit counters per word; a count is at most 32768
-    }
-    __syncthreads();
-    // exclusive scan of the 32768 counters: 64 per thread
-    unsigned sum = 0;
-    for (int k = 0; k < 32; k++) { unsigned w = tw[tid * 32 + k]; sum += (w & 0xffffu) + (w >> 16); }
-    part[tid] = sum;
-    __syncthreads();
-    if (tid < 64) {   // scan of 512 partial sums by one wave: 8 per lane
-        unsigned loc[8], s = 0;
-        for (int k = 0; k < 8; k++) { loc[k] = s; s += part[tid * 8 + k]; }
-        unsigned inc = s;
-        for (int dd = 1; dd < 64; dd <<= 1) { unsigned o = __shfl_up(inc, dd); if (lane >= dd) inc += o; }
-        unsigned excl = inc - s;
-        for (int k = 0; k < 8; k++) part[tid * 8 + k] = excl + loc[k];
-    }
-    __syncthreads();
-    {
-        unsigned run = part[tid];
-        uint16_t* bs = bstart + ((long long)st.sortBlock0 + job.blk) * LZ_SORT_BLOCK;
-        for (int k = 0; k < 32; k++) {
-            unsigned w = tw[tid * 32 + k];
-            unsigned a = run, b = run + (w & 0xffffu);
-            run = b + (w >> 16);
-            tw[tid * 32 + k] = (a & 0xffffu) | (b << 16);
-            bs[tid * 64 + 2 * k] = (uint16_t)a;
-            bs[tid * 64 + 2 * k + 1] = (uint16_t)b;
-        }
-    }
-    __syncthreads();
-    if (tid >= 64) return;
-    // Placement in position order by one wave, 64 positions per step.  Lanes whose hash is unique within the step take
-    // their bucket's cursor directly; lanes that share a hash are found by a write / read-back of lane tags in the
-    // cursor table itself and ranked by ballots (a handful of groups per step on text).
-    volatile uint16_t* vt = tbl;
-    uint16_t* Sout = S16 + st.posBase + p0;
-    uint16_t* Rout = rank16 + st.posBase + p0;
-    const unsigned long long below = lane ? (~0ULL >> (64 - lane)) : 0ULL;
-    for (int i0 = 0; i0 < nIns; i0 += 64) {
-        const int i = i0 + lane;
-        const bool valid = i < nIns;
-        unsigned h = 0;
-        if (valid) h = lz_hash3(d[i], d[i + 1], d[i + 2]);
-        unsigned cur = valid ? vt[h] : 0u;
-        d4g_wave_sync();
-        if (valid) vt[h] = (uint16_t)(0x8000u | (unsigned)lane);
-        d4g_wave_sync();
-        unsigned w = valid ? vt[h] : 0u;
-        d4g_wave_sync();
-        if (valid && (w & 63u) != (unsigned)lane) vt[h] = (uint16_t)(0xC000u | (unsigned)lane);
-        d4g_wave_sync();
-        unsigned w2 = valid ? vt[h] : 0u;
-        d4g_wave_sync();
-        bool dup = valid && (w2 & 0x4000u);
-        unsigned rank = cur;
-        if (valid && !dup) vt[h] = (uint16_t)(cur + 1);
-        unsigned long long rem = __ballot(dup);
-        while (rem) {
-            int leader = __ffsll((long long)rem) - 1;
-            unsigned hh = __shfl(h, leader);
-            unsigned long long m = __ballot(dup && h == hh);
-            if (dup && h == hh) {
-                rank = cur + (unsigned)__popcll(m & below);
-                if ((m >> lane) == 1ULL) vt[h] = (uint16_t)(cur + (unsigned)__popcll(m));   // the group's last lane
-            }
-            rem &= ~m;
-        }
-        d4g_wave_sync();
-        if (valid) {
-            Rout[i] = (uint16_t)rank;
-            Sout[rank] = (uint16_t)i;
-        }
-    }
+    d4g_block_sort_by_key([&](int i) { return lz_hash3(d[i], d[i + 1], d[i + 2]); }, lz_block_inserted(st.len, job.blk), tbl, part,
+                          bstart + ((long long)st.sortBlock0 + job.blk) * LZ_SORT_BLOCK, S16 + st.posBase + p0, rank16 + st.posBase + p0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
 // d4g_ops.h — workgroup-cooperative operations on one candidate state held in LDS, and
-// the kernels that execute the candidate-search program.  See d4g_device.h for the pieces and d4g_header.h for the
-// header operations' one-wave forms.
+// the kernels that execute the candidate-search program.  See d4g_device.h for the pieces, d4g_header.h for the
+// header operations' one-wave forms and d4g_rebuild.h for the Huffman rebuild's.
 #pragma once
 #include "d4g_header.h"
+#include "d4g_rebuild.h"
 
 #ifdef D4G_PROFILE_OPS
 __device__ unsigned long long d4g_dbg_pass[4];  // computed replace passes: lookup cycles, loop cycles, count, records
@@ -91,9 +92,9 @@ struct D4GLds {
     D4GState st;
     long long red[32];
     int misc[64];
-    alignas(16) unsigned char treeLit[TreeMem<uint64_t, uint16_t, D4G_NLIT>::bytes(1)];
-    alignas(16) unsigned char treeDist[TreeMem<uint64_t, uint16_t, D4G_NDIST>::bytes(1)];
-    alignas(16) unsigned char treeCl[TreeMem<uint32_t, uint8_t, 20>::bytes(1)];
+    alignas(16) unsigned char treeLit[D4GLevelTrees::Lit::bytes(1)];
+    alignas(16) unsigned char treeDist[D4GLevelTrees::Dist::bytes(1)];
+    alignas(16) unsigned char treeCl[D4GClTree::bytes(1)];
     uint32_t clFreq[20];
     uint16_t litCost[256];    // bits of each literal under the state's code; absent symbols cost D4G_NO_CODE
 };
@@ -717,30 +718,6 @@ __device__ __forceinline__ void wg_least(D4GLds* L, const D4GCtx& c, const D4GBl
 // ---------------------------------------------------------------------------------------
 // Header operations on the LDS state
 // ---------------------------------------------------------------------------------------
-// code-length code of clFreq — Huffman.ofRLEPacked, B/huffman/Huffman.java:117-134 — by one lane: what
-// w0_build_cl_tree runs under D4G_SERIAL_TREES
-D4G_DEV int t0_build_cl_tree(unsigned char* treeMem, const uint32_t* clFreq, uint8_t* clLen) {
-    TreeMem<uint32_t, uint8_t, 20> tm;
-    tm.carve(treeMem, 1);
-    for (int i = 0; i < 19; i++) clLen[i] = 0;
-    return d4g_build_tree(tm, 1, 0, 19, 7, [&](int i) { return (unsigned)clFreq[i]; }, [&](int v, int len) { clLen[v] = (uint8_t)len; });
-}
-
-// the same by all lanes of wave 0: the level executor's code-length-tree step for the forms of d4g_header.h
-D4G_DEV int w0_build_cl_tree(unsigned char* treeMem, const uint32_t* clFreq, uint8_t* clLen) {
-    int err = 0;
-#ifndef D4G_SERIAL_TREES
-    TreeMem<uint32_t, uint8_t, 20> tm;
-    tm.carve(treeMem, 1);
-    if ((threadIdx.x & 63) < 19) clLen[threadIdx.x & 63] = 0;
-    err = d4g_build_tree_wave<1>(tm, 19, 7, [&](int i) { return (unsigned)clFreq[i]; }, [&](int v, int len) { clLen[v] = (uint8_t)len; });
-#else
-    if ((threadIdx.x & 63) == 0) err = t0_build_cl_tree(treeMem, clFreq, clLen);
-#endif
-    d4g_wave_sync();
-    return err;
-}
-
 // removeTrailingHeaderCodes — DeflateBlockHuffman.java:366-370, by all lanes of wave 0
 __device__ __forceinline__ void w0_remove_trailing_header_codes(D4GState* S) {
     if (S->type != D4G_DYNAMIC) return;
@@ -768,7 +745,7 @@ __device__ __forceinline__ void wg_rewrite_header(D4GLds* L, int flags) {
         const int nLit = S->nLit;
         const int err = d4g_wave_pack_header(nLit + S->nDist, [&](int i) { return i < nLit ? (int)S->litLen[i] : (int)S->distLen[i - nLit]; },
                                              flags, S->pairs, L->clFreq, S->clLen,
-                                             [&](const uint32_t* f, uint8_t* l) { return w0_build_cl_tree(L->treeCl, f, l); }, S->nPairs, nCl, hb);
+                                             [&](const uint32_t* f, uint8_t* l) { return d4g_wave_cl_tree<D4GLevelTrees>(L->treeCl, f, l); }, S->nPairs, nCl, hb);
         if (threadIdx.x == 0) {
             if (err) S->flags |= 0x100;
             S->nCl = nCl;
@@ -801,7 +778,7 @@ __device__ __forceinline__ void wg_recode_header(D4GLds* L) {
     if (threadIdx.x < 64) {
         int nCl, hb;
         const int err = d4g_wave_recode_header(S->pairs, S->nPairs, L->clFreq, S->clLen, S->nCl,
-                                               [&](const uint32_t* f, uint8_t* l) { return w0_build_cl_tree(L->treeCl, f, l); }, nCl, hb);
+                                               [&](const uint32_t* f, uint8_t* l) { return d4g_wave_cl_tree<D4GLevelTrees>(L->treeCl, f, l); }, nCl, hb);
         if (threadIdx.x == 0) {
             if (err) S->flags |= 0x100;
             S->nCl = nCl;
@@ -825,13 +802,7 @@ __device__ __forceinline__ void wg_litlen_bits_from_hist(D4GLds* L) {
     D4GState* S = &L->st;
     long long v = 0;
     __syncthreads();
-    for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) {
-        unsigned h = S->hist[i];
-        if (h) {
-            if (i < D4G_NLIT) v += (long long)h * (S->litLen[i] + (i >= 257 ? d4g_lsym_ebits(i) : 0));
-            else v += (long long)h * (S->distLen[i - D4G_NLIT] + d4g_dsym_ebits(i - D4G_NLIT));
-        }
-    }
+    for (int i = threadIdx.x; i < D4G_HIST; i += blockDim.x) v += d4g_slot_token_bits(i, S->hist[i], S->litLen, S->distLen);
     v = wg_sum_i64(v, L->red);
     if (threadIdx.x == 0) {
         S->sizeBits -= S->litlenBits;
@@ -912,80 +883,30 @@ __device__ __forceinline__ void wg_recode_huffman(D4GLds* L, D4GRecodeMemo* memo
 #ifdef D4G_PROFILE_OPS
     long long pt0 = clock64(), pt1 = 0, pt2 = 0;
 #endif
-    int ml = 0, md = 0;
-    for (int i = threadIdx.x; i < 286; i += blockDim.x)
-        if (S->hist[i]) ml = i + 1 > ml ? i + 1 : ml;
-    for (int i = threadIdx.x; i < 30; i += blockDim.x)
-        if (S->hist[D4G_NLIT + i]) md = i + 1 > md ? i + 1 : md;
-    int lastLit = wg_max_i32(ml, L->red);
-    int lastDist = wg_max_i32(md, L->red);
     for (int i = threadIdx.x; i < D4G_NLIT; i += blockDim.x) S->litLen[i] = 0;
     for (int i = threadIdx.x; i < D4G_NDIST; i += blockDim.x) S->distLen[i] = 0;
     __syncthreads();
-#ifndef D4G_SERIAL_TREES
     // wave 0 builds the literal/length tree while wave 1 (when there is one) builds the distance tree
     const int wv = d4g_uniform((int)(threadIdx.x >> 6)), ln = threadIdx.x & 63;
     if (wv == 0) {
-        TreeMem<uint64_t, uint16_t, D4G_NLIT> tm;
-        tm.carve(L->treeLit, 1);
-        int err = d4g_build_tree_wave<(D4G_NLIT + 63) / 64>(tm, lastLit, 15, [&](int i) { return S->hist[i]; },
-                                                            [&](int v, int len) { S->litLen[v] = (uint8_t)len; });
+        int nLit;
+        const int err = d4g_wave_lit_tree<D4GLevelTrees>(S->hist, S->litLen, L->treeLit, nLit);
         if (ln == 0) {
             if (err) atomicOr((unsigned*)&S->flags, 0x100u);
-            S->nLit = lastLit;
+            S->nLit = nLit;
         }
 #ifdef D4G_PROFILE_OPS
         pt1 = clock64();
 #endif
     }
     if (wv == (blockDim.x > 64 ? 1 : 0)) {
-        bool used = ln < lastDist && S->hist[D4G_NLIT + ln] != 0;
-        int nz = __popcll(d4g_ballot(used));
-        if (lastDist == 0) {  // handleZero: new HuffmanTable(1)
-            if (ln == 0) S->nDist = 1;
-        } else if (nz <= 1) {  // handleOne: one used distance code, length 1
-            if (ln == 0) { S->nDist = lastDist; S->distLen[lastDist - 1] = 1; }
-        } else {
-            TreeMem<uint64_t, uint16_t, D4G_NDIST> tm;
-            tm.carve(L->treeDist, 1);
-            int err = d4g_build_tree_wave<1>(tm, lastDist, 15, [&](int i) { return S->hist[D4G_NLIT + i]; },
-                                             [&](int v, int len) { S->distLen[v] = (uint8_t)len; });
-            if (ln == 0) {
-                if (err) atomicOr((unsigned*)&S->flags, 0x100u);
-                S->nDist = lastDist;
-            }
-        }
-    }
-#else
-    if (threadIdx.x == 0) {
-        TreeMem<uint64_t, uint16_t, D4G_NLIT> tm;
-        tm.carve(L->treeLit, 1);
-        int err = d4g_build_tree(tm, 1, 0, lastLit, 15, [&](int i) { return S->hist[i]; },
-                                 [&](int v, int len) { S->litLen[v] = (uint8_t)len; });
-        if (err) atomicOr((unsigned*)&S->flags, 0x100u);
-        S->nLit = lastLit;
-#ifdef D4G_PROFILE_OPS
-        pt1 = clock64();
-#endif
-    }
-    if (threadIdx.x == 64 || (blockDim.x <= 64 && threadIdx.x == 0)) {
-        int nz = 0;
-        for (int i = 0; i < lastDist; i++) nz += S->hist[D4G_NLIT + i] != 0;
-        if (lastDist == 0) {  // handleZero: new HuffmanTable(1)
-            S->nDist = 1;
-        } else if (nz <= 1) {  // handleOne: one used distance code, length 1
-            S->nDist = lastDist;
-            S->distLen[lastDist - 1] = 1;
-        } else {
-            TreeMem<uint64_t, uint16_t, D4G_NDIST> tm;
-            tm.carve(L->treeDist, 1);
-            int err = d4g_build_tree(tm, 1, 0, lastDist, 15, [&](int i) { return S->hist[D4G_NLIT + i]; },
-                                     [&](int v, int len) { S->distLen[v] = (uint8_t)len; });
+        int nDist;
+        const int err = d4g_wave_dist_tree<D4GLevelTrees>(S->hist + D4G_NLIT, S->distLen, L->treeDist, nDist);
+        if (ln == 0) {
             if (err) atomicOr((unsigned*)&S->flags, 0x100u);
-            S->nDist = lastDist;
+            S->nDist = nDist;
         }
     }
-#endif
     __syncthreads();
     if (threadIdx.x == 0) {
         if (S->type != D4G_DYNAMIC) { S->type = D4G_DYNAMIC; S->hdrBits = 0; S->nPairs = 0; S->nCl = 0; }

@@ -272,12 +272,12 @@ __global__ void __launch_bounds__(ZF_MATCH_THREADS) k_zf_match(const ZfInput* in
 
 // ---------------------------------------------------------------------------------------------------------------
 // The shared table (block end = input end) without the window scan: both hash chains are enumerated from buckets.
-// k_zf_sort orders the positions of a 32 Ki sort block by (key, position) — k_lz_sort's counting sort with the key read from an
+// k_zf_sort orders the positions of a 32 Ki sort block by (key, position) — the block sort of d4g_sort.h with the key read from an
 // array — once for the first hash and once for the second; a position's chain is then the part of its bucket below its own slot,
 // followed by the previous sort block's bucket from the top (positions further back are out of the window).
 // ---------------------------------------------------------------------------------------------------------------
 #define ZF_SORT_BLOCK 32768
-#define ZF_SORT_THREADS 512
+#define ZF_SORT_THREADS D4G_SORT_THREADS
 struct ZfSortJob { int32_t input, blk, kind, pad; };
 __global__ void __launch_bounds__(ZF_SORT_THREADS) k_zf_sort(const ZfInput* inputs, const ZfSortJob* jobs) {
     __shared__ uint16_t tbl[32768];          // counts, then bucket cursors
@@ -286,82 +286,9 @@ __global__ void __launch_bounds__(ZF_SORT_THREADS) k_zf_sort(const ZfInput* inpu
     const ZfInput in = inputs[job.input];
     const long long p0 = (long long)job.blk * ZF_SORT_BLOCK;
     const int nIns = (int)((in.n - p0) < ZF_SORT_BLOCK ? (in.n - p0) : ZF_SORT_BLOCK);
-    const int tid = threadIdx.x, lane = tid & 63;
     const uint16_t* key = (job.kind ? in.val2 : in.val) + p0;
-    unsigned* tw = (unsigned*)tbl;
-    for (int i = tid; i < 16384; i += ZF_SORT_THREADS) tw[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < nIns; i += ZF_SORT_THREADS) {
-        const unsigned h = key[i];
-        atomicAdd(tw + (h >> 1), 1u << ((h & 1) * 16));   // two 16-bit counters per word; a count is at most 32768
-    }
-    __syncthreads();
-    unsigned sum = 0;
-    for (int k = 0; k < 32; k++) { unsigned w = tw[tid * 32 + k]; sum += (w & 0xffffu) + (w >> 16); }
-    part[tid] = sum;
-    __syncthreads();
-    if (tid < 64) {
-        unsigned loc[8], sacc = 0;
-        for (int k = 0; k < 8; k++) { loc[k] = sacc; sacc += part[tid * 8 + k]; }
-        unsigned inc = sacc;
-        for (int dd = 1; dd < 64; dd <<= 1) { unsigned o = __shfl_up(inc, dd); if (lane >= dd) inc += o; }
-        const unsigned excl = inc - sacc;
-        for (int k = 0; k < 8; k++) part[tid * 8 + k] = excl + loc[k];
-    }
-    __syncthreads();
-    {
-        unsigned run = part[tid];
-        uint16_t* bs = in.bstart[job.kind] + (long long)job.blk * ZF_SORT_BLOCK;
-        for (int k = 0; k < 32; k++) {
-            const unsigned w = tw[tid * 32 + k];
-            const unsigned a = run, b = run + (w & 0xffffu);
-            run = b + (w >> 16);
-            tw[tid * 32 + k] = (a & 0xffffu) | (b << 16);
-            bs[tid * 64 + 2 * k] = (uint16_t)a;
-            bs[tid * 64 + 2 * k + 1] = (uint16_t)b;
-        }
-    }
-    __syncthreads();
-    if (tid >= 64) return;
-    // placement in position order by one wave, 64 positions per step (as k_lz_sort: lane tags find the lanes that share a key)
-    volatile uint16_t* vt = tbl;
-    uint16_t* Sout = in.sorted[job.kind] + p0;
-    uint16_t* Rout = in.rank[job.kind] + p0;
-    const unsigned long long below = lane ? (~0ULL >> (64 - lane)) : 0ULL;
-    for (int i0 = 0; i0 < nIns; i0 += 64) {
-        const int i = i0 + lane;
-        const bool valid = i < nIns;
-        const unsigned h = valid ? key[i] : 0u;
-        const unsigned cur = valid ? vt[h] : 0u;
-        d4g_wave_sync();
-        if (valid) vt[h] = (uint16_t)(0x8000u | (unsigned)lane);
-        d4g_wave_sync();
-        const unsigned w = valid ? vt[h] : 0u;
-        d4g_wave_sync();
-        if (valid && (w & 63u) != (unsigned)lane) vt[h] = (uint16_t)(0xC000u | (unsigned)lane);
-        d4g_wave_sync();
-        const unsigned w2 = valid ? vt[h] : 0u;
-        d4g_wave_sync();
-        const bool dup = valid && (w2 & 0x4000u);
-        unsigned rank = cur;
-        if (valid && !dup) vt[h] = (uint16_t)(cur + 1);
-        unsigned long long rem = __ballot(dup);
-        while (rem) {
-            const int leader = __ffsll((long long)rem) - 1;
-            const unsigned hh = __shfl(h, leader);
-            const unsigned long long m = __ballot(dup && h == hh);
-            if (dup && h == hh) {
-                rank = cur + (unsigned)__popcll(m & below);
-                if ((m >> lane) == 1ULL) vt[h] = (uint16_t)(cur + (unsigned)__popcll(m));
-            }
-            rem &= ~m;
-        }
-        d4g_wave_sync();
-        if (valid) {
-            Rout[i] = (uint16_t)rank;
-            Sout[rank] = (uint16_t)i;
-        }
-    }
+    d4g_block_sort_by_key([&](int i) { return (unsigned)key[i]; }, nIns, tbl, part, in.bstart[job.kind] + p0, in.sorted[job.kind] + p0,
+                          in.rank[job.kind] + p0);
 }
 
 // slot range [lo, hi) of `key`'s bucket in sort block `blk`
@@ -737,6 +664,16 @@ D4G_DEV void zf_pm_wave(const ZfPmRef& r, int maxbits, uint8_t* out) {
     }
     d4g_wave_sync();
 }
+// A wave's package-merge (all 64 lanes call): the wave-wide form on the GPU.  The emulator keeps its test time down with the
+// one-lane form unless asked (the switch of d4g_arch.h); the wave-wide one is compared with the oracle through
+// d4g_debug_zopfli_code_lengths in the same tests, and on the GPU every stream is.
+D4G_DEV void zf_pm(const ZfPmRef& r, int maxbits, uint8_t* out) {
+#ifndef D4G_SERIAL_TREES
+    zf_pm_wave(r, maxbits, out);
+#else
+    if ((threadIdx.x & 63) == 0) zf_pm_serial(r, maxbits, out);
+#endif
+}
 D4G_DEV void zf_patch_dist(uint8_t* d) {   // PatchDistanceCodesForBuggyDecoders
     int num = 0;
     for (int i = 0; i < 30; i++) { if (d[i]) num++; if (num >= 2) return; }
@@ -846,30 +783,16 @@ D4G_DEV long long zf_dynamic_lengths(ZfEvalLds& E, int* combo) {
     if (lane == 2) zf_optimize_rle(ZF_NUM_LL, E.llc2, E.good);
     if (lane == 3) zf_optimize_rle(ZF_NUM_D, E.dc2, E.goodD);
     d4g_wave_sync();
-    // two passes over one set of package-merge scratch: the plain counts' trees (lit/len on lane 0, distance on lane 1), then the
+    // two passes over one set of package-merge scratch: the plain counts' trees (lit/len, then distance), then the
     // smoothed counts' (a second set would let all four run at once, but the scratch is what bounds the waves per CU)
     for (int pass = 0; pass < 2; pass++) {
         const int mBig = zf_sort_leaves(pass ? E.llc2 : E.llc, ZF_NUM_LL, E.u.pm.big[0].w, E.u.pm.big[0].sym, E.u.pm.big[0].list[1]);
         const int mSmall = zf_sort_leaves(pass ? E.dc2 : E.dc, ZF_NUM_D, E.u.pm.small[0].w, E.u.pm.small[0].sym, E.u.pm.small[0].list[1]);
         d4g_wave_sync();
-#ifdef D4G_SERIAL_TREES
-        // (the CPU emulation keeps its test time down with the one-lane builder here; the wave-wide one is compared with the oracle
-        // through d4g_debug_zopfli_code_lengths in the same test, and on the GPU every stream is)
-        if (lane < 2) {
-            ZfPmRef r;
-            uint8_t* out;
-            if (lane == 0) { r = {E.u.pm.big[0].w, E.u.pm.big[0].sym, E.u.pm.big[0].list[0], E.u.pm.big[0].list[1], &E.u.pm.big[0].bits[0][0], 18, mBig, E.lvl[0]}; out = pass ? E.ll2 : E.ll; }
-            else { r = {E.u.pm.small[0].w, E.u.pm.small[0].sym, E.u.pm.small[0].list[0], E.u.pm.small[0].list[1], &E.u.pm.small[0].bits[0][0], 2, mSmall, E.lvl[1]}; out = pass ? E.d2 : E.d; }
-            zf_pm_serial(r, 15, out);
-        }
-#else
-        {
-            ZfPmRef rb = {E.u.pm.big[0].w, E.u.pm.big[0].sym, E.u.pm.big[0].list[0], E.u.pm.big[0].list[1], &E.u.pm.big[0].bits[0][0], 18, mBig, E.lvl[0]};
-            ZfPmRef rs = {E.u.pm.small[0].w, E.u.pm.small[0].sym, E.u.pm.small[0].list[0], E.u.pm.small[0].list[1], &E.u.pm.small[0].bits[0][0], 2, mSmall, E.lvl[1]};
-            zf_pm_wave(rb, 15, pass ? E.ll2 : E.ll);
-            zf_pm_wave(rs, 15, pass ? E.d2 : E.d);
-        }
-#endif
+        const ZfPmRef rb = {E.u.pm.big[0].w, E.u.pm.big[0].sym, E.u.pm.big[0].list[0], E.u.pm.big[0].list[1], &E.u.pm.big[0].bits[0][0], 18, mBig, E.lvl[0]};
+        const ZfPmRef rs = {E.u.pm.small[0].w, E.u.pm.small[0].sym, E.u.pm.small[0].list[0], E.u.pm.small[0].list[1], &E.u.pm.small[0].bits[0][0], 2, mSmall, E.lvl[1]};
+        zf_pm(rb, 15, pass ? E.ll2 : E.ll);
+        zf_pm(rs, 15, pass ? E.d2 : E.d);
         d4g_wave_sync();
     }
     d4g_wave_sync();

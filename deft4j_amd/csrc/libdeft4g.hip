@@ -888,14 +888,14 @@ __global__ void __launch_bounds__(64) k_debug_pack_header(const uint8_t* lens320
     __shared__ uint16_t prs[D4G_MAXPAIRS];   // (a pair stands for at least one of the at most 320 lengths)
     __shared__ uint32_t clFreq[20];
     __shared__ uint8_t clLen[32];
-    __shared__ __attribute__((aligned(16))) unsigned char tree[TreeMem<uint32_t, uint8_t, 20>::bytes(1)];
+    __shared__ __attribute__((aligned(16))) unsigned char tree[D4GClTree::bytes(1)];
     const int lane = threadIdx.x & 63;
     for (int i = lane; i < D4G_NLIT + D4G_NDIST; i += 64) lens[i] = lens320[i];
     __syncthreads();
     int nPairs, nCl, bits;
     d4g_wave_clear_cl_freq(clFreq);
     const int err = d4g_wave_pack_header(nLit + nDist, [&](int i) { return i < nLit ? (int)lens[i] : (int)lens[D4G_NLIT + i - nLit]; }, flags, prs, clFreq, clLen,
-                                         [&](const uint32_t* f, uint8_t* l) { return d4f_wave_cl_tree(tree, f, l); }, nPairs, nCl, bits);
+                                         [&](const uint32_t* f, uint8_t* l) { return d4g_wave_cl_tree<D4GFusedTrees>(tree, f, l); }, nPairs, nCl, bits);
     __syncthreads();
     for (int i = lane; i < nPairs; i += 64) pairs[i] = prs[i];
     if (lane < 19) clLen19[lane] = clLen[lane];
