@@ -104,7 +104,7 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_debug_zopfli_table", "d4g_debug_zopfli_code_lengths", "d4g_debug_cl_tree_lengths", "d4g_debug_pack_header", "d4g_init_devices", "d4g_device_count", "d4g_set_device",
            "d4g_batch_create_on", "d4g_optimise_streams_sharded", "d4g_batch_create_encode_level", "d4g_deflate_streams_level",
            "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
-           "d4g_debug_device_blocks", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name",
+           "d4g_debug_device_blocks", "d4g_debug_batch_bins", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name",
            "d4g_find_streams", "d4g_batch_recover", "d4g_batch_copy_recovered", "d4g_recover_streams",
            "d4g_batch_create_dict", "d4g_batch_create_dict_on", "d4g_inflate_dict", "d4g_find_streams_dict"]
 
@@ -507,6 +507,27 @@ class Batch:
         rc = self.L.d4g_debug_batch_poke_output(self.h, i, byte_offset, xor_mask)
         if rc != 0:
             raise RuntimeError("d4g_debug_batch_poke_output: " + self.L.d4g_last_error().decode())
+
+    def debug_bins(self, block):
+        """Test hook (d4g_debug_batch_bins): device block `block`'s static bin statistics -> dict(table: 29 rows of 320,
+        masks: 29 rows of mask words, records: (x, y, z, w) per back-reference record, n_blocks).  Parses a batch that has not
+        run; RuntimeError for a block without a table.  (The prototype is declared here: a build of the library from
+        before the hook existed, as an A/B series loads through D4G_LIB, has no such symbol.)"""
+        f = self.L.d4g_debug_batch_bins
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                      ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+        mw, nr, nb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        if f(self.h, block, None, None, 0, None, 0, ctypes.byref(mw), ctypes.byref(nr), ctypes.byref(nb)) != 0:
+            raise RuntimeError("d4g_debug_batch_bins: " + self.L.d4g_last_error().decode())
+        table = (ctypes.c_uint32 * (29 * 320))()
+        masks = (ctypes.c_uint64 * max(1, 29 * mw.value))()
+        recs = (ctypes.c_uint32 * max(1, 4 * nr.value))()
+        if f(self.h, block, table, masks, 29 * mw.value, recs, nr.value, ctypes.byref(mw), ctypes.byref(nr), ctypes.byref(nb)) != 0:
+            raise RuntimeError("d4g_debug_batch_bins: " + self.L.d4g_last_error().decode())
+        return {"table": [list(table[r * 320:(r + 1) * 320]) for r in range(29)],
+                "masks": [list(masks[r * mw.value:(r + 1) * mw.value]) for r in range(29)],
+                "records": [tuple(recs[4 * r:4 * r + 4]) for r in range(nr.value)], "n_blocks": nb.value}
 
     def stats(self):
         st = d4g_stats()

@@ -734,9 +734,21 @@ inline void Batch::copy_doubling(const CopyRoute& R, int32_t* dBad, RtScratch& t
 // (queued, not waited for: the block list comes from the caller's scratch, released after its next wait on the stream)
 inline void Batch::block_bins(const std::vector<int32_t>& realBlocks, bool needSlots, RtScratch& tmp) {
     if (!needSlots || realBlocks.empty()) return;
-    int32_t* dReal = tmp.upload(realBlocks);
+    // one workgroup per span of a block's decoded bytes: a block is cut into equal spans of whole tiles, bins_span_tiles()
+    // at the most (a block without records has nothing to count: its table stays zero)
+    std::vector<D4GBinSpan> spans;
+    const i64 maxTiles = bins_span_tiles();
+    for (const int32_t bi : realBlocks) {
+        const D4GBlock& b = hBlocks[bi];
+        if (b.binStat < 0 || b.refCount == 0) continue;
+        const i64 nTiles = (b.uLen + D4G_BINS_TILE - 1) / D4G_BINS_TILE, nSpans = (nTiles + maxTiles - 1) / maxTiles;
+        const i64 per = (nTiles + nSpans - 1) / nSpans * D4G_BINS_TILE;
+        for (i64 t0 = 0; t0 < b.uLen; t0 += per) spans.push_back({bi, (uint32_t)t0, (uint32_t)std::min<i64>(b.uLen, t0 + per)});
+    }
+    if (spans.empty()) return;
+    D4GBinSpan* dSpans = tmp.upload(spans);
     D4GCtx c = make_ctx(engine().progDyn, 0);
-    RT_LAUNCH(k_block_bins, realBlocks.size() * D4G_BINS_SPLIT, 256, c, dReal);
+    RT_LAUNCH(k_block_bins, spans.size(), bins_threads(), c, dSpans);
     stats.kernel_launches++;
 }
 

@@ -101,6 +101,29 @@ static inline int parse_threads() {
 #endif
     return v == 128 || v == 256 || v == 512 ? v : 64;
 }
+// The bin statistics (k_block_bins, which runs with any workgroup size): compile-time on the GPU, measured in DESIGN §5 — 1024
+// threads per workgroup, and up to 4 tiles summed by one workgroup before it adds its table to the block's.  Emulator: the
+// block decoders' threads, and D4G_SIM_BINS_SPAN_TILES, now (default the same 4), so that small cases reach a block of several spans.
+#ifndef D4G_BINS_THREADS
+#define D4G_BINS_THREADS 1024
+#endif
+#ifndef D4G_BINS_SPAN_TILES
+#define D4G_BINS_SPAN_TILES 4
+#endif
+static inline int bins_threads() {
+#ifdef D4G_HOSTSIM
+    return parse_threads();
+#else
+    return D4G_BINS_THREADS;
+#endif
+}
+static inline int bins_span_tiles() {
+#ifdef D4G_HOSTSIM
+    return std::max(1, knob_now("D4G_SIM_BINS_SPAN_TILES", D4G_BINS_SPAN_TILES));
+#else
+    return D4G_BINS_SPAN_TILES;
+#endif
+}
 // D4G_COPY, now: how build_blocks resolves the decoded bytes.  "blocks": block-local copies with window markers (k_seg_*);
 // "doubling": pointer jumping over the whole stream (k_fill_src / k_jump_* / k_resolve_streams); "auto" (default): blocks,
 // except that a stream holding a block one workgroup should not walk alone (more than D4G_SEG_MAX_BYTES decoded bytes or

@@ -454,53 +454,166 @@ __device__ __forceinline__ void wg_replace_backrefs(D4GLds* L, const D4GCtx& c, 
 
 // ---------------------------------------------------------------------------------------
 // Static per-bin statistics of a block's back-reference records (D4G_NBINS rows, d4g_types.h) and the per-bin
-// record masks.  One workgroup per block, once per parse.
+// record masks, once per parse.  One workgroup per span of a block's decoded bytes; it stages the span tile by tile in
+// LDS, and every byte of a tile, not every record, has a thread.  The table is summed in LDS over the span's tiles and
+// added to the block's once: the span is what sets the number of global atomics, the tile what fits in LDS.
 // ---------------------------------------------------------------------------------------
-#define D4G_BINS_SPLIT 4   // workgroups per block (each sums its share in LDS, then adds it to the block's zeroed table)
-__global__ void __launch_bounds__(256) k_block_bins(D4GCtx c, const int32_t* blockList) {
-    __shared__ uint32_t T[D4G_NBINS * D4G_BINSTRIDE];
-    const D4GBlock b = c.blocks[blockList[blockIdx.x / D4G_BINS_SPLIT]];
-    const int part = blockIdx.x % D4G_BINS_SPLIT;
-    if (b.binStat < 0) return;
-    for (int i = threadIdx.x; i < D4G_NBINS * D4G_BINSTRIDE; i += blockDim.x) T[i] = 0;
-    __syncthreads();
-    const uint4* rf = c.refs + b.refStart;
-    const uint8_t* Ub = c.U + b.uBase;
-    uint64_t* bm = c.binMask + b.binMask;
-    const int lane = threadIdx.x & 63;
-    const int nRef = (int)b.refCount, nWords = (int)b.maskWords;
-    for (int r0 = part * (int)blockDim.x; r0 < nWords * 64; r0 += D4G_BINS_SPLIT * (int)blockDim.x) {
-        int r = r0 + threadIdx.x;
-        uint4 rv = r < nRef ? rf[r] : make_uint4(0u, 0u, 0u, 0u);
-        int len = ref_len(rv.x);
-        int bin = ref_lsym(rv.x) - 257;
-        if (len > 0) {
-            // the record's copy of its first eight decoded bytes (U is padded)
-            const uint32_t* uw = (const uint32_t*)Ub + (rv.y >> 2);
-            const int sh = (int)(rv.y & 3u) * 8;
-            uint32_t w0 = uw[0], w1 = uw[1], w2 = uw[2];
-            c.refs[b.refStart + r].z = d4g_alignbit(w1, w0, sh);
-            c.refs[b.refStart + r].w = d4g_alignbit(w2, w1, sh);
-            uint32_t* row = T + bin * D4G_BINSTRIDE;
-            atomicAdd(&row[D4G_BIN_DIST + ref_dsym(rv.x)], 1u);
-            atomicAdd(&row[D4G_BIN_COUNT], 1u);
-            atomicAdd(&row[D4G_BIN_EBITS], (unsigned)ref_ebits(rv.x));
-            for_bytes(Ub + rv.y, len, [&](int by) { atomicAdd(&row[by], 1u); return true; });
-        }
-        // the bin masks: one ballot per bin present in this word of records
-        unsigned long long todo = d4g_ballot(len > 0);
-        while (todo) {
-            int src = __ffsll((long long)todo) - 1;
-            int bsel = __shfl(bin, src);
-            unsigned long long same = d4g_ballot(len > 0 && bin == bsel);
-            if (lane == src) bm[(long long)bsel * nWords + (r >> 6)] = same;
-            todo &= ~same;
-        }
+#ifndef D4G_BINS_TILE
+#define D4G_BINS_TILE 16384   // decoded bytes staged at a time
+#endif
+struct D4GBinSpan { int32_t block; uint32_t t0, t1; };   // bytes [t0, t1) of the block; t0 is a multiple of D4G_BINS_TILE
+#define D4G_BINS_END 0x80u    // mark of a byte where a record ends; a record's first byte carries bin + 1 (1..29)
+struct D4GBinsLds {
+    uint32_t T[D4G_NBINS * D4G_BINSTRIDE];                 // the span's share of the block's table
+    alignas(16) uint32_t S[(D4G_BINS_TILE + 32) / 4];      // the tile's decoded bytes, from the 16-byte line that holds the first
+    alignas(16) uint32_t C[(D4G_BINS_TILE + 32) / 4];      // per byte of S: a mark where a record's cover starts or ends, else 0
+    int found[2];                                          // wg_first_record: the answer, two buffers
+    int more[2];                                           // the record loop: another pass follows (two buffers)
+    int nextLo;                                            // first record that reaches past the tile: where the next tile starts
+    uint32_t waveLast[16];
+};
+static_assert(sizeof(D4GBinsLds) <= 80 * 1024, "one bin-statistics workgroup fits beside a resident search workgroup");
+
+// The first record of [0, n) for which pred holds (n: none); pred is false, then true, along the records.  Every thread
+// probes one record per round and the range narrows blockDim-fold: a few rounds, not one thread's binary search.
+template <typename Pred>
+D4G_DEV int wg_first_record(int n, int* found, Pred pred) {
+    const int tid = threadIdx.x, bd = blockDim.x;
+    int lo = 0, hi = n;
+    bool more = n > 0;
+    for (int round = 0; more; round++) {
+        int* f = found + (round & 1);   // (the other buffer is still being read by slower waves)
+        if (tid == 0) *f = hi;
+        __syncthreads();
+        const int span = hi - lo, step = span > bd ? (span + bd - 1) / bd : 1;
+        const int p = lo + tid * step;
+        if (p < hi && pred(p)) atomicMin(f, p);
+        __syncthreads();
+        // the answer lies after the last probe that failed, at or before the first that held
+        hi = *f;
+        lo = hi - step + 1 > lo ? hi - step + 1 : lo;
+        more = step > 1;
     }
+    return hi;
+}
+// v of the nearest thread below this one whose v is not zero (0: none).  Ends with no barrier pending.
+D4G_DEV uint32_t wg_last_nonzero_before(uint32_t v, uint32_t* waveLast) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = d4g_ballot(v != 0);
+    const unsigned long long below = m & ((1ull << lane) - 1);
+    uint32_t carry = __shfl(v, below ? 63 - __clzll((long long)below) : lane);
+    const uint32_t top = __shfl(v, m ? 63 - __clzll((long long)m) : lane);
+    if (lane == 0) waveLast[wave] = m ? top : 0u;
     __syncthreads();
+    if (below) return carry;
+    carry = 0u;
+    for (int w = wave - 1; w >= 0 && !carry; w--) carry = waveLast[w];
+    return carry;
+}
+
+__global__ void __launch_bounds__(1024) k_block_bins(D4GCtx c, const D4GBinSpan* spans) {
+    __shared__ D4GBinsLds L;
+    const D4GBinSpan sp = spans[blockIdx.x];
+    const D4GBlock b = c.blocks[sp.block];
+    if (b.binStat < 0) return;
+    const int tid = threadIdx.x, bd = blockDim.x, lane = tid & 63;
+    const uint4* rf = c.refs + b.refStart;
+    const int nRef = (int)b.refCount, nWords = (int)b.maskWords;
+    uint64_t* bm = c.binMask + b.binMask;
+    for (int i = tid; i < D4G_NBINS * D4G_BINSTRIDE; i += bd) L.T[i] = 0;
+    // records ascend and do not overlap: the first that reaches into the span (its later tiles learn theirs from the tile before)
+    int rLo = 0;
+    if (sp.t0) {
+        const uint32_t s0 = (uint32_t)b.uStart + sp.t0;
+        rLo = wg_first_record(nRef, L.found, [&](int r) { const uint4 v = rf[r]; return v.y + (uint32_t)ref_len(v.x) > s0; });
+    }
+    int pass = 0;
+    for (uint32_t t0 = sp.t0; t0 < sp.t1; t0 += D4G_BINS_TILE) {
+        // the tile in the stream's decoded bytes: [ts, te); S and C start at `base`, the 16-byte line of ts
+        const uint32_t t1 = t0 + D4G_BINS_TILE < sp.t1 ? t0 + D4G_BINS_TILE : sp.t1;
+        const uint32_t ts = (uint32_t)b.uStart + t0, te = (uint32_t)b.uStart + t1, base = ts & ~15u;
+        const int nq = (int)(te - base);   // bytes of S in use (at most D4G_BINS_TILE + 15); C has one more, the closing mark
+        for (int i = tid; i <= nq >> 2; i += bd) L.C[i] = 0;
+        {   // (a stream's region of U is whole 16-byte lines)
+            const uint4* src = (const uint4*)(c.U + b.uBase + base);
+            uint4* dst = (uint4*)L.S;
+            for (int i = tid; i < (nq + 15) >> 4; i += bd) dst[i] = src[i];
+        }
+        const int nStaged = ((nq + 15) >> 4) * 4;   // words
+        if (tid == 0) L.nextLo = nRef;
+        __syncthreads();
+        if (tid == 0) atomicOr(&L.C[nq >> 2], D4G_BINS_END << (8 * (nq & 3)));   // nothing is covered past the tile
+        // the records that reach into the tile, blockDim at a time, until one starts at or past its end
+        for (int rb = rLo & ~63, more = 1; more; rb += bd, pass++) {
+            const int r = rb + tid;
+            uint4 rv = make_uint4(0u, 0u, 0u, 0u);
+            if (r < nRef) rv = rf[r];
+            if (tid == bd - 1) L.more[pass & 1] = r + 1 < nRef && rv.y < te;
+            if (r < nRef && rv.y + (uint32_t)ref_len(rv.x) > te) atomicMin(&L.nextLo, r);
+            if (rv.y >= te || rv.y + (uint32_t)ref_len(rv.x) <= ts) rv = make_uint4(0u, 0u, 0u, 0u);   // not of this tile
+            const int len = ref_len(rv.x);
+            const int bin = ref_lsym(rv.x) - 257;
+            const bool own = len > 0 && rv.y >= ts;   // the tile that holds a record's start counts the record
+            if (len > 0) {   // cover marks, clipped to the tile
+                const uint32_t qs = (rv.y > ts ? rv.y : ts) - base, ye = rv.y + (uint32_t)len;
+                atomicOr(&L.C[qs >> 2], (uint32_t)(bin + 1) << (8 * (qs & 3u)));
+                if (ye < te) atomicOr(&L.C[(ye - base) >> 2], D4G_BINS_END << (8 * ((ye - base) & 3u)));
+            }
+            if (own) {
+                // the record's copy of its first eight decoded bytes: staged, or past the tile from U (padded)
+                const uint32_t q = rv.y - base;
+                const uint32_t* uw = (const uint32_t*)(c.U + b.uBase) + (rv.y >> 2);
+                if ((int)(q >> 2) + 3 <= nStaged) uw = L.S + (q >> 2);
+                const int sh = (int)(rv.y & 3u) * 8;
+                const uint32_t w0 = uw[0], w1 = uw[1], w2 = uw[2];
+                c.refs[b.refStart + r].z = d4g_alignbit(w1, w0, sh);
+                c.refs[b.refStart + r].w = d4g_alignbit(w2, w1, sh);
+                uint32_t* row = L.T + bin * D4G_BINSTRIDE;
+                atomicAdd(&row[D4G_BIN_DIST + ref_dsym(rv.x)], 1u);
+                atomicAdd(&row[D4G_BIN_COUNT], 1u);
+                atomicAdd(&row[D4G_BIN_EBITS], (unsigned)ref_ebits(rv.x));
+            }
+            // the bin masks: one ballot per (bin, mask word) present in this wave's records; a word can hold records of two tiles
+            unsigned long long todo = d4g_ballot(own);
+            while (todo) {
+                const int src = __ffsll((long long)todo) - 1;
+                const int bsel = __shfl(bin, src), wsel = __shfl(r >> 6, src);
+                const unsigned long long same = d4g_ballot(own && bin == bsel && (r >> 6) == wsel);
+                if (lane == src) {
+                    const int s = (r - lane) - wsel * 64;   // bit of the wave's lane 0 in that word
+                    atomicOr((unsigned long long*)&bm[(long long)bsel * nWords + wsel], s >= 0 ? same << s : same >> -s);
+                }
+                todo &= ~same;
+            }
+            __syncthreads();
+            more = L.more[pass & 1];
+        }
+        rLo = L.nextLo;
+        // every byte learns the bin that covers it: the last mark at or before it.  A thread takes a run of whole words (an odd
+        // number of them: the threads' reads fall on different banks), finds its run's last mark, and gets its carry-in.
+        const int runW = ((((nq + 1 + bd - 1) / bd) + 3) >> 2) | 1;
+        const int w0 = tid * runW < (nq >> 2) + 1 ? tid * runW : (nq >> 2) + 1;
+        const int w1 = w0 + runW < (nq >> 2) + 1 ? w0 + runW : (nq >> 2) + 1;
+        uint32_t last = 0;
+        for (int w = w0; w < w1; w++) {
+            const uint32_t cw = L.C[w];
+            if (cw) last = (cw >> (8 * ((31 - __clz((int)cw)) >> 3))) & 0xffu;
+        }
+        uint32_t state = wg_last_nonzero_before(last, L.waveLast) & 31u;   // bin + 1, or 0 between records
+        for (int w = w0; w < w1; w++) {
+            const uint32_t cw = L.C[w], sw = L.S[w];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t cb = (cw >> (8 * j)) & 0xffu;
+                if (cb) state = cb & 31u;
+                if (state) atomicAdd(&L.T[(state - 1) * D4G_BINSTRIDE + ((sw >> (8 * j)) & 0xffu)], 1u);
+            }
+        }
+        __syncthreads();   // (S, C and nextLo are the next tile's now)
+    }
     uint32_t* g = c.binStat + b.binStat;   // zeroed by the host
-    for (int i = threadIdx.x; i < D4G_NBINS * D4G_BINSTRIDE; i += blockDim.x)
-        if (T[i]) atomicAdd(&g[i], T[i]);
+    for (int i = tid; i < D4G_NBINS * D4G_BINSTRIDE; i += bd)
+        if (L.T[i]) atomicAdd(&g[i], L.T[i]);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1455,7 +1455,29 @@ int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint
     });
 }
 
-int d4g_debug_verify_compare(const uint8_t* x, size_t x_skew, const uint8_t* y, size_t y_skew, size_t len, int64_t* first) {
+int d4g_debug_batch_bins(d4g_batch* b, size_t block, uint32_t* table, uint64_t* masks, size_t mask_cap, uint32_t* records, size_t record_cap,
+                         size_t* mask_words, size_t* n_records, size_t* n_blocks) {
+    return api(b, [&] {
+        if (!b) return fail(D4G_ERR_ARG, "null batch");
+        if (b->lz) return fail(D4G_ERR_ARG, "an encoder batch");
+        Batch& B = b->impl;
+        if (!B.ran) B.run_parse(false);   // the parse of d4g_batch_run: d4g_batch_parse makes no tables
+        if (n_blocks) *n_blocks = B.hBlocks.size();
+        if (block >= B.hBlocks.size()) return fail(D4G_ERR_ARG, "bad block index");
+        const D4GBlock& d = B.hBlocks[block];
+        if (d.binStat < 0 || !B.dBinStat || !B.dBinMask || !B.dRefs) return fail(D4G_ERR_ARG, "the block has no table");
+        const size_t mw = (size_t)d.maskWords, nr = (size_t)d.refCount;
+        if (mask_words) *mask_words = mw;
+        if (n_records) *n_records = nr;
+        if ((masks && mask_cap < D4G_NBINS * mw) || (records && record_cap < nr)) return fail(D4G_ERR_ARG, "output buffer too small");
+        if (table) rt_d2h(table, B.dBinStat + d.binStat, (size_t)D4G_NBINS * D4G_BINSTRIDE * 4);
+        if (masks && mw) rt_d2h(masks, B.dBinMask + d.binMask, D4G_NBINS * mw * 8);
+        if (records && nr) rt_d2h(records, B.dRefs + d.refStart, nr * 16);
+        return D4G_OK;
+    });
+}
+
+int d4g_debug_verify_compare(const uint8_t* x, size_t x_skew,const uint8_t* y, size_t y_skew, size_t len, int64_t* first) {
     if ((len && (!x || !y)) || !first || x_skew > 15 || y_skew > 15) return fail(D4G_ERR_ARG, "bad argument");
     return api(nullptr, [&] {
         RtScratch tmp;

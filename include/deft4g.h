@@ -282,6 +282,17 @@ int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint
  * (Every decoded range the library itself compares starts on a 16-byte boundary; the kernel does not rely on it.) */
 int d4g_debug_verify_compare(const uint8_t* x, size_t x_skew, const uint8_t* y, size_t y_skew, size_t len, int64_t* first);
 
+/* Test hook (tests/ only): the static bin statistics of device block `block` of a batch (its Huffman blocks in stream
+ * order; stored blocks have none), as k_block_bins left them.  A batch that has not run is parsed here the way
+ * d4g_batch_run parses it (and then counts as run); d4g_batch_parse makes no tables, and a finished run has released them:
+ * both give D4G_ERR_ARG "the block has no table", as does a block of an encoder batch.  table: 29 x 320 u32 (per length
+ * symbol: byte counts, [256, 286) distance symbols, [286] records, [287] extra bits); masks: 29 x *mask_words u64, bit r
+ * of a row set when record r carries that length symbol; records: *n_records x 4 u32 (x, y, z, w of every back-reference
+ * record: packed length and symbols, offset of its bytes in the stream's decoded data, its first eight decoded bytes).
+ * NULL buffers are skipped (the counts still come back); mask_cap / record_cap are in u64 words / records. */
+int d4g_debug_batch_bins(d4g_batch* b, size_t block, uint32_t* table, uint64_t* masks, size_t mask_cap, uint32_t* records, size_t record_cap,
+                         size_t* mask_words, size_t* n_records, size_t* n_blocks);
+
 /* Debug and tests only: *live = device-memory blocks the pool of the calling thread's context (d4g_set_device) has handed
  * out and not yet got back.  Equal before and after any call — failed ones included — once the batches it made are closed. */
 int d4g_debug_device_blocks(int64_t* live);
