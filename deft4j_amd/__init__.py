@@ -106,7 +106,8 @@ EXPORTS = ["d4g_init", "d4g_shutdown", "d4g_last_error", "d4g_batch_create", "d4
            "d4g_batch_verify", "d4g_batch_verify_result", "d4g_verify_streams", "d4g_debug_batch_poke_output", "d4g_batch_block_info", "d4g_debug_verify_compare",
            "d4g_debug_device_blocks", "d4g_debug_batch_bins", "d4g_batch_parse_error", "d4g_diagnose_streams", "d4g_parse_reason_name",
            "d4g_find_streams", "d4g_batch_recover", "d4g_batch_copy_recovered", "d4g_recover_streams",
-           "d4g_batch_create_dict", "d4g_batch_create_dict_on", "d4g_inflate_dict", "d4g_find_streams_dict"]
+           "d4g_batch_create_dict", "d4g_batch_create_dict_on", "d4g_inflate_dict", "d4g_find_streams_dict",
+           "d4g_batch_create_encode_dict", "d4g_deflate_streams_dict"]
 
 
 def load_library(path=None):
@@ -245,6 +246,12 @@ def load_library(path=None):
                                        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]
         L.d4g_find_streams_dict.restype = ctypes.c_int
         L.d4g_find_streams_dict.argtypes = L.d4g_find_streams.argtypes[:4] + dict_args[:3] + L.d4g_find_streams.argtypes[4:]
+    if hasattr(L, "d4g_batch_create_encode_dict"):   # (the encoder's preset dictionaries: likewise)
+        dict_args = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]
+        L.d4g_batch_create_encode_dict.restype = ctypes.c_void_p
+        L.d4g_batch_create_encode_dict.argtypes = L.d4g_batch_create_encode_level.argtypes[:3] + dict_args + L.d4g_batch_create_encode_level.argtypes[3:]
+        L.d4g_deflate_streams_dict.restype = ctypes.c_int
+        L.d4g_deflate_streams_dict.argtypes = L.d4g_deflate_streams_level.argtypes[:6] + dict_args + L.d4g_deflate_streams_level.argtypes[6:]
     if path is None:
         _lib = L
     return L
@@ -551,16 +558,27 @@ class EncodeBatch(Batch):
     spec — the Compressor objects of C/CompressionUtil.java:44-78.  run(optimise=False) leaves the encoder's output as it
     is (SingleCompressor.compressSingle); optimise=True also applies Deft.optimiseDeflateStream to every output.
     A spec may also be (input, encoder, strategy, level) — zlib levels -1, 1..9 (d4g_batch_create_encode_level); a
-    3-tuple next to those means level 9."""
+    3-tuple next to those means level 9.
+    dictionaries / dictionary_of: preset dictionaries of the INPUTS (zlib's zdict=, d4g_batch_create_encode_dict), in
+    Batch's convention — one bytes object for all inputs, or a list and per input an index into it or None."""
 
-    def __init__(self, inputs, specs, lib=None):  # noqa: super().__init__ deliberately not called: a different constructor
+    def __init__(self, inputs, specs, lib=None, dictionaries=None, dictionary_of=None):  # noqa: super().__init__ deliberately not called: a different constructor
         self.L = lib or _need()
         self.n = len(specs)
         self._keep = [bytes(s) for s in inputs]
         nin = len(self._keep)
         arr = (ctypes.c_char_p * max(1, nin))(*self._keep)
         lens = (ctypes.c_size_t * max(1, nin))(*[len(s) for s in self._keep])
-        if any(len(t) == 4 for t in specs):
+        if dictionaries is not None:
+            dicts, of = _dictionary_args(nin, dictionaries, dictionary_of)
+            darr, dlens = _dictionary_arrays(dicts)
+            ofarr = (ctypes.c_int32 * max(1, nin))(*of)
+            sp = (d4g_encoder_spec_level * max(1, self.n))(*[d4g_encoder_spec_level(*(tuple(t) + (9,) * (4 - len(t)))) for t in specs])
+            self.h = self.L.d4g_batch_create_encode_dict(nin, arr, lens, len(dicts), darr, dlens, ofarr, self.n, sp)
+            what = "d4g_batch_create_encode_dict: "
+        elif dictionary_of is not None:
+            raise ValueError("dictionary_of without dictionaries")
+        elif any(len(t) == 4 for t in specs):
             sp = (d4g_encoder_spec_level * max(1, self.n))(*[d4g_encoder_spec_level(*(tuple(t) + (9,) * (4 - len(t)))) for t in specs])
             self.h = self.L.d4g_batch_create_encode_level(nin, arr, lens, self.n, sp)
             what = "d4g_batch_create_encode_level: "
@@ -578,9 +596,10 @@ class EncodeBatch(Batch):
         return self
 
 
-def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None, level=9):
+def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None, level=9, dictionaries=None, dictionary_of=None):
     """SingleCompressor.compressSingle for every input (d4g_deflate_streams); at another zlib level (-1, 1..9) or with
-    STRATEGY_RLE / STRATEGY_FIXED through d4g_deflate_streams_level."""
+    STRATEGY_RLE / STRATEGY_FIXED through d4g_deflate_streams_level; with preset dictionaries (Batch's convention, per
+    input) through d4g_deflate_streams_dict."""
     L = lib or _need()
     n = len(inputs)
     keep = [bytes(s) for s in inputs]
@@ -588,7 +607,15 @@ def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None
     lens = (ctypes.c_size_t * max(1, n))(*[len(s) for s in keep])
     out = (ctypes.c_void_p * max(1, n))()
     olen = (ctypes.c_size_t * max(1, n))()
-    if level == 9 and strategy in (STRATEGY_DEFAULT, STRATEGY_FILTERED, STRATEGY_HUFFMAN_ONLY):
+    if dictionaries is not None:
+        dicts, of = _dictionary_args(n, dictionaries, dictionary_of)
+        darr, dlens = _dictionary_arrays(dicts)
+        ofarr = (ctypes.c_int32 * max(1, n))(*of)
+        rc = L.d4g_deflate_streams_dict(n, arr, lens, encoder, level, strategy, len(dicts), darr, dlens, ofarr, out, olen)
+        what = "d4g_deflate_streams_dict: "
+    elif dictionary_of is not None:
+        raise ValueError("dictionary_of without dictionaries")
+    elif level == 9 and strategy in (STRATEGY_DEFAULT, STRATEGY_FILTERED, STRATEGY_HUFFMAN_ONLY):
         rc, what = L.d4g_deflate_streams(n, arr, lens, encoder, strategy, out, olen), "d4g_deflate_streams: "
     else:
         rc, what = L.d4g_deflate_streams_level(n, arr, lens, encoder, level, strategy, out, olen), "d4g_deflate_streams_level: "
@@ -599,6 +626,32 @@ def deflate_streams(inputs, encoder=ENC_JVM, strategy=STRATEGY_DEFAULT, lib=None
         res.append(ctypes.string_at(out[i], olen[i]))
         L.d4g_free(out[i])
     return res
+
+
+def zlib_streams(inputs, level=9, strategy=STRATEGY_DEFAULT, dictionaries=None, dictionary_of=None, lib=None):
+    """Complete zlib streams (RFC 1950) of the inputs, as zlib 1.2.11's deflateInit2(level, Z_DEFLATED, 15, 8, strategy) [+
+    deflateSetDictionary] writes them: CMF FLG [DICTID] payload ADLER32.  The payload is the encoder's, the trailer the
+    device checksum of the batch; FLEVEL follows zlib's rule and DICTID is the Adler-32 of the whole dictionary as passed."""
+    import zlib
+    n = len(inputs)
+    dicts, of = ([], [-1] * n) if dictionaries is None else _dictionary_args(n, dictionaries, dictionary_of)
+    if dictionaries is None and dictionary_of is not None:
+        raise ValueError("dictionary_of without dictionaries")
+    b = EncodeBatch(inputs, [(i, ENC_JVM, strategy, level) for i in range(n)], lib=lib, dictionaries=dictionaries, dictionary_of=dictionary_of)
+    try:
+        b.run(False)
+        lv = 6 if level == -1 else level
+        flevel = 0 if (strategy >= STRATEGY_HUFFMAN_ONLY or lv < 2) else 1 if lv < 6 else 2 if lv == 6 else 3
+        res = []
+        for i in range(n):
+            d = dicts[of[i]] if of[i] >= 0 else b""
+            head = 0x7800 | (flevel << 6) | (0x20 if d else 0)
+            head += 31 - head % 31
+            res.append(head.to_bytes(2, "big") + (zlib.adler32(d).to_bytes(4, "big") if d else b"") + b.output(i) +
+                       b.checksums(i)[1].to_bytes(4, "big"))
+        return res
+    finally:
+        b.close()
 
 
 def verify_streams(a, b, lib=None):

@@ -63,7 +63,8 @@ struct HStream {
     std::vector<HBlock> blocks;
     i64 consumed = 0, sizeBitsIn = 0, saved = 0;
     i64 inOff = 0, inLen = 0;
-    const uint8_t* dict = nullptr;   // preset dictionary: its tail in device memory (the batch's dDict, or that of the batch this one works for)
+    const uint8_t* dict = nullptr;   // preset dictionary: its tail in device memory — the batch's dDict (or that of the batch this one works
+                                     // for); an encoder batch's own dU, right in front of the input (LzFront::create).  Both live as long as the batch
     i64 dictLen = 0;                 // bytes of that tail (<= 32768), 0: none
     i64 tokBase = 0, uBase = 0, nTok = 0, nU = 0, refBase = 0, nRef = 0;
     i64 outWordBase = 0, outBits = 0;

@@ -54,12 +54,20 @@
 #define LZ_FLAVOR_ZLIB 0
 #define LZ_FLAVOR_JZLIB 1
 
-struct LzStream {           // one uncompressed input
-    const uint8_t* data;    // in U (16-byte aligned, >= 320 zero bytes after the end)
-    long long len;
+// Coordinates.  An input with a preset dictionary (deflateSetDictionary) is encoded as zlib encodes it: as the stream
+// tail(dictionary) || input from position dictLen on, nothing before dictLen emitted.  INSIDE the encoder a position is a
+// position of that concatenation: sort blocks, ranks, chunks and their metas (firstPos, the packed states), the staged
+// window, LZ_MAX_DIST, the NIL slot (position 0: the tail's first byte), the insertion map, LzBlockDesc::lastTop and the
+// window base in k_lz_blocks.  What LEAVES the encoder counts from the input's first byte, as the optimiser expects:
+// tok[].y, refs[].y and LzBlockDesc::uStart / uLen.  Without a dictionary (dictLen == 0) the two are the same.
+struct LzStream {           // one uncompressed input, its dictionary's tail in front of it
+    const uint8_t* data;    // position 0 in U: the tail's first byte.  data + dictLen (the input) is 16-byte aligned, >= 320
+                            // zero bytes follow the end and the 15 bytes before data are readable
+    long long len;          // dictLen + the input's length (concatenation)
     long long posBase;      // index of position 0 in S16 / rank16 (a multiple of LZ_SORT_BLOCK)
     int32_t sortBlock0;     // first sort block (index into bstart / LZ_SORT_BLOCK)
-    int32_t nChunks;
+    int32_t nChunks;        // chunks of the concatenation; the first dictLen / LZ_CHUNK of them lie in the dictionary: not parsed
+    long long dictLen;      // bytes of dictionary tail (<= 32768), 0: none
 };
 struct LzSortJob { int32_t stream, blk; };
 // meta index of chunk c = metaBase + c.  good / lazy / nice / chain: zlib's configuration_table row of the level
@@ -78,8 +86,8 @@ struct LzChunkMeta {
 };
 
 // parse state at a loop top of deflate_slow: position, match_available, match_length carried from the previous
-// position (2 = none) and the distance of that pending match
-D4G_DEV unsigned long long lz_pack_state(long long p, int ma, int ml, int md) {
+// position (2 = none) and the distance of that pending match.  (The host writes the dictionary chunks' states with it.)
+__host__ D4G_DEV unsigned long long lz_pack_state(long long p, int ma, int ml, int md) {
     return (unsigned long long)p | ((unsigned long long)ml << 32) | ((unsigned long long)ma << 41) | ((unsigned long long)(ml >= 3 ? md : 0) << 42);
 }
 
@@ -124,6 +132,8 @@ struct LzCtx {
 
 // deflate_fast's insertion map as a chain walk sees it: bit x - base of w = position x was inserted.  Below own0 (the
 // running chunk's first position) a speculative run assumes every position inserted; an exact run reads the window.
+// Every position of a preset dictionary is inserted (deflateSetDictionary inserts them all at levels 1-3 too): the words
+// of the chunks before the stream's first keep their initial all-ones, and the first chunk never clears below dictLen.
 struct LzBits {
     const uint32_t* w;
     long long base, own0;
@@ -243,6 +253,10 @@ D4G_DEV void lz_search(const LzCtx& c, const LzStream& st, const uint32_t* win, 
 // exact = 0: every chunk but a stream's first starts LZ_WARM positions early from a clean state and records from its
 //            first loop top inside the chunk;  exact = 1 (one wave per job): the chunk starts from its predecessor's
 //            recorded exit state and the wave carries on into the following chunks while they disagree.
+// A stream's first chunk is the one that holds position dictLen (chunk 0 without a dictionary): it starts exact, at dictLen
+// from lz_pack_state(dictLen, 0, 2, 0) — zlib's state after deflateSetDictionary.  The chunks before it lie wholly in the
+// dictionary: never launched, their metas are the host's (no tokens, entry = exit = that state, so k_lz_check's induction
+// starts there).  Later chunks' warm-up may reach into the dictionary, never before dictLen's exact state.
 // deflate_fast (KIND == LZ_KIND_FAST) also keeps an insertion map, one bit per position: a chunk writes
 // the bits of its own LZ_CHUNK positions; its searches read them below its position, and below its first position read
 // "inserted" (speculative pass) or the map of the pass's start (insFrozen; exact passes), except for chunks this wave
@@ -264,7 +278,11 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
     const LzParseJob job = jobs[blockIdx.x];
     const LzStream st = c.streams[job.stream];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const uint8_t* wb = (const uint8_t*)win;
+    // the staged window begins `skew` bytes before position w0, where 16-byte loads are aligned (a dictionary tail puts
+    // position 0 at any address; without one skew is 0)
+    const int skew = (int)((unsigned long long)st.data & 15u);
+    const uint8_t* wb = (const uint8_t*)win + skew;
+    const int firstChunk = (int)(st.dictLen / LZ_CHUNK);   // the chunk that holds the input's first byte: the stream's first
     int tileChunk = job.firstChunk;                 // first chunk of the staged tile
     unsigned long long carry = 0;                   // exact mode, from the second chunk of a chain on: the state to start from
     bool chained = false;
@@ -281,8 +299,8 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
     {   // stage [w0, w1): the input is padded with zero bytes, so reading past st.len is harmless
         long long lim = ((st.len + 15) & ~15LL) + 320;
         if (w1 > lim) w1 = lim;
-        const int nvec = (int)((w1 - w0 + 15) >> 4);
-        const uint4* src = (const uint4*)(st.data + w0);
+        const int nvec = (int)((w1 - w0 + skew + 15) >> 4);
+        const uint4* src = (const uint4*)(st.data + w0 - skew);
         uint4* dst = (uint4*)win;
         for (int i = threadIdx.x; i < nvec; i += blockDim.x) dst[i] = src[i];
     }
@@ -317,7 +335,8 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
     long long p;
     int ma = 0, ml = 2, md = 0;
     bool rec;
-    if (chunk == 0) { p = 0; rec = true; }
+    const bool first = chunk == firstChunk;
+    if (first) { p = st.dictLen; rec = true; }   // exact: the clean state at the input's first byte (after deflateSetDictionary)
     else if (exact) {
         unsigned long long e = chained ? carry : (M - 1)->exit;
         p = (long long)(e & 0xffffffffULL);
@@ -327,7 +346,7 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
         rec = true;
     } else {
         p = c0 - LZ_WARM;
-        if (p < 0) p = 0;
+        if (p < st.dictLen) p = st.dictLen;   // (the warm-up may reach into the dictionary, never before the exact start)
         rec = false;
     }
     unsigned long long entry = lz_pack_state(p, ma, ml, md);
@@ -369,7 +388,7 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
     if (KIND == LZ_KIND_FAST) {
         own[((c0 - bw0) >> 5) + lane] = 0xffffffffu;   // LZ_CHUNK_WORDS == 64: one word per lane
         d4g_wave_sync();
-        if (rec && p > c0 && !ma) clearBits(c0, p);
+        if (rec && p > c0 && !ma && !first) clearBits(c0, p);   // (the first chunk: [c0, p) is dictionary, all of it inserted)
     }
     if (KIND == LZ_KIND_SLOW) {
     while (p < c1) {
@@ -378,7 +397,7 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
         ml = 2;
         if (st.len - p >= 3 && prevLen < job.lazy && job.strategy != LZ_HUFFMAN_ONLY) {
             int bl, bd;
-            lz_search<false>(c, st, win, w0, p, prevLen, prevLen >= job.good ? job.chain >> 2 : job.chain, job.nice, bits, bl, bd);
+            lz_search<false>(c, st, win, w0 - skew, p, prevLen, prevLen >= job.good ? job.chain >> 2 : job.chain, job.nice, bits, bl, bd);
             if (bl > prevLen) {
                 ml = bl;
                 md = bd;
@@ -411,10 +430,10 @@ __global__ void __launch_bounds__(64 * LZ_PARSE_MAXWAVES) k_lz_parse(LzCtx c, co
         const long long rem = st.len - p;
         int bl = 2, bd = 0;
         if (KIND == LZ_KIND_FAST) {
-            if (rem >= 3) lz_search<true>(c, st, win, w0, p, 2, job.chain, job.nice, bits, bl, bd);
+            if (rem >= 3) lz_search<true>(c, st, win, w0 - skew, p, 2, job.chain, job.nice, bits, bl, bd);
         } else if (rem >= 3 && p > 0) {   // deflate_rle: how far the byte before p repeats (eight bytes per lane)
-            const int po = (int)(p - w0);
-            const unsigned long long pat = 0x0101010101010101ULL * wb[po - 1];
+            const int po = (int)(p - w0) + skew;
+            const unsigned long long pat = 0x0101010101010101ULL * ((const uint8_t*)win)[po - 1];
             const unsigned long long x = lane < 33 ? lz_load8(win, po + 8 * lane) ^ pat : 0ULL;
             const unsigned long long m = __ballot(lane < 33 && x != 0ULL);
             int run = 264;
@@ -607,9 +626,10 @@ struct LzOutStream {           // one emitted deflate stream = (input, strategy,
 struct LzFillJob { int32_t out, chunk; long long symBase, refBase; };   // symbols / records before this chunk in its stream
 struct LzBlockDesc {           // per emitted block
     long long symStart, symCount;   // symbols (tokens without the end-of-block) of the stream that the block holds
-    long long uStart, uLen;         // decoded byte range (written by k_lz_fill)
+    long long uStart, uLen;         // decoded byte range, from the input's first byte (written by k_lz_fill)
     long long refStart, refCount;   // back-reference records, relative to the stream (written by k_lz_fill / host)
-    long long lastTop;              // loop-top position of the iteration that flushed the block (window base rule)
+    long long lastTop;              // loop-top position of the iteration that flushed the block (window base rule), a position of
+                                    // the concatenation
     int32_t out, isLast;
 };
 
@@ -643,11 +663,13 @@ __global__ void __launch_bounds__(64) k_lz_fill(LzCtx c, const LzOutStream* outs
     } else {
         long long c0 = (long long)job.chunk * LZ_CHUNK, c1 = c0 + LZ_CHUNK;
         if (c1 > st.len) c1 = st.len;
-        ntok = (unsigned)(c1 - c0);
+        if (c0 < st.dictLen) c0 = st.dictLen;   // (HUFFMAN_ONLY ignores the dictionary: only the input's bytes are symbols)
+        ntok = c1 > c0 ? (unsigned)(c1 - c0) : 0u;
         pos = c0;
     }
+    const long long out0 = st.dictLen;   // what leaves counts from the input's first byte
     if (job.chunk == 0 && lane == 0 && bd[o.nBlocks - 1].symCount == 0)   // an empty last block holds just its end-of-block token
-        tok[o.tokBase + bd[o.nBlocks - 1].symStart + (o.nBlocks - 1)] = make_uint2(256u, (uint32_t)st.len);
+        tok[o.tokBase + bd[o.nBlocks - 1].symStart + (o.nBlocks - 1)] = make_uint2(256u, (uint32_t)(st.len - out0));
     if (ntok == 0) return;
     int blk = lz_find_block(bd, o.nBlocks, job.symBase);
     long long nrefBefore = job.refBase;
@@ -664,7 +686,8 @@ __global__ void __launch_bounds__(64) k_lz_fill(LzCtx c, const LzOutStream* outs
             int a = __shfl_up(il, d), b = __shfl_up(ir, d);
             if (lane >= d) { il += a; ir += b; }
         }
-        const long long myPos = pos + (il - sl);
+        const long long myTop = pos + (il - sl);   // the token's first byte as the parse counted it
+        const long long myPos = myTop - out0;      // ... and from the input's first byte
         const long long myRef = nrefBefore + (ir - sr);
         const long long sym = job.symBase + t;
         if (ok) {
@@ -685,7 +708,7 @@ __global__ void __launch_bounds__(64) k_lz_fill(LzCtx c, const LzOutStream* outs
                 tok[ti + 1] = make_uint2(256u, (uint32_t)(myPos + len));
                 blocks[o.blkBase + b].uLen = myPos + len;         // end position; the host subtracts uStart
                 blocks[o.blkBase + b].refCount = myRef + (dist ? 1 : 0);   // end record; the host subtracts refStart
-                blocks[o.blkBase + b].lastTop = myPos + ((o.flags & LZ_OUT_TOP_AT_TOKEN) ? 0 : 1);
+                blocks[o.blkBase + b].lastTop = myTop + ((o.flags & LZ_OUT_TOP_AT_TOKEN) ? 0 : 1);
             }
         }
         pos += __shfl(il, 63);
@@ -886,7 +909,9 @@ __global__ void __launch_bounds__(64) k_lz_blocks(const LzStream* streams, const
         const long long storedLen = B.uLen;
         // zlib can only store a block whose first byte is still in its window (block_start >= 0).  The window base
         // when the block is flushed follows from the loop-top position of that iteration (fill_window slides by
-        // 32 KiB whenever a loop top finds strstart >= base + 65274 with fewer than 262 bytes of lookahead).
+        // 32 KiB whenever a loop top finds strstart >= base + 65274 with fewer than 262 bytes of lookahead).  With a preset
+        // dictionary the window starts with its tail: base, top, st.len and the block's first byte below are positions of the
+        // concatenation (block_start = dictLength after deflateSetDictionary).
         long long base = 0;
         {
             const long long top = B.isLast ? st.len : B.lastTop;
@@ -898,7 +923,7 @@ __global__ void __launch_bounds__(64) k_lz_blocks(const LzStream* streams, const
             }
         }
         int type;
-        if (storedLen + 4 <= best && B.uStart >= base) type = D4G_STORED;
+        if (storedLen + 4 <= best && B.uStart + st.dictLen >= base) type = D4G_STORED;
         else if ((o.flags & LZ_OUT_FIXED) || staticLenb == best) type = D4G_FIXED;
         else type = D4G_DYNAMIC;
         long long litBits = 0;

@@ -51,21 +51,43 @@ inline std::string lz_spec_refusal(const LzSpecL& s, size_t nIn) {
     return "";
 }
 
+// Preset dictionaries (deflateSetDictionary, zlib 1.2.11): the tail that counts is the last w_size = 32768 bytes, and a
+// dictionary of length 0 is none.  dictOf: per input an index, or -1.
+inline i64 lz_dict_tail(size_t nDict, const size_t* dictLen, const int32_t* dictOf, size_t input) {
+    if (!nDict || !dictOf || dictOf[input] < 0) return 0;
+    return (i64)std::min<size_t>(dictLen[dictOf[input]], LZ_SORT_BLOCK);
+}
+// why specs are refused next to these dictionaries ("" = accepted; the specs have passed lz_spec_refusal)
+inline std::string lz_dict_spec_refusal(size_t nOut, const LzSpecL* sp, size_t nDict, const size_t* dictLen, const int32_t* dictOf) {
+    for (size_t i = 0; i < nOut; i++)
+        if (sp[i].encoder == LZ_FLAVOR_JZLIB && lz_dict_tail(nDict, dictLen, dictOf, (size_t)sp[i].input) > 0)
+            return "encoder spec: the jzlib flavour takes no preset dictionary (jzlib's setDictionary follows an older zlib rule — a 32506-byte tail, "
+                   "the last two strings never inserted — that nothing here can pin)";
+    return "";
+}
+
 struct LzFront {
     Batch& B;
     std::vector<LzSpecL> specs;   // levels resolved (-1 -> 6)
-    std::vector<i64> rawLen, rawU;
+    std::vector<i64> rawLen, rawU;   // per input: its length and where its first byte lies in dU (16-byte aligned)
+    std::vector<i64> dictTail;       // per input: bytes of dictionary tail that lie in dU right before it (0: none)
     explicit LzFront(Batch& b) : B(b) {}
 
-    void create(size_t nIn, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpec* sp, bool fromDevice = false) {
+    // the specs of the level-9 entry points (DEFAULT / FILTERED / HUFFMAN_ONLY only) as specs with a level
+    static std::vector<LzSpecL> at_level_9(size_t nIn, size_t nOut, const LzSpec* sp) {
         for (size_t i = 0; i < nOut; i++)
             if (sp[i].input < 0 || (size_t)sp[i].input >= nIn || sp[i].encoder < 0 || sp[i].encoder > 1 || sp[i].strategy < 0 || sp[i].strategy > 2)
                 throw std::runtime_error("bad encoder spec");
         std::vector<LzSpecL> l(nOut);
         for (size_t i = 0; i < nOut; i++) l[i] = {sp[i].input, sp[i].encoder, sp[i].strategy, 9};
-        create(nIn, raw, len, nOut, l.data(), fromDevice);
+        return l;
     }
-    void create(size_t nIn, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpecL* sp, bool fromDevice = false) {
+    // dict / dictLen / dictOf (host memory; the caller has checked them — dict_refusal and lz_dict_spec_refusal, libdeft4g.hip): per input that names a
+    // dictionary, dU holds [tail of the dictionary][input] contiguously, padded IN FRONT of the tail so that the input
+    // stays 16-byte aligned (the optimiser, the writer and the checksums load it so); the encoder kernels read the tail
+    // bytewise or through the aligned-down window staging.  The output streams carry that copy as their HStream::dict.
+    void create(size_t nIn, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpecL* sp, bool fromDevice = false, size_t nDict = 0,
+                const uint8_t* const* dict = nullptr, const size_t* dictLen = nullptr, const int32_t* dictOf = nullptr) {
         memset(&B.stats, 0, sizeof(B.stats));
         double t0 = now_ms();
         specs.assign(sp, sp + nOut);
@@ -76,21 +98,35 @@ struct LzFront {
         }
         rawLen.resize(nIn);
         rawU.resize(nIn);
+        dictTail.resize(nIn);
         i64 off = 0;
         for (size_t i = 0; i < nIn; i++) {
-            if ((i64)len[i] >= 0x7fff0000LL) throw std::runtime_error("input of 2 GiB or more: split it");
+            dictTail[i] = lz_dict_tail(nDict, dictLen, dictOf, i);
+            if ((i64)len[i] + dictTail[i] >= 0x7fff0000LL) throw std::runtime_error("input of 2 GiB or more: split it");
             rawLen[i] = (i64)len[i];
-            rawU[i] = off;
-            off += (((i64)len[i] + 15) & ~15LL) + 512;   // zero padding: the kernels read (never use) a few words past the end
+            rawU[i] = off + ((dictTail[i] + 15) & ~15LL);
+            off = rawU[i] + (((i64)len[i] + 15) & ~15LL) + 512;   // zero padding: the kernels read (never use) a few words past the end
             B.stats.bytes_decoded += (i64)len[i];
+            B.stats.dict_bytes += dictTail[i];
         }
         B.dU.alloc_zero((size_t)off, 1024);
         for (size_t i = 0; i < nIn; i++) {
             if (fromDevice) rt_d2d(B.dU + rawU[i], raw[i], len[i]);
             else rt_h2d(B.dU + rawU[i], raw[i], len[i]);
+            if (dictTail[i]) {
+                const size_t d = (size_t)dictOf[i];
+                rt_h2d(B.dU + rawU[i] - dictTail[i], dict[d] + (dictLen[d] - (size_t)dictTail[i]), (size_t)dictTail[i]);
+            }
         }
         rt_sync();
         B.streams.resize(nOut);
+        for (size_t o = 0; o < nOut; o++) {
+            const i64 t = dictTail[specs[o].input];
+            if (!t) continue;
+            B.streams[o].dict = B.dU + rawU[specs[o].input] - t;
+            B.streams[o].dictLen = t;
+            B.stats.dict_streams++;
+        }
         B.stats.n_streams = (i64)nOut;
         B.stats.ms_upload = now_ms() - t0;
     }
@@ -108,14 +144,17 @@ struct LzFront {
         std::vector<LzSortJob> sortJobs;
         i64 posTot = 0;
         for (size_t i = 0; i < nIn; i++) {
-            hs[i].data = B.dU + rawU[i];
-            hs[i].len = rawLen[i];
+            // positions, chunks and sort blocks are those of tail(dictionary) || input (d4g_lz77.h, "Coordinates")
+            hs[i].data = B.dU + rawU[i] - dictTail[i];
+            hs[i].len = dictTail[i] + rawLen[i];
+            hs[i].dictLen = dictTail[i];
             hs[i].posBase = posTot;
             hs[i].sortBlock0 = (int32_t)(posTot / LZ_SORT_BLOCK);
-            hs[i].nChunks = (int32_t)((rawLen[i] + LZ_CHUNK - 1) / LZ_CHUNK);
-            i64 nsb = (rawLen[i] + LZ_SORT_BLOCK - 1) / LZ_SORT_BLOCK;
+            hs[i].nChunks = (int32_t)((hs[i].len + LZ_CHUNK - 1) / LZ_CHUNK);
+            i64 nsb = rawLen[i] > 0 ? (hs[i].len + LZ_SORT_BLOCK - 1) / LZ_SORT_BLOCK : 0;   // (an empty input is never sorted, dictionary or not)
             posTot += nsb * LZ_SORT_BLOCK;
         }
+        auto first_chunk = [&](int input) { return (int)(dictTail[input] / LZ_CHUNK); };   // the chunk that holds the input's first byte
         // parses needed: one per (input, effective parse) — lz_parse_key; HUFFMAN_ONLY needs neither sort nor parse, and
         // deflate_rle no sort.  deflate_fast parses also get an insertion map (LZ_CHUNK_WORDS words per chunk).
         std::map<LzParseKey, int> parseOf;
@@ -130,11 +169,11 @@ struct LzFront {
             parses.push_back({key.input, key.kind, key.strategy, key.level, metaTot, key.kind == LZ_KIND_FAST ? insTot : -1});
             metaTot += hs[s.input].nChunks;
             if (key.kind == LZ_KIND_FAST) insTot += (i64)hs[s.input].nChunks * LZ_CHUNK_WORDS;
-            if (key.kind != LZ_KIND_RLE) needSort[s.input] = 1;
+            if (key.kind != LZ_KIND_RLE && rawLen[s.input] > 0) needSort[s.input] = 1;   // (an empty input behind a dictionary: nothing is searched)
         }
         for (size_t i = 0; i < nIn; i++)
             if (needSort[i])
-                for (i64 b = 0; b * LZ_SORT_BLOCK < rawLen[i]; b++) sortJobs.push_back({(int32_t)i, (int32_t)b});
+                for (i64 b = 0; b * LZ_SORT_BLOCK < hs[i].len; b++) sortJobs.push_back({(int32_t)i, (int32_t)b});
         // device buffers of the front end that must not outlive it: released before the batch's own phases start
         RtScratch tmp;
         LzStream* dStreamsLz = tmp.alloc<LzStream>(nIn, 16);
@@ -201,11 +240,27 @@ struct LzFront {
             std::vector<uint8_t> chunkFast((size_t)metaTot, 0);
             for (size_t pi = 0; pi < parses.size(); pi++) {
                 const Parse& P = parses[pi];
-                for (int fc = 0; fc < hs[P.input].nChunks; fc += LZ_PARSE_MAXWAVES) { jobs.push_back(makeJob(P, fc)); jobKind.push_back(P.kind); }
+                // (the chunks before the input's first byte lie wholly in the dictionary: nothing to parse)
+                for (int fc = first_chunk(P.input); fc < hs[P.input].nChunks; fc += LZ_PARSE_MAXWAVES) { jobs.push_back(makeJob(P, fc)); jobKind.push_back(P.kind); }
                 for (int k = 0; k < hs[P.input].nChunks; k++) {
                     chunkIndex[P.metaBase + k] = k; chunkParse[P.metaBase + k] = (int32_t)pi;
                     chunkFast[P.metaBase + k] = P.kind == LZ_KIND_FAST;
                 }
+            }
+            // Dictionary chunks record no tokens and hand the first parsed chunk its exact start: entry = exit =
+            // lz_pack_state(dictLen, 0, 2, 0), so k_lz_check's induction begins at the chunk that holds dictLen.  (An
+            // input that ends where its dictionary does has no such chunk, or one that finds nothing to do.)  Only these
+            // metas are the host's; every other chunk is launched and writes its own.
+            for (const Parse& P : parses) {
+                const int nd = std::min(first_chunk(P.input), (int)hs[P.input].nChunks);
+                if (nd == 0) continue;
+                LzChunkMeta m;
+                memset(&m, 0, sizeof(m));
+                m.entry = m.exit = lz_pack_state(dictTail[P.input], 0, 2, 0);
+                m.firstPos = (uint32_t)dictTail[P.input];
+                std::vector<LzChunkMeta> init((size_t)nd, m);
+                for (int k = 0; k < nd; k++) init[k].chainStart = k;
+                rt_h2d(dMeta + P.metaBase, init.data(), init.size() * sizeof(LzChunkMeta));
             }
             if (dFast) rt_h2d(dFast, chunkFast.data(), (size_t)metaTot);
             RtScratch st;
@@ -299,7 +354,7 @@ struct LzFront {
                     if (m.ntok) lastIsMatch = (m.pad >> 9) != 0;
                 }
             } else {
-                for (int k = 0; k < st.nChunks; k++) symPre[k + 1] = std::min<i64>(st.len, (i64)(k + 1) * LZ_CHUNK);
+                for (int k = 0; k < st.nChunks; k++) symPre[k + 1] = std::max<i64>(0, std::min<i64>(st.len, (i64)(k + 1) * LZ_CHUNK) - st.dictLen);
             }
             lastIsMatchOf[oi] = lastIsMatch;
             outSyms[oi] = symPre[st.nChunks];
@@ -347,7 +402,7 @@ struct LzFront {
                 LzBlockDesc d;
                 memset(&d, 0, sizeof(d));
                 d.symStart = symStart; d.symCount = symCount; d.out = (int32_t)oi; d.isLast = isLast;
-                d.uStart = d.uLen = st.len; d.refStart = d.refCount = R;   // (an empty block: overwritten for the others)
+                d.uStart = d.uLen = st.len - st.dictLen; d.refStart = d.refCount = R;   // (an empty block: overwritten for the others)
                 blocks.push_back(d);
             };
             if (sp.encoder == LZ_FLAVOR_JZLIB) {
@@ -378,7 +433,8 @@ struct LzFront {
             tokTot += N + o.nBlocks;
             refTot += R;
             for (int k = 0; k < std::max(1, (int)st.nChunks); k++)
-                fillJobs.push_back({(int32_t)oi, (int32_t)k, k < st.nChunks ? symPreOf[oi][k] : 0, k < st.nChunks ? refPreOf[oi][k] : 0});
+                if (k == 0 || k >= first_chunk(sp.input))   // (chunk 0 also writes an empty last block's token; dictionary chunks hold none)
+                    fillJobs.push_back({(int32_t)oi, (int32_t)k, k < st.nChunks ? symPreOf[oi][k] : 0, k < st.nChunks ? refPreOf[oi][k] : 0});
         }
         if (refTot >= (1LL << 32)) throw std::runtime_error("batch holds 2^32 or more back-references: split it");
         // ---- 4. tokens / records in the optimiser's layout ----

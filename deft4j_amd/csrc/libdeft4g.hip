@@ -171,14 +171,19 @@ std::unique_ptr<d4g_batch> make_batch_dict(size_t n, const uint8_t* const* in, c
 }
 static_assert(sizeof(LzSpec) == sizeof(d4g_encoder_spec), "spec layout");
 static_assert(sizeof(LzSpecL) == sizeof(d4g_encoder_spec_level), "spec layout");
-template <class Spec>   // LzSpec or LzSpecL
-std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const Spec* spec,
-                                        bool fromDevice = false) {
+// every encoder batch is made here; the dictionary arguments (host memory, n_dict = 0: none) have passed dict_refusal
+std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpecL* spec,
+                                        bool fromDevice = false, size_t n_dict = 0, const uint8_t* const* dict = nullptr,
+                                        const size_t* dict_len = nullptr, const int32_t* dict_of = nullptr) {
     std::unique_ptr<d4g_batch> e(new d4g_batch());
     e->ctx = rt_ctx();
     e->lz.reset(new LzFront(e->impl));
-    e->lz->create(n, raw, len, nOut, spec, fromDevice);
+    e->lz->create(n, raw, len, nOut, spec, fromDevice, n_dict, dict, dict_len, dict_of);
     return e;
+}
+std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpec* spec,
+                                        bool fromDevice = false) {
+    return encode_batch(n, raw, len, nOut, LzFront::at_level_9(n, nOut, spec).data(), fromDevice);   // (the level-9 entry points)
 }
 // one stream, parsed (and decoded): d4g_size_bits_fallback, d4g_inflate
 std::unique_ptr<d4g_batch> parse_one(const uint8_t* in, size_t len, bool decode, const uint8_t* dict = nullptr, size_t dict_len = 0) {
@@ -342,6 +347,35 @@ int encode_into(d4g_batch& b, uint8_t** out, size_t* out_len) {
     }
     return D4G_OK;
 }
+// d4g_batch_create_encode_level and d4g_batch_create_encode_dict (n_dict = 0: the former), the guard held by the caller
+int create_encode_into(d4g_batch** b, size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_dict, const uint8_t* const* dict,
+                       const size_t* dict_len, const int32_t* dict_of, size_t n_out, const d4g_encoder_spec_level* spec) {
+    if ((n_in && (!raw || !raw_len)) || (n_out && !spec)) return fail(D4G_ERR_ARG, "null argument");
+    const LzSpecL* sp = (const LzSpecL*)spec;
+    for (size_t i = 0; i < n_out; i++) {
+        const std::string why = lz_spec_refusal(sp[i], n_in);
+        if (!why.empty()) return fail(D4G_ERR_ARG, why);
+    }
+    std::string why = dict_refusal(n_in, n_dict, dict, dict_len, dict_of);
+    if (why.empty()) why = lz_dict_spec_refusal(n_out, sp, n_dict, dict_len, dict_of);
+    if (!why.empty()) return fail(D4G_ERR_ARG, why);
+    *b = encode_batch(n_in, raw, raw_len, n_out, sp, false, n_dict, dict, dict_len, dict_of).release();
+    return D4G_OK;
+}
+// d4g_deflate_streams_level and d4g_deflate_streams_dict (n_dict = 0: the former): takes the guard
+int deflate_streams_into(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy, size_t n_dict,
+                         const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of, uint8_t** out, size_t* out_len) {
+    if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
+    Outputs o(n, out, out_len);
+    std::string why = lz_spec_refusal(LzSpecL{0, encoder, strategy, level}, 1);
+    if (why.empty()) why = dict_refusal(n, n_dict, dict, dict_len, dict_of);
+    if (!why.empty()) return fail(D4G_ERR_ARG, why);
+    std::vector<LzSpecL> sp(n);
+    for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy, level};
+    why = lz_dict_spec_refusal(n, sp.data(), n_dict, dict_len, dict_of);
+    if (!why.empty()) return fail(D4G_ERR_ARG, why);
+    return o.commit(api(nullptr, [&] { return encode_into(*encode_batch(n, raw, raw_len, n, sp.data(), false, n_dict, dict, dict_len, dict_of), out, out_len); }));
+}
 
 }  // namespace
 
@@ -479,29 +513,25 @@ int d4g_batch_run_encode(d4g_batch* b, int optimise, int merge_blocks) {
 d4g_batch* d4g_batch_create_encode_level(size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_out,
                                          const d4g_encoder_spec_level* spec) {
     d4g_batch* b = nullptr;
-    api(nullptr, [&] {
-        if ((n_in && (!raw || !raw_len)) || (n_out && !spec)) return fail(D4G_ERR_ARG, "null argument");
-        for (size_t i = 0; i < n_out; i++) {
-            const std::string why = lz_spec_refusal(((const LzSpecL*)spec)[i], n_in);
-            if (!why.empty()) return fail(D4G_ERR_ARG, why);
-        }
-        b = encode_batch(n_in, raw, raw_len, n_out, (const LzSpecL*)spec).release();
-        return D4G_OK;
-    });
+    api(nullptr, [&] { return create_encode_into(&b, n_in, raw, raw_len, 0, nullptr, nullptr, nullptr, n_out, spec); });
+    return b;
+}
+
+d4g_batch* d4g_batch_create_encode_dict(size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_dict, const uint8_t* const* dict,
+                                        const size_t* dict_len, const int32_t* dict_of, size_t n_out, const d4g_encoder_spec_level* spec) {
+    d4g_batch* b = nullptr;
+    api(nullptr, [&] { return create_encode_into(&b, n_in, raw, raw_len, n_dict, dict, dict_len, dict_of, n_out, spec); });
     return b;
 }
 
 int d4g_deflate_streams_level(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy,
                               uint8_t** out, size_t* out_len) {
-    if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
-    Outputs o(n, out, out_len);
-    const std::string why = lz_spec_refusal(LzSpecL{0, encoder, strategy, level}, 1);
-    if (!why.empty()) return fail(D4G_ERR_ARG, why);
-    return o.commit(api(nullptr, [&] {
-        std::vector<LzSpecL> sp(n);
-        for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy, level};
-        return encode_into(*encode_batch(n, raw, raw_len, n, sp.data()), out, out_len);
-    }));
+    return deflate_streams_into(n, raw, raw_len, encoder, level, strategy, 0, nullptr, nullptr, nullptr, out, out_len);
+}
+
+int d4g_deflate_streams_dict(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy, size_t n_dict,
+                             const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of, uint8_t** out, size_t* out_len) {
+    return deflate_streams_into(n, raw, raw_len, encoder, level, strategy, n_dict, dict, dict_len, dict_of, out, out_len);
 }
 
 int d4g_deflate_streams(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int strategy, uint8_t** out,

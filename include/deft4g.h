@@ -94,7 +94,8 @@ typedef struct d4g_stats {
      * whose coded code lengths also give complete codes, which is what the probe is run on */
     int64_t scan_kept;
     /* preset dictionaries (d4g_batch_create_dict): streams of the batch that have one (of non-zero length), and the bytes of
-     * dictionary tails uploaded — each dictionary once, its last 32 768 bytes at most, however many streams name it */
+     * dictionary tails uploaded — each dictionary once, its last 32 768 bytes at most, however many streams name it (an
+     * encoder batch, d4g_batch_create_encode_dict: once per input that names it, in front of the input) */
     int64_t dict_streams, dict_bytes;
 } d4g_stats;
 
@@ -130,8 +131,9 @@ d4g_batch* d4g_batch_create_on(int context, size_t n, const uint8_t* const* in, 
  * NULL dictionary with a length.
  * Everything a batch can be asked works on such a batch — parse, run with and without mergeBlocks, outputs, decoded bytes,
  * checksums, block info, parse errors (DISTANCE_TOO_FAR by the rule above), recovery, and verification, which parses the
- * written stream again with the same dictionary — except d4g_batch_run_recompress with a mode above NONE: the LZ77 and Zopfli
- * encoders take no dictionary, so a batch that holds any dictionary stream is refused there with D4G_ERR_ARG. */
+ * written stream again with the same dictionary — except d4g_batch_run_recompress with a mode above NONE: its jzlib and
+ * Zopfli compressors take no dictionary, so a batch that holds any dictionary stream is refused there with D4G_ERR_ARG.  (The
+ * zlib-flavour LZ77 encoder does write dictionary streams from raw data: d4g_batch_create_encode_dict, below.) */
 d4g_batch* d4g_batch_create_dict(size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict, const uint8_t* const* dict,
                                  const size_t* dict_len, const int32_t* dict_of);
 d4g_batch* d4g_batch_create_dict_on(int context, size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict,
@@ -191,6 +193,23 @@ d4g_batch* d4g_batch_create_encode_level(size_t n_in, const uint8_t* const* raw,
                                          const d4g_encoder_spec_level* spec);
 int d4g_deflate_streams_level(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy,
                               uint8_t** out, size_t* out_len);
+/* The same with preset dictionaries: output byte-identical to zlib 1.2.11 deflateInit2(level, Z_DEFLATED, -15, 8, strategy)
+ * followed by deflateSetDictionary(dict, dict_len) — raw DEFLATE, no header: a zlib wrapper's DICTID is the Adler-32 of the
+ * whole dictionary as passed.  zlib 1.2.11's rule: only the dictionary's last 32 768 bytes count, all of its strings are
+ * inserted at every level, and the stream is what deflate would write from position L of tail || input on; a dictionary of
+ * length 0 is none, and HUFFMAN_ONLY ignores it.  dict_of[i] = index of INPUT i's dictionary, -1: none; dict_of NULL or
+ * n_dict 0: the calls above.  The dictionary arguments are checked as d4g_batch_create_dict checks them.  The batch's
+ * streams carry their dictionary: run_encode with optimise = 1, verification (D4G_VERIFY, d4g_batch_verify), block info and
+ * checksums work as on a d4g_batch_create_dict batch.
+ * Scope limits: the jzlib flavour with a dictionary is refused (D4G_ERR_ARG / NULL) — jzlib's setDictionary follows the older
+ * zlib rule (a 32 506-byte tail, the last two strings never inserted, dictionaries under 3 bytes ignored), which nothing
+ * here can pin; the Zopfli encoder takes no dictionary; d4g_batch_run_recompress keeps refusing dictionary batches. */
+d4g_batch* d4g_batch_create_encode_dict(size_t n_in, const uint8_t* const* raw, const size_t* raw_len, size_t n_dict,
+                                        const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of /* per input, -1 = none */,
+                                        size_t n_out, const d4g_encoder_spec_level* spec);
+int d4g_deflate_streams_dict(size_t n, const uint8_t* const* raw, const size_t* raw_len, int encoder, int level, int strategy,
+                             size_t n_dict, const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of, uint8_t** out,
+                             size_t* out_len);
 
 /* ---- recompress modes (deft4j-cmd/.../cmd/CMDUtil.java:44-50, Optimise.java `--mode`) ----
  * mode = ordinal of RecompressMode: the compressor list CompressionUtil.getCompressors builds for it (:44-78), in list

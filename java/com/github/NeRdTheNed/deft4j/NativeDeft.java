@@ -67,6 +67,9 @@ public final class NativeDeft {
     /** The same at a Deflater / zlib level: -1 (DEFAULT_COMPRESSION = 6) or 1..9; strategies add RLE and FIXED */
     public static native byte[][] deflateStreamsLevel(byte[][] raw, int encoder, int level, int strategy) throws java.io.IOException;
 
+    /** The same with one preset dictionary for every buffer (Deflater.setDictionary, zlib 1.2.11's rule); ENC_JVM only */
+    public static native byte[][] deflateStreamsDict(byte[][] raw, int encoder, int level, int strategy, byte[] dictionary) throws java.io.IOException;
+
     /** MultiCafeUndZopfliCompressor / MultiJZopfliCompressor.compressWithOptions for every buffer (splitting: 0 FIRST, 1 LAST, 2 NONE) */
     public static native byte[][] zopfliStreams(byte[][] raw, int iterations, int splitting, int maxBlocks, long masterBlock) throws java.io.IOException;
 

@@ -16,6 +16,7 @@ public class GpuCompressor implements SingleCompressor {
     private final int encoder;
     private final int level;
     private final int strategy;
+    private byte[] dictionary;
 
     public GpuCompressor(int encoder, int strategy) {
         this(encoder, 9, strategy);
@@ -27,8 +28,19 @@ public class GpuCompressor implements SingleCompressor {
         this.strategy = strategy;
     }
 
+    /**
+     * A preset dictionary in the manner of Deflater.setDictionary: every later compressSingle writes its stream against it
+     * (raw DEFLATE; a reader needs the same dictionary).  null or an empty array: none.  ENC_JVM only.
+     */
+    public void setDictionary(byte[] dictionary) {
+        this.dictionary = dictionary == null || dictionary.length == 0 ? null : dictionary.clone();
+    }
+
     @Override
     public byte[] compressSingle(byte[] uncompressedData) throws IOException {
+        if (dictionary != null) {
+            return NativeDeft.deflateStreamsDict(new byte[][] { uncompressedData }, encoder, level, strategy, dictionary)[0];
+        }
         if (level == 9 && strategy <= NativeDeft.STRATEGY_HUFFMAN_ONLY) {
             return NativeDeft.deflateStreams(new byte[][] { uncompressedData }, encoder, strategy)[0];
         }

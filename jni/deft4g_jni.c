@@ -193,6 +193,30 @@ JNIEXPORT jobjectArray JNICALL JFN(deflateStreamsLevel)(JNIEnv* e, jclass c, job
     return res;
 }
 
+/* byte[][] deflateStreamsDict(byte[][] raw, int encoder, int level, int strategy, byte[] dictionary): the same with one preset
+ * dictionary for every buffer (Deflater.setDictionary; a dictionary of length 0 is none) */
+JNIEXPORT jobjectArray JNICALL JFN(deflateStreamsDict)(JNIEnv* e, jclass c, jobjectArray raw, jint encoder, jint level, jint strategy, jbyteArray dictionary) {
+    (void)c;
+    in_list L = {0};
+    jobjectArray res = NULL;
+    /* a null dictionary is none (n_dict = 0: deflateStreamsLevel), as GpuCompressor.setDictionary(null) means */
+    const size_t dlen = dictionary ? (size_t)(*e)->GetArrayLength(e, dictionary) : 0;
+    jbyte* d = dictionary ? (*e)->GetByteArrayElements(e, dictionary, NULL) : NULL;
+    if ((d || !dictionary) && pin(e, raw, &L) == 0) {
+        uint8_t** out = calloc((size_t)L.n + 1, sizeof *out);
+        size_t* olen = calloc((size_t)L.n + 1, sizeof *olen);
+        int32_t* of = calloc((size_t)L.n + 1, sizeof *of);               /* every input names dictionary 0 */
+        const uint8_t* dp = (const uint8_t*)d;
+        if (out && olen && of && d4g_deflate_streams_dict((size_t)L.n, L.ptr, L.len, encoder, level, strategy, d ? 1 : 0, &dp, &dlen, of, out, olen) == D4G_OK)
+            res = to_java(e, L.n, out, olen);
+        else throw_io(e, "d4g_deflate_streams_dict");
+        free(out); free(olen); free(of);
+    }
+    unpin(e, &L);
+    if (d) (*e)->ReleaseByteArrayElements(e, dictionary, d, JNI_ABORT);
+    return res;
+}
+
 /* byte[][] zopfliStreams(byte[][] raw, int iterations, int splitting, int maxBlocks, long masterBlock):
  * MultiCafeUndZopfliCompressor / MultiJZopfliCompressor.compressWithOptions for every buffer */
 JNIEXPORT jobjectArray JNICALL JFN(zopfliStreams)(JNIEnv* e, jclass c, jobjectArray raw, jint iterations, jint splitting, jint maxBlocks, jlong masterBlock) {
