@@ -3,7 +3,8 @@
 // that depend on a stream-wide bit position (stored-block alignment); all token, Huffman and header arithmetic runs in
 // the HIP kernels.  This header holds the batch's data; its phases are defined in the d4g_host_*.h headers included at
 // the end (parse, search, merge, write), the search program and the per-process engine in d4g_program.h, and every
-// environment knob in d4g_knobs.h.
+// environment knob in d4g_knobs.h.  The drivers above a batch have headers of their own: the encoders' front ends (d4g_lz77_host.h,
+// d4g_zopfli_host.h), the stream finder (d4g_host_find.h) and CompressionUtil.compress with CMDUtil.optimise's loop (d4g_host_recompress.h).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -39,6 +40,11 @@ static inline int seg_threads() {
 static inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+// bytes in device memory; a bit stream's are its whole bytes (a DEFLATE stream ends inside its last byte)
+struct DevBytes { const uint8_t* p; size_t len; };
+struct DevList { std::vector<const uint8_t*> p; std::vector<size_t> len; void add(DevBytes b) { p.push_back(b.p); len.push_back(b.len); } };   // as the arrays Batch::create takes
+static inline DevBytes dev_bits(const uint32_t* words, i64 bits) { return {(const uint8_t*)words, (size_t)((bits + 7) / 8)}; }
 
 // host view of one block of a stream
 struct HBlock {
@@ -213,7 +219,9 @@ struct Batch {
     void phase_write();
     void checksums();
     D4GCsumOut* launch_checksums(RtScratch& tmp);
+    DevBytes out_bytes(size_t i) const { return dev_bits(dOut + streams[i].outWordBase, streams[i].outBits); }   // stream i as written
     void run(bool merge);
+    void parse_only(bool decode);
     void run_parse(bool merge);
     void run_rest(bool merge);
     void release_scratch();

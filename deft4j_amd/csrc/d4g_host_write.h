@@ -85,6 +85,12 @@ inline void Batch::run(bool merge) {
     run_parse(merge);
     run_rest(merge);
 }
+// no search and no output: the streams' parse and, with `decode`, their decoded bytes (d4g_batch_parse, the one-shot questions, verification)
+inline void Batch::parse_only(bool decode) {
+    engine().init();
+    parse_probe();
+    if (decode) build_blocks(false, false);
+}
 // run() in two steps, for callers that start other work on the decoded bytes between them (the recompress modes)
 inline void Batch::run_parse(bool merge) {
     if (ran) throw std::runtime_error("batch already ran");
@@ -153,9 +159,7 @@ inline void verify_items(std::vector<VerifyItem>& items, bool bytesOnHost, Verif
     Batch V;
     V.create(n, p.data(), l.data(), !bytesOnHost);
     for (size_t i = 0; i < n; i++) { V.streams[i].dict = items[i].dict; V.streams[i].dictLen = items[i].dictLen; }
-    engine().init();
-    V.parse_probe();
-    V.build_blocks(false, false);
+    V.parse_only(true);
     std::vector<D4GVerifyPair> pairs;
     std::vector<size_t> owner;
     std::vector<long long> base(1, 0);

@@ -151,6 +151,15 @@ static inline bool verify_switch() { const char* v = knob_now("D4G_VERIFY"); ret
 static inline void pool_max_bytes(size_t* bytes) { if (const char* t = knob_now("D4G_POOL_MAX_MB")) *bytes = (size_t)atoll(t) << 20; }
 // D4G_GROUP_BLOCKS, now (default 12000): blocks per recompress group.
 static inline long long group_blocks() { return knob_now("D4G_GROUP_BLOCKS", 12000); }
+// The Zopfli stage of a recompress group (d4g_host_recompress.h): on the GPU a host thread of its own with low-priority
+// streams, started before the other stages; the emulator runs one kernel at a time, so there it runs inline after them.
+static inline bool zopfli_stage_threaded() {
+#ifdef D4G_HOSTSIM
+    return false;
+#else
+    return true;
+#endif
+}
 // D4G_ZF_TABLE, now: "scan" = Zopfli match table by window scan instead of sorted buckets.  D4G_ZF_POOL_WORDS, now: first size
 // of the Zopfli word pool, at least 64 (tests: start small, exercise the growth); 0 here = unset.
 static inline bool zf_table_scan() { const char* t = knob_now("D4G_ZF_TABLE"); return t && !strcmp(t, "scan"); }

@@ -72,6 +72,8 @@ struct LzFront {
     std::vector<i64> rawLen, rawU;   // per input: its length and where its first byte lies in dU (16-byte aligned)
     std::vector<i64> dictTail;       // per input: bytes of dictionary tail that lie in dU right before it (0: none)
     explicit LzFront(Batch& b) : B(b) {}
+    // input i where it lies in dU: stable from create() on, whatever runs on the batch
+    DevBytes input(size_t i) const { return {B.dU + rawU[i], (size_t)rawLen[i]}; }
 
     // the specs of the level-9 entry points (DEFAULT / FILTERED / HUFFMAN_ONLY only) as specs with a level
     static std::vector<LzSpecL> at_level_9(size_t nIn, size_t nOut, const LzSpec* sp) {
@@ -540,6 +542,22 @@ struct LzFront {
         B.stats.ms_search_kernels = B.msSearch;
         B.stats.search_bytes_algorithmic = B.stats.bytes_decoded + B.stats.bytes_out;
         B.release_scratch();
+    }
+};
+
+// A batch as the drivers and the C ABI hold it: the Batch and, when its streams come from the encoder, the front end that
+// fills it.  LzFront refers to its Batch, so the two are made in place and stay together.  The dictionary arguments (host
+// memory, nDict = 0: none) have been checked by the caller, as for LzFront::create.
+struct HostBatch {
+    Batch impl;
+    std::unique_ptr<LzFront> lz;   // set for encoder batches
+    void create_encode(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpecL* spec, bool fromDevice = false, size_t nDict = 0,
+                       const uint8_t* const* dict = nullptr, const size_t* dictLen = nullptr, const int32_t* dictOf = nullptr) {
+        lz.reset(new LzFront(impl));
+        lz->create(n, raw, len, nOut, spec, fromDevice, nDict, dict, dictLen, dictOf);
+    }
+    void create_encode(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpec* spec, bool fromDevice = false) {
+        create_encode(n, raw, len, nOut, LzFront::at_level_9(n, nOut, spec).data(), fromDevice);   // (the level-9 entry points)
     }
 };
 

@@ -241,6 +241,14 @@ inline float rt_elapsed_ms(RtEvent& a, RtEvent& b) {
 }
 #endif
 
+// HIP's current device is per thread: CompressionUtil's pool threads (and any rank with device != 0), and every thread a
+// driver starts, must bind the library's device before allocating or launching.  The emulator has no device to bind.
+inline void bind_device() {
+#ifndef D4G_HOSTSIM
+    if (rt().ready && rt().device >= 0) RT_CHECK(hipSetDevice(rt().device));
+#endif
+}
+
 // ---- device-memory ownership (both builds; the emulator's hipsim.h provides rt_malloc / rt_free / rt_sync_all) ----
 // Blocks handed out and not yet returned (debug / tests: d4g_debug_device_blocks).  The GPU build asks its pool (above);
 // the emulator's rt_malloc / rt_free are calloc / free, so there the two owners count what passes through them.

@@ -20,6 +20,31 @@ namespace d4g {
 
 struct ZfSpec { int32_t input, iterations, splitting, maxblocks; long long master; };
 
+// what an encode cost: wall clock of the match tables, the block-split searches, the squeeze kernel and the block choice +
+// emission; blocks squeezed; squeeze work = sum over blocks of iterations x block bytes (d4g_stats' zopfli fields)
+struct ZfFigures {
+    double msTable = 0, msSplit = 0, msSqueeze = 0, msEmit = 0;
+    i64 blocks = 0, positions = 0;
+    void operator+=(const ZfFigures& o) {
+        msTable += o.msTable; msSplit += o.msSplit; msSqueeze += o.msSqueeze; msEmit += o.msEmit; blocks += o.blocks; positions += o.positions;
+    }
+};
+
+// host inputs -> one padded device buffer (16-byte aligned starts, 512 zero bytes after each end)
+struct ZfUpload {
+    RtBuf<uint8_t> buf;
+    std::vector<const uint8_t*> ptr;
+    std::vector<i64> len;
+    ZfUpload(size_t n, const uint8_t* const* raw, const size_t* raw_len) {
+        i64 off = 0;
+        std::vector<i64> at(n);
+        for (size_t i = 0; i < n; i++) { at[i] = off; off += (((i64)raw_len[i] + 15) & ~15LL) + 512; }
+        uint8_t* d = buf.alloc_zero((size_t)off, 1024);
+        for (size_t i = 0; i < n; i++) { rt_h2d(d + at[i], raw[i], raw_len[i]); ptr.push_back(d + at[i]); len.push_back((i64)raw_len[i]); }
+        rt_sync();
+    }
+};
+
 struct ZfFront {
     // (poolWords before own: members go in reverse order, and own's destructor is the one that waits when an exception unwinds)
     RtBuf<uint32_t> poolWords;      // the change-point pool's words (pool.words), replaced when the pool grows
@@ -29,8 +54,9 @@ struct ZfFront {
     ZfPool pool{};
     std::vector<uint32_t*> outWords;     // per spec: device words of the stream
     std::vector<i64> outBits;
-    double msTable = 0, msSplit = 0, msSqueeze = 0, msEmit = 0;
-    i64 squeezeBlocks = 0, squeezePositions = 0;
+    ZfFigures fig;
+
+    DevBytes out_bytes(size_t q) const { return dev_bits(outWords[q], outBits[q]); }   // the stream of spec q
 
     void release() { own.release(); poolWords.reset(); }   // the ordinary end: the caller has read its results (and so waited)
 
@@ -98,7 +124,7 @@ struct ZfFront {
                 with_pool_retry([&]() { RT_LAUNCH(k_zf_match_sorted, mj.size(), ZF_MS_THREADS, dIn, dM, pool); });
             }
         }
-        msTable += now_ms() - t0;
+        fig.msTable += now_ms() - t0;
     }
     void run_match(const std::vector<ZfMatchJob>& mj) {
         if (mj.empty()) return;
@@ -286,7 +312,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
                 for (uint32_t b : sp[q].bytePos) mbs[who[q]].cuts.push_back((i64)b);
         }
     }
-    msSplit += now_ms() - t0;
+    fig.msSplit += now_ms() - t0;
     // ---- B: squeeze every block ----
     t0 = now_ms();
     std::vector<Block> blocks;
@@ -326,8 +352,8 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
             j.lengthArray = b.la; j.path = b.path; j.iterations = iters; j.fixedModel = 0;
             jobOf[q] = jobs.size();
             jobs.push_back(j);
-            squeezeBlocks++;
-            squeezePositions += (b.end - b.start) * j.iterations;
+            fig.blocks++;
+            fig.positions += (b.end - b.start) * j.iterations;
         }
         if (!jobs.empty()) {
             ZfSqJob* dJ = own.upload(jobs);
@@ -349,7 +375,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
                             (long long)(jobs[q].v.end - jobs[q].v.start), outs[q].cyc[0], outs[q].cyc[1], outs[q].cyc[2], outs[q].cyc[3], outs[q].cyc[4]);
         }
     }
-    msSqueeze += now_ms() - t0;
+    fig.msSqueeze += now_ms() - t0;
     // ---- C: concatenate, second split ----
     t0 = now_ms();
     {
@@ -410,7 +436,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
             if (specs[m.spec].splitting == ZF_SPLIT_FIRST && total2[q] < total1[who[q]]) m.sp = s2[q].points;
         }
     }
-    msSplit += now_ms() - t0;
+    fig.msSplit += now_ms() - t0;
     // ---- D: final blocks ----
     t0 = now_ms();
     struct Fin { int mb; uint32_t a, b; ZfRangeOut c; bool expensive; int fixedBlock; ZfRangeOut cf; int btype; };
@@ -538,7 +564,7 @@ inline void ZfFront::encode(const std::vector<ZfSpec>& specs) {
         }
         rt_sync();
     }
-    msEmit += now_ms() - t0;
+    fig.msEmit += now_ms() - t0;
 }
 
 }  // namespace d4g

@@ -1,36 +1,26 @@
 // libdeft4g.hip — the single translation unit of libdeft4g.so (kernels + host + C ABI).
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -shared -fPIC -o libdeft4g.so libdeft4g.hip
-#include <functional>
+// It holds the ABI's guard, its argument checks, its entry points and the debug hooks; the drivers are in the d4g_host*.h headers.
 #include <mutex>
-#include <thread>
 
 #include "d4g_host.h"
-#include "d4g_lz77_host.h"
-#include "d4g_zopfli_host.h"
+#include "d4g_host_recompress.h"
 #include "d4g_host_find.h"
 
 using namespace d4g;
 
-struct d4g_batch {
+struct d4g_batch : HostBatch {   // (lz: set for batches made by d4g_batch_create_encode*)
     int ctx = 0;   // the context (device) the batch lives on: every call with the batch works there
-    Batch impl;
-    std::unique_ptr<LzFront> lz;   // set for batches made by d4g_batch_create_encode
-    // d4g_batch_run_recompress: the re-optimised winners of the recompression (its own copy of their bytes) and which streams took them
-    std::unique_ptr<Batch> reopt;
-    std::vector<int> reoptIndex;       // stream -> index in reopt (-1: none)
-    std::vector<char> graft;
-    std::vector<int64_t> recompSaved;
+    std::unique_ptr<Recompressed> recomp;   // d4g_batch_run_recompress: absent until a recompression ran
     // d4g_batch_verify: verdict and first mismatch per stream, and the final stream's block list as the re-parse read it
     bool verified = false;
     std::vector<int32_t> verdict;
     std::vector<int64_t> firstMismatch;
     std::vector<std::vector<Batch::PBlock>> finalBlocks;
-    // where stream i's final bytes live
-    const HStream& final_stream(size_t i, const Batch** owner) const {
-        if (i < graft.size() && graft[i]) { *owner = reopt.get(); return reopt->streams[reoptIndex[i]]; }
-        *owner = &impl;
-        return impl.streams[i];
-    }
+    bool grafted(size_t i) const { return recomp && recomp->grafted(i); }
+    int64_t graft_saved(size_t i) const { return recomp ? recomp->saved[i] : 0; }   // bits
+    // where stream i's final bytes live: the grafted recompression where it won
+    DevBytes final_bytes(size_t i) const { return grafted(i) ? recomp->bytes(i) : impl.out_bytes(i); }
 };
 
 namespace {
@@ -63,13 +53,16 @@ bool rtp_ctx_ready(int k) {
     return rtp().ctx[k].ready;
 #endif
 }
-// HIP's current device is per thread: CompressionUtil's pool threads (and any rank with device != 0) must bind
-// the library's device before allocating or launching.
-void bind_device() {
-#ifndef D4G_HOSTSIM
-    if (rt().ready && rt().device >= 0) RT_CHECK(hipSetDevice(rt().device));
-#endif
-}
+// the calling thread works on context k for a scope (the _on creators); not ok: there is no such context
+struct OnContext {
+    const int keep = g_tlsCtx;
+    const bool ok;
+    explicit OnContext(int k) : ok(k >= 0 && k < RT_MAX_CTX && rtp_ctx_ready(k)) {
+        if (ok) g_tlsCtx = k;
+        else g_err = "no such context (d4g_init_devices)";
+    }
+    ~OnContext() { g_tlsCtx = keep; }
+};
 
 // Runs `body` (returns a D4G_* code); whatever it throws becomes D4G_ERR_RUNTIME with its text — nothing crosses extern "C".
 template <class F>
@@ -97,16 +90,6 @@ int api(const d4g_batch* b, F&& body) {
         return body();
     });
 }
-
-// Joins its threads on every way out of a scope (a joinable std::thread's destructor calls std::terminate).
-struct Joiner {
-    std::vector<std::thread> threads;
-    void join() {
-        for (std::thread& t : threads)
-            if (t.joinable()) t.join();
-    }
-    ~Joiner() { join(); }
-};
 
 // The caller's result arrays of a one-shot call.  They hold the defined "unchanged" values from the start (out[i] = NULL,
 // out_len[i] = 0, status[i] = D4G_STREAM_UNCHANGED, the optional arrays cleared) and get them back, buffers freed, unless
@@ -171,27 +154,20 @@ std::unique_ptr<d4g_batch> make_batch_dict(size_t n, const uint8_t* const* in, c
 }
 static_assert(sizeof(LzSpec) == sizeof(d4g_encoder_spec), "spec layout");
 static_assert(sizeof(LzSpecL) == sizeof(d4g_encoder_spec_level), "spec layout");
-// every encoder batch is made here; the dictionary arguments (host memory, n_dict = 0: none) have passed dict_refusal
-std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpecL* spec,
-                                        bool fromDevice = false, size_t n_dict = 0, const uint8_t* const* dict = nullptr,
-                                        const size_t* dict_len = nullptr, const int32_t* dict_of = nullptr) {
+// every encoder batch of the ABI is made here, from specs with a level or (the level-9 entry points) without; dict...: n_dict, dict,
+// dict_len, dict_of (host memory), which have passed dict_refusal
+template <class Spec, class... Dict>
+std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const Spec* spec, Dict... dict) {
     std::unique_ptr<d4g_batch> e(new d4g_batch());
     e->ctx = rt_ctx();
-    e->lz.reset(new LzFront(e->impl));
-    e->lz->create(n, raw, len, nOut, spec, fromDevice, n_dict, dict, dict_len, dict_of);
+    e->create_encode(n, raw, len, nOut, spec, false, dict...);
     return e;
-}
-std::unique_ptr<d4g_batch> encode_batch(size_t n, const uint8_t* const* raw, const size_t* len, size_t nOut, const LzSpec* spec,
-                                        bool fromDevice = false) {
-    return encode_batch(n, raw, len, nOut, LzFront::at_level_9(n, nOut, spec).data(), fromDevice);   // (the level-9 entry points)
 }
 // one stream, parsed (and decoded): d4g_size_bits_fallback, d4g_inflate
 std::unique_ptr<d4g_batch> parse_one(const uint8_t* in, size_t len, bool decode, const uint8_t* dict = nullptr, size_t dict_len = 0) {
     const int32_t first = 0;
     std::unique_ptr<d4g_batch> b = make_batch_dict(1, &in, &len, dict_len ? 1 : 0, &dict, &dict_len, &first);
-    engine().init();
-    b->impl.parse_probe();
-    if (decode) b->impl.build_blocks(false, false);
+    b->impl.parse_only(decode);
     return b;
 }
 // a malloc'd copy of n bytes of device memory
@@ -203,15 +179,13 @@ uint8_t* host_copy(const void* src, size_t n) {
 }
 // a malloc'd copy of stream i's final bytes (the grafted recompression where it won)
 uint8_t* final_copy(const d4g_batch& b, size_t i, size_t* len) {
-    const Batch* owner = nullptr;
-    const HStream& s = b.final_stream(i, &owner);
-    *len = (size_t)((s.outBits + 7) / 8);
-    return host_copy(owner->dOut + s.outWordBase, *len);
+    const DevBytes f = b.final_bytes(i);
+    *len = f.len;
+    return host_copy(f.p, f.len);
 }
 int32_t stream_status(const d4g_batch& b, size_t i) {
     const HStream& s = b.impl.streams[i];
-    const bool grafted = i < b.graft.size() && b.graft[i];
-    return s.status != 0 ? D4G_STREAM_PARSE_ERROR : ((s.saved > 0 || grafted) ? D4G_STREAM_CHANGED : D4G_STREAM_UNCHANGED);
+    return s.status != 0 ? D4G_STREAM_PARSE_ERROR : ((s.saved > 0 || b.grafted(i)) ? D4G_STREAM_CHANGED : D4G_STREAM_UNCHANGED);
 }
 // ---- round-trip verification (verify_items, d4g_host.h) ----
 const char* verdict_name(int v) {
@@ -276,15 +250,13 @@ int batch_verify(d4g_batch& b, const char* what, bool failOnNegative) {
     for (size_t i = 0; i < n; i++) {
         if (!stream_written(b, i)) continue;
         const HStream& s = b.impl.streams[i];
-        const Batch* owner = nullptr;
-        const HStream& f = b.final_stream(i, &owner);
         VerifyItem it;
-        it.bytes = (const uint8_t*)(owner->dOut + f.outWordBase);
-        it.len = (size_t)((f.outBits + 7) / 8);
+        it.bytes = b.final_bytes(i).p;
+        it.len = b.final_bytes(i).len;
         it.want = b.impl.dU + s.uBase;
         it.wantLen = s.nU;
         it.dict = s.dict; it.dictLen = s.dictLen;   // the written stream is parsed against the dictionary the input was
-        it.wantBits = s.sizeBitsIn - s.saved - (i < b.recompSaved.size() ? b.recompSaved[i] : 0);   // what d4g_batch_stream_result lets the caller compute
+        it.wantBits = s.sizeBitsIn - s.saved - b.graft_saved(i);   // what d4g_batch_stream_result lets the caller compute
         items.push_back(it);
         index.push_back(i);
     }
@@ -302,14 +274,9 @@ int batch_verify(d4g_batch& b, const char* what, bool failOnNegative) {
 }
 int verify_if_switched(d4g_batch& b, const char* what) { return verify_switch() ? batch_verify(b, what, true) : D4G_OK; }
 // outputs that sit in device memory outside a batch (d4g_compress, d4g_zopfli_streams) against raw inputs already on the device
-int verify_loose(size_t n, const std::function<const uint8_t*(size_t)>& bytes, const std::function<size_t(size_t)>& len,
-                 const std::function<const uint8_t*(size_t)>& want, const size_t* wantLen, const char* what) {
-    std::vector<VerifyItem> items(n);
-    std::vector<size_t> index(n);
-    for (size_t i = 0; i < n; i++) {
-        items[i].bytes = bytes(i); items[i].len = len(i); items[i].want = want(i); items[i].wantLen = (i64)wantLen[i];
-        index[i] = i;
-    }
+int verify_loose(std::vector<VerifyItem>& items, const char* what) {
+    std::vector<size_t> index(items.size());
+    for (size_t i = 0; i < index.size(); i++) index[i] = i;
     VerifyTotals T;
     verify_items(items, false, T);
     return verdicts_to_code(items, index, what);
@@ -323,7 +290,7 @@ void results_into(const d4g_batch& b, const size_t* idx, uint8_t** out, size_t* 
         status[i] = stream_status(b, j);
         if (status[i] == D4G_STREAM_CHANGED) out[i] = final_copy(b, j, &out_len[i]);
         if (saved_bits) saved_bits[i] = b.impl.streams[j].status == 0 ? b.impl.streams[j].saved : 0;
-        if (recompress_saved) recompress_saved[i] = j < b.recompSaved.size() ? b.recompSaved[j] : 0;
+        if (recompress_saved) recompress_saved[i] = b.graft_saved(j);
     }
 }
 // d4g_optimise_streams on the calling thread's context for the caller's streams idx[0..m) (0..m when idx is null)
@@ -359,7 +326,7 @@ int create_encode_into(d4g_batch** b, size_t n_in, const uint8_t* const* raw, co
     std::string why = dict_refusal(n_in, n_dict, dict, dict_len, dict_of);
     if (why.empty()) why = lz_dict_spec_refusal(n_out, sp, n_dict, dict_len, dict_of);
     if (!why.empty()) return fail(D4G_ERR_ARG, why);
-    *b = encode_batch(n_in, raw, raw_len, n_out, sp, false, n_dict, dict, dict_len, dict_of).release();
+    *b = encode_batch(n_in, raw, raw_len, n_out, sp, n_dict, dict, dict_len, dict_of).release();
     return D4G_OK;
 }
 // d4g_deflate_streams_level and d4g_deflate_streams_dict (n_dict = 0: the former): takes the guard
@@ -374,7 +341,14 @@ int deflate_streams_into(size_t n, const uint8_t* const* raw, const size_t* raw_
     for (size_t i = 0; i < n; i++) sp[i] = {(int32_t)i, encoder, strategy, level};
     why = lz_dict_spec_refusal(n, sp.data(), n_dict, dict_len, dict_of);
     if (!why.empty()) return fail(D4G_ERR_ARG, why);
-    return o.commit(api(nullptr, [&] { return encode_into(*encode_batch(n, raw, raw_len, n, sp.data(), false, n_dict, dict, dict_len, dict_of), out, out_len); }));
+    return o.commit(api(nullptr, [&] { return encode_into(*encode_batch(n, raw, raw_len, n, sp.data(), n_dict, dict, dict_len, dict_of), out, out_len); }));
+}
+// CMDUtil.optimise's per-stream loop on a batch made by d4g_batch_create (d4g_host_recompress.h)
+int recompress_batch(d4g_batch& b, int mode, int iter, bool merge) {
+    const std::string why = recompress_refusal(b.impl, mode);
+    if (!why.empty()) return fail(D4G_ERR_ARG, why);
+    b.recomp = recompress(b.impl, mode, iter, merge);
+    return D4G_OK;
 }
 
 }  // namespace
@@ -549,11 +523,9 @@ int d4g_batch_stream_result(d4g_batch* b, size_t i, int32_t* status, int64_t* sa
                             int64_t* size_bits_in) {
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     const HStream& s = b->impl.streams[i];
-    const Batch* owner = nullptr;
-    const HStream& f = b->final_stream(i, &owner);
     if (status) *status = stream_status(*b, i);
     if (saved_bits) *saved_bits = s.status == 0 ? s.saved : 0;
-    if (out_len) *out_len = s.status == 0 ? (size_t)((f.outBits + 7) / 8) : 0;
+    if (out_len) *out_len = s.status == 0 ? b->final_bytes(i).len : 0;
     if (consumed) *consumed = (size_t)s.consumed;
     if (size_bits_in) *size_bits_in = s.status == 0 ? s.sizeBitsIn : -1;
     return D4G_OK;
@@ -562,12 +534,10 @@ int d4g_batch_stream_result(d4g_batch* b, size_t i, int32_t* status, int64_t* sa
 int d4g_batch_copy_output(d4g_batch* b, size_t i, uint8_t* dst, size_t cap) {
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     if (b->impl.streams[i].status != 0) return fail(D4G_ERR_ARG, "stream did not parse");
-    const Batch* owner = nullptr;
-    const HStream& s = b->final_stream(i, &owner);
-    size_t n = (size_t)((s.outBits + 7) / 8);
-    if (cap < n) return fail(D4G_ERR_ARG, "output buffer too small");
+    const DevBytes f = b->final_bytes(i);
+    if (cap < f.len) return fail(D4G_ERR_ARG, "output buffer too small");
     return api(b, [&] {
-        rt_d2h(dst, (const uint8_t*)(owner->dOut + s.outWordBase), n);
+        rt_d2h(dst, f.p, f.len);
         return D4G_OK;
     });
 }
@@ -590,9 +560,7 @@ int d4g_batch_parse(d4g_batch* b) {
         if (!b) return fail(D4G_ERR_ARG, "null batch");
         if (b->impl.ran) return fail(D4G_ERR_ARG, "batch already ran");
         b->impl.ran = true;
-        engine().init();
-        b->impl.parse_probe();
-        b->impl.build_blocks(false, false);
+        b->impl.parse_only(true);
         return D4G_OK;
     });
 }
@@ -634,12 +602,8 @@ int d4g_optimise_streams(size_t n, const uint8_t* const* in, const size_t* in_le
 }
 
 d4g_batch* d4g_batch_create_on(int context, size_t n, const uint8_t* const* in, const size_t* in_len) {
-    if (context < 0 || context >= RT_MAX_CTX || !rtp_ctx_ready(context)) { fail(D4G_ERR_ARG, "no such context (d4g_init_devices)"); return nullptr; }
-    const int keep = g_tlsCtx;
-    g_tlsCtx = context;
-    d4g_batch* b = d4g_batch_create(n, in, in_len);
-    g_tlsCtx = keep;
-    return b;
+    OnContext on(context);
+    return on.ok ? d4g_batch_create(n, in, in_len) : nullptr;
 }
 
 // DeflateFilesContainer.optimise(List<DeflateStream>, boolean) over every initialised context (K/DeflateFilesContainer.java:18-43:
@@ -688,12 +652,8 @@ int d4g_optimise_streams_sharded(size_t n, const uint8_t* const* in, const size_
 
 d4g_batch* d4g_batch_create_dict_on(int context, size_t n, const uint8_t* const* in, const size_t* in_len, size_t n_dict,
                                     const uint8_t* const* dict, const size_t* dict_len, const int32_t* dict_of) {
-    if (context < 0 || context >= RT_MAX_CTX || !rtp_ctx_ready(context)) { fail(D4G_ERR_ARG, "no such context (d4g_init_devices)"); return nullptr; }
-    const int keep = g_tlsCtx;
-    g_tlsCtx = context;
-    d4g_batch* b = d4g_batch_create_dict(n, in, in_len, n_dict, dict, dict_len, dict_of);
-    g_tlsCtx = keep;
-    return b;
+    OnContext on(context);
+    return on.ok ? d4g_batch_create_dict(n, in, in_len, n_dict, dict, dict_len, dict_of) : nullptr;
 }
 
 int d4g_size_bits_fallback(const uint8_t* in, size_t len, int64_t* bits) {
@@ -764,23 +724,6 @@ int d4g_find_streams_dict(size_t n, const uint8_t* const* file, const size_t* fi
 }
 
 // ---- Zopfli encoder ----
-namespace {
-// host inputs -> one padded device buffer (16-byte aligned starts, 512 zero bytes after each end)
-struct ZfUpload {
-    RtBuf<uint8_t> buf;
-    std::vector<const uint8_t*> ptr;
-    std::vector<i64> len;
-    ZfUpload(size_t n, const uint8_t* const* raw, const size_t* raw_len) {
-        i64 off = 0;
-        std::vector<i64> at(n);
-        for (size_t i = 0; i < n; i++) { at[i] = off; off += (((i64)raw_len[i] + 15) & ~15LL) + 512; }
-        uint8_t* d = buf.alloc_zero((size_t)off, 1024);
-        for (size_t i = 0; i < n; i++) { rt_h2d(d + at[i], raw[i], raw_len[i]); ptr.push_back(d + at[i]); len.push_back((i64)raw_len[i]); }
-        rt_sync();
-    }
-};
-}  // namespace
-
 int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_len, int iterations, int splitting, int max_blocks,
                        size_t master_block, uint8_t** out, size_t* out_len) {
     if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
@@ -798,13 +741,15 @@ int d4g_zopfli_streams(size_t n, const uint8_t* const* raw, const size_t* raw_le
         zf.encode(specs);
         if (debug_zopfli())
             fprintf(stderr, "[zopfli] inputs %zu: table %.1f ms, split %.1f ms, squeeze %.1f ms (%lld blocks, %lld position-iterations), final+emit %.1f ms\n", n,
-                    zf.msTable, zf.msSplit, zf.msSqueeze, (long long)zf.squeezeBlocks, (long long)zf.squeezePositions, zf.msEmit);
-        if (verify_switch())
-            if (int rc = verify_loose(n, [&](size_t i) { return (const uint8_t*)zf.outWords[i]; }, [&](size_t i) { return (size_t)((zf.outBits[i] + 7) / 8); },
-                                      [&](size_t i) { return up.ptr[i]; }, raw_len, "d4g_zopfli_streams")) return rc;
+                    zf.fig.msTable, zf.fig.msSplit, zf.fig.msSqueeze, (long long)zf.fig.blocks, (long long)zf.fig.positions, zf.fig.msEmit);
+        if (verify_switch()) {
+            std::vector<VerifyItem> items(n);
+            for (size_t i = 0; i < n; i++) { items[i].bytes = zf.out_bytes(i).p; items[i].len = zf.out_bytes(i).len; items[i].want = up.ptr[i]; items[i].wantLen = (i64)raw_len[i]; }
+            if (int rc = verify_loose(items, "d4g_zopfli_streams")) return rc;
+        }
         for (size_t i = 0; i < n; i++) {
-            out_len[i] = (size_t)((zf.outBits[i] + 7) / 8);
-            out[i] = host_copy(zf.outWords[i], out_len[i]);
+            out_len[i] = zf.out_bytes(i).len;
+            out[i] = host_copy(zf.out_bytes(i).p, out_len[i]);
         }
         zf.release();
         return D4G_OK;
@@ -957,359 +902,25 @@ int d4g_debug_pack_header(const uint8_t* lens320, int nLit, int nDist, int flags
 
 void d4g_free(void* p) { free(p); }
 
-}  // extern "C"
-
-namespace {
-// compressor list of a recompress mode, in CompressionUtil.getCompressors order (C/CompressionUtil.java:44-78 with the
-// flags CMDUtil.java:44-50 derives from the mode)
-#define D4G_COMP_JZOPFLI 2   // list entries beyond the two zlib flavours: `strategy` is the option set's index
-#define D4G_COMP_CAFE 3
-bool mode_specs(int mode, std::vector<LzSpec>& list, std::string& why) {
-    list.clear();
-    if (mode < D4G_MODE_CHEAP || mode > D4G_MODE_ZOPFLI_VERY_EXTENSIVE) { why = "mode out of range"; return false; }
-    const bool extensive = mode >= D4G_MODE_ZOPFLI_EXTENSIVE;      // Strategy.EXTENSIVE (CMDUtil.java:46)
-    for (int st : {LZ_DEFAULT, LZ_FILTERED, LZ_HUFFMAN_ONLY}) list.push_back({0, LZ_FLAVOR_ZLIB, st});       // java (JVM) first (:51-58)
-    if (mode >= D4G_MODE_ZOPFLI_VERY_EXTENSIVE)                                                              // jzopfli (:60-62)
-        for (int o = 0; o < (extensive ? 5 : 1); o++) list.push_back({0, D4G_COMP_JZOPFLI, o});
-    if (mode >= D4G_MODE_ZOPFLI)                                                                             // CafeUndZopfli (:64-66)
-        for (int o = 0; o < (extensive ? 3 : 1); o++) list.push_back({0, D4G_COMP_CAFE, o});
-    for (int st : {LZ_DEFAULT, LZ_FILTERED, LZ_HUFFMAN_ONLY}) list.push_back({0, LZ_FLAVOR_JZLIB, st});      // jzlib last (:68-75)
-    return true;
-}
-// the option set of a Zopfli list entry: MultiJZopfliCompressor.getOptions (C/MultiJZopfliCompressor.java:18-60: split15/first,
-// split15/last, split0/first, split0/last, nosplit; libzopfli's 1000000-byte master block) and
-// MultiCafeUndZopfliCompressor.getOptions (C/MultiCafeUndZopfliCompressor.java:19-25,33: FIRST, LAST, NONE; 8 MiB master block)
-ZfSpec zopfli_options(const LzSpec& e, int input, int iter) {
-    ZfSpec z{};
-    z.input = input;
-    z.iterations = iter < 1 ? 1 : iter;
-    if (e.encoder == D4G_COMP_CAFE) {
-        z.splitting = e.strategy; z.maxblocks = 15; z.master = 8LL << 20;
-    } else {
-        static const int split[5] = {ZF_SPLIT_FIRST, ZF_SPLIT_LAST, ZF_SPLIT_FIRST, ZF_SPLIT_LAST, ZF_SPLIT_NONE};
-        static const int maxb[5] = {15, 15, 0, 0, 0};
-        z.splitting = split[e.strategy]; z.maxblocks = maxb[e.strategy]; z.master = 1000000;
-    }
-    return z;
-}
-
-// CompressionUtil.compress for inputs that live in host or device memory.  Inputs are processed in groups sized to the
-// device memory the candidate search needs (every block owns ~1.6 MB of candidate states); the winners' bytes are kept
-// in one device buffer.
-struct CompressRun {
-    std::vector<int> winner;             // index in list order, per input
-    std::vector<long long> bits;         // its parsed bit size
-    std::vector<size_t> off, len;        // its bytes in dWin
-    RtBuf<uint8_t> dWin;
-    size_t used = 0;
-    size_t perInput = 0;
-    d4g_stats agg;
-    int iter = 20;
-    double msZopfli = 0, msZfTable = 0, msZfSplit = 0, msZfSqueeze = 0, msZfEmit = 0;
-    int64_t zfBlocks = 0, zfPosIter = 0;
-    int64_t outputsOptimised = 0, outputsPruned = 0;
-    CompressRun() { memset(&agg, 0, sizeof(agg)); }
-};
-void add_stats(d4g_stats& a, const d4g_stats& o) {
-    a.ms_lz_sort += o.ms_lz_sort; a.ms_lz_parse += o.ms_lz_parse; a.ms_lz_emit += o.ms_lz_emit;
-    a.lz_parse_passes += o.lz_parse_passes; a.lz_chunks_rerun += o.lz_chunks_rerun; a.lz_symbols += o.lz_symbols;
-    a.ms_parse += o.ms_parse; a.ms_optimise += o.ms_optimise; a.ms_merge += o.ms_merge; a.ms_write += o.ms_write;
-    a.ms_state_kernels += o.ms_state_kernels; a.state_launches += o.state_launches;
-    a.state_tokens_per_round += o.state_tokens_per_round; a.state_bytes_per_round += o.state_bytes_per_round;
-    a.kernel_launches += o.kernel_launches; a.rounds += o.rounds; a.n_blocks += o.n_blocks; a.n_tokens += o.n_tokens;
-    a.ms_search_kernels += o.ms_search_kernels; a.ms_parse_kernels += o.ms_parse_kernels;
-    a.search_bytes_algorithmic += o.search_bytes_algorithmic;
-}
-// one group of inputs [i0, i1)
-void compress_group(CompressRun& R, size_t i0, size_t i1, const uint8_t* const* raw, const size_t* len, bool fromDevice,
-                    const std::vector<LzSpec>& list, bool merge, const std::function<void()>& afterStart) {
-    const size_t n = i1 - i0;
-    // stage 1: every compressor output that can hold back-references
-    std::vector<int> lzIdx, hIdx;   // list positions
-    std::vector<int> zIdx;          // the Zopfli entries
-    for (size_t k = 0; k < list.size(); k++) {
-        if (list[k].encoder >= D4G_COMP_JZOPFLI) zIdx.push_back((int)k);
-        else (list[k].strategy == LZ_HUFFMAN_ONLY ? hIdx : lzIdx).push_back((int)k);
-    }
-    std::vector<LzSpec> specs;
-    for (size_t i = 0; i < n; i++)
-        for (int k : lzIdx) { LzSpec s = list[k]; s.input = (int32_t)i; specs.push_back(s); }
-    std::unique_ptr<d4g_batch> e1 = encode_batch(n, raw + i0, len + i0, specs.size(), specs.data(), fromDevice);
-    // stage 3 starts here, on its own host thread (its own HIP streams): the Zopfli compressors' outputs, encoded on the device
-    // and parsed + optimised like any other stream.  A squeeze keeps a handful of waves busy for a long time; the zlib-family
-    // stages below fill the rest of the device meanwhile.  It only reads the inputs (e1's dU, stable from create on).
-    struct ZStage {
-        std::unique_ptr<d4g_batch> e3;
-        std::exception_ptr err;
-        double ms = 0, msTable = 0, msSplit = 0, msSqueeze = 0, msEmit = 0;
-        int64_t blocks = 0, posIter = 0, outputs = 0;
-    } Z;
-    const int parentCtx = rt_ctx();
-    auto zopfli_stage = [&]() {
-        try {
-            rt_ctx() = parentCtx;   // (a new host thread starts on context 0)
-#ifndef D4G_HOSTSIM
-            rt_low_priority_thread() = true;      // this thread's streams carry kernels that run for minutes (d4g_rt.h)
-#endif
-            bind_device();
-            double tz = now_ms();
-            std::vector<const uint8_t*> dp(n);
-            std::vector<i64> dl(n);
-            for (size_t i = 0; i < n; i++) { dp[i] = e1->impl.dU + e1->lz->rawU[i]; dl[i] = e1->lz->rawLen[i]; }
-            ZfFront zf;
-            zf.create(n, dp.data(), dl.data());
-            std::vector<ZfSpec> zs;
-            for (size_t i = 0; i < n; i++)
-                for (int k : zIdx) zs.push_back(zopfli_options(list[k], (int)i, R.iter));
-            zf.encode(zs);
-            Z.msTable = zf.msTable; Z.msSplit = zf.msSplit; Z.msSqueeze = zf.msSqueeze; Z.msEmit = zf.msEmit;
-            Z.blocks = zf.squeezeBlocks; Z.posIter = zf.squeezePositions; Z.outputs = (int64_t)zs.size();
-            std::vector<const uint8_t*> sp(zs.size());
-            std::vector<size_t> sl(zs.size());
-            for (size_t q = 0; q < zs.size(); q++) { sp[q] = (const uint8_t*)zf.outWords[q]; sl[q] = (size_t)((zf.outBits[q] + 7) / 8); }
-            Z.e3.reset(new d4g_batch());
-            Z.e3->ctx = rt_ctx();
-            Z.e3->impl.create(zs.size(), sp.data(), sl.data(), true);
-            Z.ms = now_ms() - tz;
-            Z.e3->impl.run(merge);
-            zf.release();
-        } catch (...) {
-            Z.err = std::current_exception();
-        }
-    };
-    Joiner zthread;   // also when a stage below throws
-#ifndef D4G_HOSTSIM
-    if (!zIdx.empty()) zthread.threads.emplace_back(zopfli_stage);
-#endif
-    const bool dbg = debug_zopfli() > 0;
-    const double tg0 = now_ms();
-    if (afterStart) afterStart();      // the caller's own work that only had to wait for the Zopfli stage to be under way
-    if (dbg) fprintf(stderr, "[group] +%.1f s: caller's work done\n", (now_ms() - tg0) / 1000);
-    e1->lz->run(true, merge);
-    if (dbg) fprintf(stderr, "[group] +%.1f s: zlib-family stage 1 done (front %.1f s, search %.1f s, merge %.1f s)\n", (now_ms() - tg0) / 1000,
-                     e1->impl.stats.ms_parse / 1000, e1->impl.stats.ms_optimise / 1000, e1->impl.stats.ms_merge / 1000);
-    add_stats(R.agg, e1->impl.stats);
-    R.outputsOptimised += (int64_t)specs.size();
-    struct Best { long long bits = 0; int listIdx = -1; const Batch* owner = nullptr; int stream = -1; };
-    std::vector<Best> best(n);
-    auto offer = [&](size_t i, int listIdx, const Batch* owner, int stream) {
-        const HStream& s = owner->streams[stream];
-        // Deft.getSizeBitsFallback of what Deft.optimiseDeflateStream returned: the written optimised stream (a stored
-        // block's padding follows its new position) or, when nothing was saved, the input
-        long long bits = s.saved > 0 ? s.outBits : s.sizeBitsIn;
-        Best& b = best[i];
-        if (b.listIdx < 0 || bits < b.bits || (bits == b.bits && listIdx < b.listIdx)) { b.bits = bits; b.listIdx = listIdx; b.owner = owner; b.stream = stream; }
-    };
-    for (size_t i = 0; i < n; i++)
-        for (size_t k = 0; k < lzIdx.size(); k++) offer(i, lzIdx[k], &e1->impl, (int)(i * lzIdx.size() + k));
-    // stage 2: the HUFFMAN_ONLY outputs, unless their entropy bound already loses
-    std::unique_ptr<d4g_batch> e2;
-    if (!hIdx.empty()) {
-        std::vector<LzBoundJob> jobs;
-        for (size_t i = 0; i < n; i++) {
-            const uint8_t* d = e1->impl.dU + e1->lz->rawU[i];
-            for (long long p = 0; p < e1->lz->rawLen[i]; p += LZ_SYMS_PER_BLOCK)
-                jobs.push_back({d + p, (int32_t)std::min<long long>(LZ_SYMS_PER_BLOCK, e1->lz->rawLen[i] - p), (int32_t)i});
-        }
-        std::vector<double> lb(n, 0.0);
-        if (!jobs.empty()) {
-            RtScratch tmp;
-            LzBoundJob* dJ = tmp.upload(jobs);
-            double* dLb = tmp.alloc<double>(n, 16);
-            rt_memset(dLb, 0, n * 8);
-            RT_LAUNCH(k_lz_entropy_bound, jobs.size(), 256, dJ, dLb);
-            rt_d2h(lb.data(), dLb, n * 8);
-            tmp.release();
-        }
-        std::vector<size_t> need;
-        for (size_t i = 0; i < n; i++) {
-            double bound = lb[i] * (1.0 - 1e-9) - 1.0;       // rounding of the sum can only have raised it by less than this
-            if (bound > (double)best[i].bits) R.outputsPruned += (int64_t)hIdx.size();
-            else need.push_back(i);
-        }
-        if (!need.empty()) {
-            std::vector<const uint8_t*> rp(need.size());
-            std::vector<size_t> rl(need.size());
-            std::vector<LzSpec> sp2;
-            for (size_t q = 0; q < need.size(); q++) {
-                rp[q] = e1->impl.dU + e1->lz->rawU[need[q]];
-                rl[q] = (size_t)e1->lz->rawLen[need[q]];
-                for (int k : hIdx) { LzSpec s = list[k]; s.input = (int32_t)q; sp2.push_back(s); }
-            }
-            e2 = encode_batch(need.size(), rp.data(), rl.data(), sp2.size(), sp2.data(), true);
-            e2->lz->run(true, merge);
-            add_stats(R.agg, e2->impl.stats);
-            R.outputsOptimised += (int64_t)sp2.size();
-            for (size_t q = 0; q < need.size(); q++)
-                for (size_t k = 0; k < hIdx.size(); k++) offer(need[q], hIdx[k], &e2->impl, (int)(q * hIdx.size() + k));
-        }
-    }
-    // stage 3's results
-    if (!zIdx.empty()) {
-#ifdef D4G_HOSTSIM
-        zopfli_stage();            // the emulator runs one kernel at a time
-#else
-        if (dbg) fprintf(stderr, "[group] +%.1f s: stage 2 done, waiting for the Zopfli stage\n", (now_ms() - tg0) / 1000);
-        zthread.join();
-        if (dbg) fprintf(stderr, "[group] +%.1f s: Zopfli stage joined (encode %.1f s, its outputs' search %.1f s + merge %.1f s)\n", (now_ms() - tg0) / 1000,
-                         Z.ms / 1000, Z.e3 ? Z.e3->impl.stats.ms_optimise / 1000 : 0.0, Z.e3 ? Z.e3->impl.stats.ms_merge / 1000 : 0.0);
-#endif
-        if (Z.err) std::rethrow_exception(Z.err);
-        R.msZfTable += Z.msTable; R.msZfSplit += Z.msSplit; R.msZfSqueeze += Z.msSqueeze; R.msZfEmit += Z.msEmit;
-        R.zfBlocks += Z.blocks; R.zfPosIter += Z.posIter;
-        R.msZopfli += Z.ms;
-        add_stats(R.agg, Z.e3->impl.stats);
-        R.outputsOptimised += Z.outputs;
-        for (size_t i = 0; i < n; i++)
-            for (size_t k = 0; k < zIdx.size(); k++) {
-                const int st = (int)(i * zIdx.size() + k);
-                if (Z.e3->impl.streams[st].status != 0) throw std::runtime_error("zopfli output does not parse");
-                offer(i, zIdx[k], &Z.e3->impl, st);
-            }
-    }
-    for (size_t i = 0; i < n; i++) {
-        const Best& b = best[i];
-        const HStream& w = b.owner->streams[b.stream];
-        size_t nb = (size_t)((w.outBits + 7) / 8);
-        R.winner[i0 + i] = b.listIdx;
-        R.bits[i0 + i] = b.bits;
-        R.off[i0 + i] = R.used;
-        R.len[i0 + i] = nb;
-        rt_d2d(R.dWin + R.used, (const uint8_t*)(b.owner->dOut + w.outWordBase), nb);
-        R.used += (nb + 15) & ~(size_t)15;
-    }
-    rt_sync();
-}
-void compress_run(CompressRun& R, size_t n, const uint8_t* const* raw, const size_t* len, bool fromDevice, int mode, int iter, bool merge,
-                  const std::function<void()>& between = nullptr) {
-    R.iter = iter;
-    int betweenState = 0;      // 0 not run, 1 running, 2 done
-    std::function<void()> once = [&]() { if (between && betweenState == 0) { betweenState = 1; between(); betweenState = 2; } };
-    std::vector<LzSpec> list;
-    std::string why;
-    if (!mode_specs(mode, list, why)) throw std::runtime_error(why);
-    R.perInput = list.size();
-    R.winner.assign(n, -1); R.bits.assign(n, 0); R.off.assign(n, 0); R.len.assign(n, 0);
-    size_t cap = 64;
-    for (size_t i = 0; i < n; i++) cap += len[i] + len[i] / 512 + 96;   // a deflate stream never exceeds its input by more than this
-    R.dWin.alloc(cap);
-    // group size: the candidate search keeps ~1.6 MB of states per block; estimate >= 3 bytes per symbol and let an
-    // out-of-memory failure halve the group
-    const long long budget = group_blocks();
-    size_t i0 = 0;
-    long long shrink = 1;
-    while (i0 < n) {
-        size_t i1 = i0;
-        long long est = 0;
-        while (i1 < n) {
-            long long e = 4 * ((long long)len[i1] / (3LL * LZ_SYMS_PER_BLOCK) + 2);
-            if (i1 > i0 && (est + e) * shrink > budget) break;
-            est += e;
-            i1++;
-        }
-        try {
-            compress_group(R, i0, i1, raw, len, fromDevice, list, merge, once);
-            i0 = i1;
-        } catch (const std::runtime_error& ex) {
-            if (betweenState != 1 && strstr(ex.what(), "hipMalloc") && i1 - i0 > 1) { shrink *= 2; continue; }   // group too large for the device: retry smaller
-            throw;
-        }
-    }
-    once();
-}
-// CMDUtil.optimise's per-stream loop on a batch made by d4g_batch_create
-int recompress_batch(d4g_batch& b, int mode, int iter, bool merge) {
-    std::vector<LzSpec> probe;
-    std::string why;
-    if (mode != D4G_MODE_NONE && !mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
-    Batch& A = b.impl;
-    if (mode != D4G_MODE_NONE && A.has_dictionary())
-        return fail(D4G_ERR_ARG, "the batch holds streams with a preset dictionary and the encoders take no dictionary: only mode NONE runs on it");
-    const size_t n = A.streams.size();
-    double t0 = now_ms();
-    // container.optimise(mergeBlocks) — CMDUtil.java:70.  In a Zopfli mode only the parse happens here: the search of the originals
-    // runs once the Zopfli stage of the recompression (its own host thread, a few long-running waves) is under way.
-    const bool deferSearch = mode >= D4G_MODE_ZOPFLI;
-    A.run_parse(merge);
-    if (!deferSearch) A.run_rest(merge);
-    b.graft.assign(n, 0);
-    b.recompSaved.assign(n, 0);
-    b.reoptIndex.assign(n, -1);
-    std::vector<size_t> ok;
-    for (size_t i = 0; i < n; i++)
-        if (A.streams[i].status == 0) ok.push_back(i);
-    if (mode == D4G_MODE_NONE || ok.empty()) { if (deferSearch) A.run_rest(merge); return D4G_OK; }
-    const double tc0 = now_ms();
-    // stream.getUncompressedData() -> compUtil.compress(uncompressed, true) — :83-84; the decoded bytes stay in HBM
-    std::vector<const uint8_t*> rp(ok.size());
-    std::vector<size_t> rl(ok.size());
-    for (size_t k = 0; k < ok.size(); k++) { rp[k] = A.dU + A.streams[ok[k]].uBase; rl[k] = (size_t)A.streams[ok[k]].nU; }
-    CompressRun R;
-    compress_run(R, ok.size(), rp.data(), rl.data(), true, mode, iter, merge, deferSearch ? std::function<void()>([&]() { A.run_rest(merge); }) : std::function<void()>());
-    double t1 = now_ms();
-    // new DeflateStream().parse(recompressed); recompStream.optimise(mergeBlocks) — :85-89
-    std::vector<const uint8_t*> wp(ok.size());
-    std::vector<size_t> wl(ok.size());
-    for (size_t k = 0; k < ok.size(); k++) { wp[k] = R.dWin + R.off[k]; wl[k] = R.len[k]; }
-    b.reopt.reset(new Batch());
-    b.reopt->create(ok.size(), wp.data(), wl.data(), true);
-    b.reopt->run(merge);
-    for (size_t k = 0; k < ok.size(); k++) {
-        const HStream& a = A.streams[ok[k]];
-        const HStream& c2 = b.reopt->streams[k];
-        b.reoptIndex[ok[k]] = (int)k;
-        if (c2.status != 0) continue;                  // recompStream.parse failed: the original stays (:88)
-        // recompStream.getSizeBits() / stream.getSizeBits() of the optimised streams (DeflateStream.java:171-182): the
-        // written sizes, in which a stored block's padding follows its new position (sizeBitsIn - saved does not)
-        long long recompSize = c2.outBits, originalSize = a.outBits;
-        if (recompSize < originalSize) {               // :94-98
-            b.graft[ok[k]] = 1;
-            b.recompSaved[ok[k]] = originalSize - recompSize;
-        }
-    }
-    const d4g_stats& es = R.agg;
-    A.stats.ms_lz_sort = es.ms_lz_sort; A.stats.ms_lz_parse = es.ms_lz_parse; A.stats.ms_lz_emit = es.ms_lz_emit;
-    A.stats.lz_parse_passes = es.lz_parse_passes; A.stats.lz_chunks_rerun = es.lz_chunks_rerun; A.stats.lz_symbols = es.lz_symbols;
-    A.stats.ms_recompress_encode = t1 - tc0 - (deferSearch ? A.stats.ms_total - A.stats.ms_parse : 0.0);
-    A.stats.ms_recompress_encode_front = es.ms_parse;
-    A.stats.ms_recompress_encode_search = es.ms_optimise + es.ms_merge;
-    A.stats.ms_recompress_reoptimise = now_ms() - t1;
-    A.stats.recompress_outputs = R.outputsOptimised;
-    A.stats.recompress_outputs_pruned = R.outputsPruned;
-    A.stats.ms_zopfli_table = R.msZfTable; A.stats.ms_zopfli_split = R.msZfSplit; A.stats.ms_zopfli_squeeze = R.msZfSqueeze; A.stats.ms_zopfli_emit = R.msZfEmit;
-    A.stats.zopfli_blocks = R.zfBlocks; A.stats.zopfli_position_iterations = R.zfPosIter;
-    const d4g_stats* chained[2] = {&es, &b.reopt->stats};
-    for (const d4g_stats* o : chained) {   // the same kernels ran in the chained batches: one set of counters
-        A.stats.ms_state_kernels += o->ms_state_kernels; A.stats.state_launches += o->state_launches;
-        A.stats.state_tokens_per_round += o->state_tokens_per_round; A.stats.state_bytes_per_round += o->state_bytes_per_round;
-        A.stats.kernel_launches += o->kernel_launches; A.stats.rounds += o->rounds;
-        A.stats.ms_search_kernels += o->ms_search_kernels; A.stats.ms_parse_kernels += o->ms_parse_kernels;
-    }
-    A.stats.search_bytes_algorithmic += es.search_bytes_algorithmic + b.reopt->stats.search_bytes_algorithmic;
-    return D4G_OK;
-}
-}  // namespace
-
-extern "C" {
-
+// ---- recompression (d4g_host_recompress.h) ----
 int d4g_compress(size_t n, const uint8_t* const* raw, const size_t* raw_len, int mode, int iter, int merge_blocks, uint8_t** out,
                  size_t* out_len, int32_t* winner) {
     if (n && (!raw || !raw_len || !out || !out_len)) return fail(D4G_ERR_ARG, "null argument");
     Outputs o(n, out, out_len, nullptr, nullptr, nullptr, winner);
     return o.commit(api(nullptr, [&] {
-        std::vector<LzSpec> probe;
-        std::string why;
-        if (!mode_specs(mode, probe, why)) return fail(D4G_ERR_ARG, why);
+        const std::string why = mode_refusal(mode);
+        if (!why.empty()) return fail(D4G_ERR_ARG, why);
         CompressRun R;
         compress_run(R, n, raw, raw_len, false, mode, iter, merge_blocks != 0);
         if (verify_switch()) {
             ZfUpload up(n, raw, raw_len);
-            if (int rc = verify_loose(n, [&](size_t i) { return (const uint8_t*)(R.dWin + R.off[i]); }, [&](size_t i) { return R.len[i]; },
-                                      [&](size_t i) { return up.ptr[i]; }, raw_len, "d4g_compress")) return rc;
+            std::vector<VerifyItem> items(n);
+            for (size_t i = 0; i < n; i++) { items[i].bytes = R.win.p[i]; items[i].len = R.win.len[i]; items[i].want = up.ptr[i]; items[i].wantLen = (i64)raw_len[i]; }
+            if (int rc = verify_loose(items, "d4g_compress")) return rc;
         }
         for (size_t i = 0; i < n; i++) {
-            out[i] = host_copy(R.dWin + R.off[i], R.len[i]);
-            out_len[i] = R.len[i];
+            out[i] = host_copy(R.win.p[i], R.win.len[i]);
+            out_len[i] = R.win.len[i];
             if (winner) winner[i] = (int32_t)R.winner[i];
         }
         return D4G_OK;
@@ -1326,8 +937,8 @@ int d4g_batch_run_recompress(d4g_batch* b, int mode, int iter, int merge_blocks)
 
 int d4g_batch_recompress_result(d4g_batch* b, size_t i, int32_t* grafted, int64_t* recompress_saved) {
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
-    if (grafted) *grafted = i < b->graft.size() ? b->graft[i] : 0;
-    if (recompress_saved) *recompress_saved = i < b->recompSaved.size() ? b->recompSaved[i] : 0;
+    if (grafted) *grafted = b->grafted(i);
+    if (recompress_saved) *recompress_saved = b->graft_saved(i);
     return D4G_OK;
 }
 
@@ -1366,9 +977,7 @@ int d4g_verify_streams(size_t n, const uint8_t* const* a, const size_t* a_len, c
     for (size_t i = 0; i < n; i++) { verdict[i] = D4G_VERIFY_SKIPPED; if (first_mismatch) first_mismatch[i] = -1; }
     return api(nullptr, [&] {
         std::unique_ptr<d4g_batch> A = make_batch(n, a, a_len);   // side a: parsed and decoded; its bytes stay in HBM
-        engine().init();
-        A->impl.parse_probe();
-        A->impl.build_blocks(false, false);
+        A->impl.parse_only(true);
         std::vector<VerifyItem> items;
         std::vector<size_t> index;
         for (size_t i = 0; i < n; i++) {
@@ -1404,8 +1013,7 @@ int d4g_diagnose_streams(size_t n, const uint8_t* const* in, const size_t* in_le
     for (size_t i = 0; i < n; i++) out[i] = PARSE_ERROR_NONE;
     return api(nullptr, [&] {
         std::unique_ptr<d4g_batch> b = make_batch(n, in, in_len);
-        engine().init();
-        b->impl.parse_probe();
+        b->impl.parse_only(false);
         for (size_t i = 0; i < n; i++) out[i] = batch_parse_error(*b, i);
         return D4G_OK;
     });
@@ -1443,9 +1051,7 @@ int d4g_recover_streams(size_t n, const uint8_t* const* in, const size_t* in_len
     Outputs o(n, out, out_len);
     const int rc = o.commit(api(nullptr, [&] {
         std::unique_ptr<d4g_batch> b = make_batch(n, in, in_len);
-        engine().init();
-        b->impl.parse_probe();
-        b->impl.build_blocks(false, false);
+        b->impl.parse_only(true);
         for (size_t i = 0; i < n; i++) {
             const uint8_t* src = batch_recovered(*b, i, &out_len[i]);
             out[i] = host_copy(src, out_len[i]);
@@ -1471,11 +1077,10 @@ const char* d4g_parse_reason_name(int reason) {   // (NULL, like the batch creat
 int d4g_debug_batch_poke_output(d4g_batch* b, size_t i, size_t byte_offset, uint8_t xor_mask) {
     if (!b || i >= b->impl.streams.size()) return fail(D4G_ERR_ARG, "bad stream index");
     if (!b->impl.dOut || b->impl.streams[i].status != 0) return fail(D4G_ERR_ARG, "stream has no output");
-    const Batch* owner = nullptr;
-    const HStream& f = b->final_stream(i, &owner);
-    if (byte_offset >= (size_t)((f.outBits + 7) / 8)) return fail(D4G_ERR_ARG, "offset outside the stream's output");
+    const DevBytes f = b->final_bytes(i);
+    if (byte_offset >= f.len) return fail(D4G_ERR_ARG, "offset outside the stream's output");
     return api(b, [&] {
-        uint8_t* at = (uint8_t*)(owner->dOut + f.outWordBase) + byte_offset;
+        uint8_t* at = (uint8_t*)f.p + byte_offset;
         uint8_t v = 0;
         rt_d2h(&v, at, 1);
         v ^= xor_mask;
